@@ -32,6 +32,20 @@ has):
 
 Inputs are resident in HBM before the timed region starts.  Rank 0 prints one
 JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the
+configuration).  Everything else the benchmark measures or checks runs only
+with --full: the cold step, per-kernel times and the roofline, the emulated
+N-GPU shards, the D2H-inclusive rates, the CPU baseline, the host-stream and
+BAM-file scopes, BASELINE.json's other configurations and, with N > 1, the
+compute / gather split, the check of the library's collective against
+torch.distributed's and the cohort side case.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the
+path receives it, to DIR/<name>.npy (float32 / float64, at most 64 MB; larger
+outputs as a fixed, seeded sample).  The inputs are seeded: the same arguments
+give the same inputs, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -86,6 +100,13 @@ def parse():
                          "and exit 0; without this flag such a run still prints its line and then exits with status 3 -- a fallback is never silent")
     ap.add_argument("--verify", action="store_true",
                     help="check one contig against the CPU oracle after timing")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the cold step, kernel times and roofline, emulated shards, CPU baseline, "
+                         "host-stream and BAM-file scopes, the other workloads (and with N > 1 the split, the collective "
+                         "check and the cohort case); the options above that tune those apply only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy "
+                         "(float32/float64, <= 64 MB in all, larger outputs as a fixed seeded sample)")
     return ap.parse_args()
 
 
@@ -487,9 +508,91 @@ def load_traffic(tag, kernel):
     return None
 
 
-def run_case(args, scaling, world, rank, dev, local_rank, want_streams=False):
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SEED = 20240611
+# what --dump-outputs writes: name -> (dtype, most cells).  A 2-D output keeps at most cells // row width rows
+# (callable_runs: 100 000 rows of 3, run_bounds: 150 000 of 2, depthwed: 1.2 M / samples).  float64 holds every int64
+# sum and every coordinate exactly, float32 every depth below 2**24.  The window arrays hold every window of the 3.1 Gb
+# genome at W = 1000; the arrays one run writes stay below DUMP_LIMIT_BYTES together (at most 55 MB: the cohort with
+# --cohort-outputs windows)
+DUMP_SPEC = {"window_sums": (np.float64, 3_200_000), "window_mins": (np.float32, 3_200_000),
+             "callable_runs": (np.float64, 300_000), "run_bounds": (np.float64, 300_000),
+             "perbase_sample": (np.float32, 1_000_000), "depthwed": (np.float64, 1_200_000)}
+
+
+def sample_rows(n, k, salt):
+    """Rows to keep of an output with n rows: None (all) when n <= k, else k sorted indices drawn from a generator
+    seeded by (DUMP_SEED, salt, n) -- the same rows for the same output shape in every run."""
+    if n <= k:
+        return None
+    return np.sort(np.random.default_rng([DUMP_SEED, salt, n]).integers(0, n, size=k))
+
+
+def _dump_entry(name, a, salt, row_cells=1):
+    dtype, cap = DUMP_SPEC[name]
+    idx = sample_rows(a.shape[0], max(1, cap // row_cells), salt)
+    a = np.asarray(a if idx is None else a[idx])
+    if dtype == np.float32 and a.size and int(np.abs(a.astype(np.int64)).max()) >= (1 << 24):
+        raise SystemExit("bench.py --dump-outputs: %s holds values float32 cannot represent" % name)
+    return name, a.astype(dtype)
+
+
+def last_step_outputs(eng, dev, mine, lengths, perbase, sums_only, wed, gath, rank):
+    """What a caller of the timed path holds after its last step, [(name, float array)], larger outputs sampled
+    (DUMP_SPEC).  This rank's contigs (`mine`, in order): window sums, minima and coverage-class runs (start, end,
+    class), the per-base depth at seeded positions, the depthwed matrix (cohort).  One genome over N GPUs: what rank 0
+    gathered for the whole genome (window sums, minima, run boundaries); other ranks return None."""
+    import torch
+    from goleft_amd import shard
+    if gath is not None:
+        if rank != 0:
+            return None
+        g = shard.unpack_gathered(gath.result())
+        tids = sorted(g)
+        return [_dump_entry("window_sums", torch.cat([g[t]["sums"] for t in tids]).cpu().numpy(), 1),
+                _dump_entry("window_mins", torch.cat([g[t]["mins"] for t in tids]).cpu().numpy(), 2),
+                _dump_entry("run_bounds", torch.cat([g[t]["bounds"] for t in tids]).cpu().numpy(), 3, 2)]
+    if not mine:
+        return []
+    out = [_dump_entry("window_sums", np.concatenate([eng.window_sums(t) for t in mine]), 1)]
+    if not sums_only:
+        out.append(_dump_entry("window_mins", np.concatenate([eng.windows(t)[1] for t in mine]), 2))
+        out.append(_dump_entry("callable_runs", np.concatenate([eng.callable_runs(t) for t in mine]), 3, 3))
+    if perbase:
+        # seeded positions over this rank's contigs laid end to end, read on the device from the per-base vectors
+        ends = np.cumsum([lengths[t] for t in mine])
+        pick = sample_rows(int(ends[-1]), DUMP_SPEC["perbase_sample"][1], 4)
+        pick = np.arange(int(ends[-1])) if pick is None else pick
+        part = np.searchsorted(ends, pick, "right")
+        vals = []
+        for j, t in enumerate(mine):
+            local = pick[part == j] - (int(ends[j - 1]) if j else 0)
+            ptr, n = eng.device_perbase(t)
+            assert n >= lengths[t], (t, n, lengths[t])
+            view = shard.device_view(ptr, n, torch.int32, dev)
+            vals.append(view[torch.from_numpy(local).to(dev)].cpu().numpy())
+        out.append(_dump_entry("perbase_sample", np.concatenate(vals), 4))
+    if wed.get("ptr"):
+        rows, ns = wed["shape"]
+        m = shard.device_view(wed["ptr"], rows * ns, torch.int64, dev).view(rows, ns).cpu().numpy()
+        out.append(_dump_entry("depthwed", m, 5, ns))
+    return out
+
+
+def write_outputs(path, arrays):
+    total = sum(a.nbytes for _, a in arrays)
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes, more than %d" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays:
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def run_case(args, scaling, world, rank, dev, local_rank, want_streams=False, dump_dir=None):
     """Set up one workload (weak: N-genome cohort, strong: one genome) on this
-    rank, time `steps` steps, return a dict of measurements."""
+    rank, time `steps` steps, return a dict of measurements.  With args.full also
+    the cold step, per-kernel times, the compute / gather split and the emulated
+    shards; dump_dir: the last timed step's outputs go there (rank 0)."""
     import torch
     import torch.distributed as dist
     from goleft_amd import shard, synth
@@ -574,7 +677,7 @@ def run_case(args, scaling, world, rank, dev, local_rank, want_streams=False):
     # fresh context -> gd_adopt_device (above) -> ONE gd_compute with the default max_span_hint.  Device allocations
     # of the result arrays (gd_compute_timing's prepare share) are reported separately: `ms` is the rest.
     first = None
-    if world == 1:
+    if world == 1 and args.full:
         eng.set_profiling(True)
         t1 = time.perf_counter()
         eng.compute()
@@ -645,7 +748,7 @@ def run_case(args, scaling, world, rank, dev, local_rank, want_streams=False):
         gath.attach(eng)
         gath.fallback_note = native_note
         gath.comm_lib = comm_lib
-        if native:
+        if native and args.full:
             # one step through EACH collective before anything is timed: what rank 0 received through the library's
             # gather must be what torch.distributed's gather delivers for the same export blocks
             eng.compute(); gath.step_exported(); gath.drain()
@@ -674,7 +777,8 @@ def run_case(args, scaling, world, rank, dev, local_rank, want_streams=False):
             # the sites x samples matrix of this rank's samples, left in HBM for its consumer
             # (the D2H of the whole matrix is timed separately, below -- never part of `value`)
             tids = np.asarray(mine, np.int32).reshape(-1, 1)
-            wed["shape"] = [eng.depthwed_device(tids, args.wed_size)[1], len(mine)]
+            wed["ptr"], rows = eng.depthwed_device(tids, args.wed_size)
+            wed["shape"] = [rows, len(mine)]
         if exchange:
             gath.step_exported()                    # ONE asynchronous collective on the buffer this compute filled;
                                                     # the next compute fills the other one (no allocation)
@@ -716,9 +820,14 @@ def run_case(args, scaling, world, rank, dev, local_rank, want_streams=False):
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if dump_dir:
+        got = last_step_outputs(eng, dev, mine, lengths, not cohort and os.environ.get("GOLEFT_BENCH_OUTPUTS") != "windows",
+                                cohort and args.cohort_outputs == "sums", wed, gath, rank)
+        if got is not None and rank == 0:
+            write_outputs(dump_dir, got)
     # kernel durations (HIP events on the engine's stream): the same steps again, profiled, after the timed region
     tile_ms, prep_ms, runs_ms, expand_ms, scan_ms, ckpt_ms, norm_ms = [], [], [], [], [], [], []
-    for _ in range(args.steps):
+    for _ in range(args.steps if args.full else 0):
         eng.set_profiling(True)                     # (also clears the accumulating NORM / CKPT timers)
         step()
         tile_ms.append(eng.kernel_ms(K_TILE))
@@ -742,7 +851,7 @@ def run_case(args, scaling, world, rank, dev, local_rank, want_streams=False):
         dt = float(tt.item())
 
     split = None
-    if exchange:
+    if exchange and args.full:
         # where a step goes, measured AFTER the timed loop with a synchronisation between the two
         # halves (the timed loop itself has none): gd_compute wall, then the gather until it has landed
         tc, tg = [], []
@@ -783,7 +892,7 @@ def run_case(args, scaling, world, rank, dev, local_rank, want_streams=False):
 
     # ---- the N-GPU job's shards, one after the other on this device (a measured stand-in for the scaling curve) ----
     emu = None
-    if world == 1 and args.emulate_shards and not cohort:
+    if world == 1 and args.full and args.emulate_shards and not cohort:
         emu = {}
         for N in [int(x) for x in args.emulate_shards.split(",") if x.strip()]:
             if N < 2 or N > len(lengths):
@@ -824,16 +933,22 @@ def run_case(args, scaling, world, rank, dev, local_rank, want_streams=False):
         "mine": mine, "dt": dt, "total_bases": sum(lengths), "my_bases": my_bases,
         "my_windows": my_windows, "n_reads": n_reads, "n_ops": n_ops, "wname": wname,
         "n_samples": n_samples, "W": W, "Q": Q, "mincov": mincov,
-        "tile_ms": float(np.mean(tile_ms)), "prep_ms": float(np.mean(prep_ms)),
-        "runs_ms": float(np.mean(runs_ms)), "tile_positions": st.tile_positions, "lookback": st.lookback,
-        "expand_ms": float(np.mean(expand_ms)), "scan_ms": float(np.mean(scan_ms)), "path": int(st.path),
-        "ckpt_ms": float(np.mean(ckpt_ms)), "norm_ms": float(np.mean(norm_ms)), "derive": derive,
+        "tile_ms": _mean(tile_ms), "prep_ms": _mean(prep_ms),
+        "runs_ms": _mean(runs_ms), "tile_positions": st.tile_positions, "lookback": st.lookback,
+        "expand_ms": _mean(expand_ms), "scan_ms": _mean(scan_ms), "path": int(st.path),
+        "ckpt_ms": _mean(ckpt_ms), "norm_ms": _mean(norm_ms), "derive": derive,
         "n_canonical_ops": incl_canon, "n_slow_tiles": incl_slow, "kernel": TK_NAMES[incl_kernel],
         "perbase": not cohort, "wed_shape": wed.get("shape"), "split": split, "emu": emu, "first": first,
+        "collective_fallback_reason": (getattr(gath, "fallback_note", "") or None) if exchange else None,
     }
     if not want_streams:
         streams.clear()
     return res
+
+
+def _mean(xs):
+    """Mean of the profiled steps' kernel times; None when none ran (a run without --full)."""
+    return float(np.mean(xs)) if xs else None
 
 
 def roofline_of(r, args, world):
@@ -1093,6 +1208,8 @@ def main():
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     if os.environ.get("GOLEFT_BENCH_STUB") == "1":
         return stub_rank(args, world, rank)
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     import torch
     import torch.distributed as dist
     from goleft_amd import synth
@@ -1122,26 +1239,24 @@ def main():
         raise SystemExit("bench.py --gpus %d: the %d ranks sit on %d distinct device(s) %s -- not an %d-GPU run"
                          % (args.gpus, world, took_part["distinct_devices"], took_part["devices_seen"], world))
 
-    r = run_case(args, args.scaling, world, rank, dev, local_rank, want_streams=True)
+    r = run_case(args, args.scaling, world, rank, dev, local_rank, want_streams=True, dump_dir=args.dump_outputs)
     eng, streams, names, lengths, mine = r["eng"], r["streams"], r["names"], r["lengths"], r["mine"]
     dt, W, Q, mincov = r["dt"], r["W"], r["Q"], r["mincov"]
     value = r["total_bases"] * args.steps / dt
-    rf = roofline_of(r, args, world)
-    raw_records, scatter, chunk = rf["raw_records"], rf["scatter"], rf["chunk"]
-    avg_tile_s, traffic, tr, kname = rf["avg_tile_s"], rf["traffic"], rf["tr"], rf["kernel"]
-    ops_read, alg_bytes, alg_bytes_read, achieved = rf["ops_read"], rf["alg_bytes"], rf["alg_bytes_read"], rf["achieved"]
+    scatter, chunk, raw_records = r["path"] == 2, r["path"] == 3, r["kernel"].endswith("<raw>")
 
-    # PCIe-inclusive rate (results to host) -- reported, never `value`
-    t1 = time.perf_counter()
-    sums_only = args.workload == "cohort" and args.cohort_outputs == "sums"
-    for t in mine[:48]:
-        eng.window_sums(t) if sums_only else eng.windows(t)
-    d2h = (time.perf_counter() - t1) * (len(mine) / max(1, min(len(mine), 48)))
-    d2h_matrix = None
-    if args.workload == "cohort":
+    d2h = d2h_matrix = None
+    if args.full:
+        # PCIe-inclusive rate (results to host) -- reported, never `value`
         t1 = time.perf_counter()
-        eng.depthwed(np.asarray(mine, np.int32).reshape(-1, 1), args.wed_size)
-        d2h_matrix = time.perf_counter() - t1
+        sums_only = args.workload == "cohort" and args.cohort_outputs == "sums"
+        for t in mine[:48]:
+            eng.window_sums(t) if sums_only else eng.windows(t)
+        d2h = (time.perf_counter() - t1) * (len(mine) / max(1, min(len(mine), 48)))
+        if args.workload == "cohort":
+            t1 = time.perf_counter()
+            eng.depthwed(np.asarray(mine, np.int32).reshape(-1, 1), args.wed_size)
+            d2h_matrix = time.perf_counter() - t1
 
     out = {
         "metric": ("ref bases/sec per-base depth, 20x ONT-like synthetic" if args.workload.startswith("ont")
@@ -1174,7 +1289,6 @@ def main():
                             "records as they arrived] + gd_compute" if r["derive"] else
                             "gd_compute on the records as they arrived (nothing derived exists)" if raw_records else
                             "gd_compute") + (" + gd_depthwed_device" if args.workload == "cohort" else ""),
-                   "in_step_normalise_kernels_ms_rank0": r["norm_ms"], "in_step_checkpoint_kernels_ms_rank0": r["ckpt_ms"],
                    "sharding": ("single GPU" if world == 1 else
                                 "by sample (one genome per GPU, no exchange)" if args.scaling == "weak" else
                                 "by chromosome, LPT, RCCL gather of window sums/minima + class runs to rank 0"),
@@ -1184,10 +1298,14 @@ def main():
                               (" + depthwed matrix %s" % r["wed_shape"] if r["wed_shape"] else ""),
                    "tile_positions": r["tile_positions"], "lookback": r["lookback"],
                    "device_path": "scatter" if scatter else "chunk" if chunk else "tile"},
-        "roofline": rf["roofline"],
-        "kernels_ms": rf["kernels_ms"],
-        "with_d2h_windows_ref_bases_per_s": r["my_bases"] / (dt / args.steps + d2h) if world == 1 else None,
     }
+    if args.full:
+        rf = roofline_of(r, args, world)
+        out["config"]["in_step_normalise_kernels_ms_rank0"] = r["norm_ms"]
+        out["config"]["in_step_checkpoint_kernels_ms_rank0"] = r["ckpt_ms"]
+        out["roofline"] = rf["roofline"]
+        out["kernels_ms"] = rf["kernels_ms"]
+        out["with_d2h_windows_ref_bases_per_s"] = r["my_bases"] / (dt / args.steps + d2h) if world == 1 else None
     if r.get("first"):
         out["first_compute"] = dict(r["first"], warm_ms_per_step=dt / args.steps * 1e3,
                                     ratio_to_warm=r["first"]["ms"] / (dt / args.steps * 1e3))
@@ -1199,7 +1317,7 @@ def main():
                     "asynchronous collective of gather_bytes_per_rank per rank to rank 0, issued under the next step's "
                     "kernels) is not in it: no second GPU here",
             "by_n_gpus": r["emu"]}
-    if world == 1 and args.workload != "cohort":
+    if args.full and world == 1 and args.workload != "cohort":
         from goleft_amd import shard as _sh
         # checksum of checksums: equals "split.gathered_sum_of_window_sums" of an N > 1 run of the same workload
         out["sum_of_window_sums"] = int(_sh.local_results(eng, dev)[0].sum().item())
@@ -1230,13 +1348,13 @@ def main():
         if bad:
             out["verified_mismatch"] = bad
 
-    if rank == 0 and world == 1 and not args.no_host_stream and args.workload in ("wgs", "chr20"):
+    if args.full and rank == 0 and world == 1 and not args.no_host_stream and args.workload in ("wgs", "chr20"):
         out["host_stream_scope"] = host_stream_scope(local_rank, W, Q, mincov, opts=args.opt)
         if args.workload == "wgs":
             # the genome-sized run needs the HBM the resident streams hold: measured after they are released (below)
             out["host_stream_scope_wgs"] = "pending"
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:      # a reported baseline, N = 1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:      # a reported baseline, N = 1 only
         from oracle import pyoracle as po
         cores = usable_cpus()                     # threads actually used: what the container's CPU quota lets run at once
         sample = []
@@ -1261,6 +1379,7 @@ def main():
             "value": v1, "unit": "ref-bases/s", "cores": 1,
             "sample": "%s (%d ref bases), one thread, %.1f s" % (sample[-1][0], b1, sec1)}
     r_split = r["split"]
+    fb = r["collective_fallback_reason"]
     eng.close()
     streams.clear()
     del r
@@ -1271,12 +1390,12 @@ def main():
         except Exception as e:                       # never lose the headline line to a side measurement
             out["host_stream_scope_wgs"] = {"error": "%s: %s" % (type(e).__name__, e)}
 
-    if rank == 0 and world == 1 and args.workload == "wgs" and args.other_workloads.strip():
+    if args.full and rank == 0 and world == 1 and args.workload == "wgs" and args.other_workloads.strip():
         torch.cuda.empty_cache()
         which_w = [w for w in (x.strip() for x in args.other_workloads.split(",")) if w in ("chr20", "ont", "ont-chr20", "cohort")]
         out["other_workloads"] = other_workloads(args, dev, local_rank, which_w)
 
-    if rank == 0 and world == 1 and args.workload == "wgs" and args.bam_scope != "off":
+    if args.full and rank == 0 and world == 1 and args.workload == "wgs" and args.bam_scope != "off":
         which = args.bam_scope
         if which == "auto":
             which = "genome" if (os.cpu_count() or 1) >= 64 else "chr20-21"
@@ -1338,7 +1457,7 @@ def main():
         out["split"] = r_split
     # N > 1: the headline is ONE genome over N GPUs (BASELINE.json config 3); the cohort case (N genomes,
     # one per GPU, no exchange) is reported next to it
-    if world > 1 and args.scaling == "strong" and args.workload in ("wgs", "ont") and \
+    if args.full and world > 1 and args.scaling == "strong" and args.workload in ("wgs", "ont") and \
             not os.environ.get("GOLEFT_BENCH_SKIP_COHORT"):     # (dry runs on the 1-GPU box skip the side case)
         try:
             torch.cuda.empty_cache()
@@ -1355,7 +1474,7 @@ def main():
     if world > 1:
         torch.cuda.empty_cache()
         dist.barrier()                                  # every rank has closed its engine: the devices are free
-        file_ngpu = args.workload == "wgs" and args.scaling == "strong" and not single and \
+        file_ngpu = args.full and args.workload == "wgs" and args.scaling == "strong" and not single and \
             os.environ.get("GOLEFT_BENCH_SKIP_FILE_NGPU") != "1"
         store = None
         if file_ngpu:
@@ -1393,7 +1512,6 @@ def main():
     if rank == 0:
         print(json.dumps(out), flush=True)
     # a fallback is never silent: the line is out, the status says what it was measured with
-    fb = (r_split or {}).get("collective_fallback_reason") if world > 1 else None
     if fb and fb != "asked for" and not args.allow_gather_fallback:
         if rank == 0:
             print("bench.py: the library's collective (gd_gather_export) was NOT used -- %s; the line above was measured with torch.distributed's "

@@ -1,5 +1,5 @@
 """CPU: the bench line the driver parses.  The latest committed bench line (profiles/r*_bench_wgs_n1.json,
-written by bench.py on an MI355X) must carry every field of the contract, with BASELINE.json's metric."""
+written by `bench.py --full` on an MI355X) must carry every field of the contract, with BASELINE.json's metric."""
 import glob
 import json
 import os
@@ -142,3 +142,21 @@ def test_reference_children_hook_runs_with_a_samtools_on_path(tmp_path, monkeypa
     assert "3 tiles" in out["sample"]
     monkeypatch.setenv("SAMTOOLS", os.path.join(bench.ROOT, "goleft_amd", "shim", "samtools"))
     assert bench.real_samtools() is None
+
+
+def test_dumped_outputs_fit_the_limit_and_their_samples_are_fixed():
+    """--dump-outputs: the arrays one run can write stay under 64 MB together, and a sampled output keeps the same rows
+    in every run (a generator seeded by the output's shape)."""
+    import importlib
+    import numpy as np
+    bench = importlib.import_module("bench")
+    size = {k: np.dtype(t).itemsize * n for k, (t, n) in bench.DUMP_SPEC.items()}
+    runs = {"window_sums", "window_mins", "callable_runs"}
+    for case in (runs | {"perbase_sample"}, runs | {"depthwed"}, {"window_sums", "depthwed"},
+                 {"window_sums", "window_mins", "run_bounds"}):
+        assert sum(size[k] for k in case) <= bench.DUMP_LIMIT_BYTES <= 64_000_000, case
+    assert bench.sample_rows(1000, 1000, 1) is None
+    a, b = bench.sample_rows(3_095_677_412, 1_000_000, 4), bench.sample_rows(3_095_677_412, 1_000_000, 4)
+    assert np.array_equal(a, b) and len(a) == 1_000_000 and np.all(a[1:] >= a[:-1]) and a[-1] < 3_095_677_412
+    name, arr = bench._dump_entry("callable_runs", np.arange(3 * 400_000, dtype=np.int32).reshape(-1, 3), 3, 3)
+    assert arr.dtype == np.float64 and arr.shape == (bench.DUMP_SPEC["callable_runs"][1] // 3, 3)

@@ -73,3 +73,13 @@ def test_the_json_line_is_the_last_thing_on_a_piped_stdout():
     assert r.returncode == 0, r.stderr[-500:]
     lines = r.stdout.strip().splitlines()
     assert lines[-1] == '{"metric": "x"}' and "Librccl path : banner" in lines[:-1], lines
+
+
+def test_full_and_dump_outputs_are_accepted_and_steps_reach_the_line(tmp_path):
+    # the stub returns before the engine: what is checked here is only that the options parse and --steps / --warmup
+    # reach the line; tests/test_gpu_bench_outputs.py counts the computes inside the clock of a real run
+    p = _run(["--gpus", "1", "--steps", "7", "--warmup", "2", "--full", "--dump-outputs", str(tmp_path / "o")],
+             {"GOLEFT_BENCH_STUB": "1"})
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads(p.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] >= 0

@@ -9,7 +9,11 @@ from hypothesis import given, settings, strategies as st
 from oracle import pyoracle as po
 from tests import helpers as H
 
-REF_TEST = "/root/reference/depth/test"
+REF_TEST = os.path.join(H.GOLDEN, "ref")    # byte copies of the reference's depth/test fixture BAMs
+# SHA-256 of the reference's own depth/test/{t,hla,t-empty}.bam: the copies above are those files, byte for byte
+REF_BAM_SHA256 = {"t": "e3a9c167ecec96a7434ec97ebe5cdf1a756f0d9859c92c7c60c7cd8d53c7a4ee",
+                  "hla": "c8d4b8d8f016e99c4b50bef1483e057b9fe750700d45f2be2694948d9c161f93",
+                  "t-empty": "9beb2092b1946d8cfcef0e8ba768be027f7f94504974ec22073b0a72b53e519b"}
 
 
 def test_survey_known_answers_t_bam():
@@ -155,11 +159,14 @@ def test_perbase_random_cigars(seed):
     assert np.array_equal(po.perbase_numpy(r, 1, s, e), want)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_TEST), reason="reference fixtures only exist in the build container")
 def test_golden_streams_match_reference_bams():
+    import hashlib
     from oracle import bamio
     for name, key in (("t", "t"), ("hla", "hla"), ("t-empty", "t_empty")):
-        _, contigs, reads, total = bamio.read_bam(os.path.join(REF_TEST, name + ".bam"))
+        path = os.path.join(REF_TEST, name + ".bam")
+        with open(path, "rb") as fh:
+            assert hashlib.sha256(fh.read()).hexdigest() == REF_BAM_SHA256[name], path
+        _, contigs, reads, total = bamio.read_bam(path)
         gc, gr, z = H.load_golden_bam(key)
         assert contigs == gc and int(z["n_records_total"]) == total
         assert set(reads) == set(gr)

@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 run() {   # name, env...
   local name=$1; shift
   local out=$R/gpurun_out/prof_l2_cohort_$name; rm -rf $out; mkdir -p $out
-  local cmd="python $R/bench.py --no-cpu-baseline --no-host-stream --bam-scope off --other-workloads= --emulate-shards= --steps 3 --warmup 1 --workload cohort"
+  local cmd="python $R/bench.py --full --no-cpu-baseline --no-host-stream --bam-scope off --other-workloads= --emulate-shards= --steps 3 --warmup 1 --workload cohort"
   env "$@" rocprofv3 --kernel-trace --pmc FETCH_SIZE TCC_MISS_sum TCP_TCC_READ_REQ_sum --output-format csv -d $out/pmc1 -- $cmd > $out/pmc1.log 2>&1
   grep '^{' $out/pmc1.log | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$name: step ms', round(d['ms_per_step'],2), 'kernel ms', round(d['roofline']['avg_kernel_ms'],2), 'bytes read', d['roofline']['bytes_really_read_per_launch'])"
   for f in $(find $out -name "*counter_collection.csv"); do { head -1 $f; grep "gd::" $f; } > $f.tmp && mv $f.tmp $f; done

@@ -1,11 +1,13 @@
 #!/bin/bash
-# One GPU-box session (run through gpurun): stages given as arguments, in order; logs and JSON lines under gpurun_out/.
+# One GPU-box session: stages given as arguments, in order; logs and JSON lines under $GD_OUT_DIR (default: a new
+# temporary directory, printed at the end).
 #   tools/gpu.sh <tag> [tests [pytest args]] [bench:<workload>[:extra bench args]] [prof:<workload>] [cmd:<shell command>] ...
 # e.g. tools/gpu.sh r03a tests bench:wgs bench:chr20 "bench:ont:--steps 5 --warmup 2" prof:wgs
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 T=$1; shift
-mkdir -p gpurun_out
-LOG=gpurun_out/${T}.log
+O=${GD_OUT_DIR:-$(mktemp -d)}
+mkdir -p $O
+LOG=$O/${T}.log
 : > $LOG
 summ='import sys,json
 d=json.loads(sys.stdin.read())
@@ -27,14 +29,14 @@ for st in "$@"; do
     tests*)
       what=${st#tests}; case "$what" in *tests/*) ;; *) what="tests $what";; esac      # "tests" = the whole directory; "tests tests/x.py -k y" = just that
       echo "== pytest -m gpu $what" >> $LOG
-      timeout 1500 python -X faulthandler -m pytest -m gpu --maxfail=8 -q $what > gpurun_out/${T}_pytest.txt 2>&1
-      grep -n "Fatal\|fault\|tests/.*line\|passed\|failed\|Error" gpurun_out/${T}_pytest.txt | head -30 >> $LOG
-      tail -5 gpurun_out/${T}_pytest.txt >> $LOG ;;
+      timeout 1500 python -X faulthandler -m pytest -m gpu --maxfail=8 -q $what > $O/${T}_pytest.txt 2>&1
+      grep -n "Fatal\|fault\|tests/.*line\|passed\|failed\|Error" $O/${T}_pytest.txt | head -30 >> $LOG
+      tail -5 $O/${T}_pytest.txt >> $LOG ;;
     bench:*)
       w=${st#bench:}; extra=""; case "$w" in *:*) extra=${w#*:}; w=${w%%:*};; esac
       echo "== bench $w $extra" >> $LOG
-      timeout 900 python bench.py --workload $w $extra 2>gpurun_out/${T}_$w.err | tail -1 > gpurun_out/${T}_bench_$w.json
-      python -c "$summ" < gpurun_out/${T}_bench_$w.json >> $LOG 2>&1 || tail -5 gpurun_out/${T}_$w.err >> $LOG ;;
+      timeout 900 python bench.py --full --workload $w $extra 2>$O/${T}_$w.err | tail -1 > $O/${T}_bench_$w.json
+      python -c "$summ" < $O/${T}_bench_$w.json >> $LOG 2>&1 || tail -5 $O/${T}_$w.err >> $LOG ;;
     prof:*)
       w=${st#prof:}; extra=""; case "$w" in *:*) extra=${w#*:}; w=${w%%:*};; esac
       echo "== prof $w $extra" >> $LOG
@@ -45,3 +47,4 @@ for st in "$@"; do
   esac
 done
 cat $LOG
+echo "outputs in $O"

@@ -8,7 +8,7 @@ cd /tmp 2>/dev/null && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 out=$R/gpurun_out/prof_$tag
 mkdir -p $out
-cmd="python $R/bench.py --no-cpu-baseline --no-host-stream --bam-scope off --other-workloads= --emulate-shards= --steps 5 --warmup 2 $@"
+cmd="python $R/bench.py --full --no-cpu-baseline --no-host-stream --bam-scope off --other-workloads= --emulate-shards= --steps 5 --warmup 2 $@"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- $cmd > $out/trace.log 2>&1
 # the same statistics over the WORKLOAD's launches (gd_create's warm-up dispatches left out): what a roofline is recomputed from
 python $R/tools/kernel_stats_trimmed.py $out/trace $out/kernel_stats_trimmed.csv > /dev/null 2>&1

@@ -54,7 +54,7 @@ res = {
     "hbm_bytes_per_launch": read_b + write_b,
     "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, tools/prof.sh), "
               "FETCH_SIZE doubled per the gfx950 correction of MI355X_MICROARCH.md; "
-              "python bench.py %s--no-cpu-baseline --no-host-stream --emulate-shards= --steps 5 --warmup 2" % (bench_args + " " if bench_args else ""),
+              "python bench.py %s--full --no-cpu-baseline --no-host-stream --emulate-shards= --steps 5 --warmup 2" % (bench_args + " " if bench_args else ""),
 }
 json.dump(res, open(out, "w"), indent=1)
 print(json.dumps(res))
