@@ -15,7 +15,17 @@
 //          and the double sum 0.5 + fl(D) truncates to the same integer.
 // Everything below is exact: two-product / FMA remainders decide the decimal
 // rounding, no table of decimal strings, no snprintf.  Compiles for host and
-// device (the host instance is the unit-tested one, tests/test_depthwed.py).
+// device (the host instance is unit-tested in tests/test_depthwed.py, the device
+// one in tests/test_gpu_depthwed_cells.py).
+//
+// The proofs hold for the operations AS WRITTEN, each rounded on its own.  HIP
+// clang fuses a multiply and a dependent add into one FMA across statements by
+// default: `r = hi - d0` after `hi = q * P` became fma(q, P, -d0), the exact
+// q*P - d0, which misses the x.5 tie that the rounded hi sits on and keeps the
+// wrong neighbour (123450 / 1000 gave 123, not 124).  So each function body
+// turns contraction off for itself (`#pragma clang fp contract(off)`); at file
+// scope it would also reach every kernel included after this header.
+// tests/test_depthwed_isa.py holds the compiled code to it.
 #pragma once
 
 #include <math.h>
@@ -30,6 +40,9 @@
 // q (>= 1000) rounded to 4 significant digits; exact integer result.
 GD_HD int64_t gd_round4g_big(double q)
 {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
     // largest k with 10^(k+3) <= q; powers of ten up to 1e22 are exact doubles
     double P = 1.0;                      // 10^k
     while (q >= P * 1e4) P *= 10.0;      // P * 1e4 is exact while P <= 1e18
@@ -45,6 +58,9 @@ GD_HD int64_t gd_round4g_big(double q)
 // The depthwed cell of one window: int(0.5 + parse(fmt("%.4g", sum/len))).
 GD_HD int64_t gd_depthwed_cell(int64_t sum, int64_t len)
 {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
     if (sum <= 0 || len <= 0) return 0;              // mean() returns 0 for an empty window
     const double q = (double)sum / (double)len;      // depth/depth.go:188 (sum < 2^53: exact operands)
     if (q < 0.1) return 0;                           // D <= 0.1000 -> 0 (0.1 here is the double just above 1/10)

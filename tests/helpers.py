@@ -99,6 +99,57 @@ def oracle_runs(depth, mincov, maxmean, step, start=0):
     return np.stack([s, e, cls[brk]], 1).astype(np.int32)
 
 
+def depthwed_tie_grid():
+    """(sums, lens) int64: window sums whose mean sits exactly on (or one unit of the sum away from) a 4-digit
+    rounding tie or a x.5 boundary of the depthwed cell, for every magnitude and a range of window lengths."""
+    sums, lens = [], []
+    for l in (1, 2, 4, 5, 8, 10, 20, 40, 125, 250, 1000, 2000, 16384):
+        for e in range(-1, 7):
+            for d in (1000, 1001, 1234, 1235, 4999, 5000, 5001, 9998, 9999):
+                for half in (0, 1):
+                    # mean ~ (d + half/2) * 10^(e-3)
+                    num = (2 * d + half) * 10 ** max(e, 0) * l
+                    den = 2 * 10 ** 3 * 10 ** max(-e, 0)
+                    base = num // den
+                    for delta in (-1, 0, 1):
+                        if base + delta >= 0:
+                            sums.append(base + delta)
+                            lens.append(l)
+    return np.array(sums, np.int64), np.array(lens, np.int64)
+
+
+def window_sum_reads(rng, length, W, sums, n_filtered=0):
+    """Records on one contig of `length` bases whose W-window sums (min_mapq 1, flag mask 0x704) are `sums`.
+    Every record stays inside its window: sum // len reads of `<len>M` at the window's start plus one of
+    `<sum % len>M`, len being the window's length (the last window is shorter).  n_filtered more records that
+    the filters drop (unmapped, secondary, QC-failed, duplicate, MAPQ 0) land at random places inside windows."""
+    sums = np.asarray(sums, np.int64)
+    nw = (length + W - 1) // W
+    assert sums.shape == (nw,) and (sums >= 0).all()
+    start = np.arange(nw, dtype=np.int64) * W
+    wlen = np.minimum(start + W, length) - start
+    assert (sums <= wlen * 200000).all()            # keeps the record count (about the mean) bounded
+    full, rem = sums // wlen, sums % wlen
+    pos = [np.repeat(start, full), start[rem > 0]]
+    span = [np.repeat(wlen, full), rem[rem > 0]]
+    flag = [np.zeros(int(full.sum()) + int((rem > 0).sum()), np.uint16)]
+    mapq = [np.full(flag[0].shape[0], 60, np.uint8)]
+    if n_filtered:
+        w = rng.integers(0, nw, size=n_filtered)
+        off = rng.integers(0, wlen[w])
+        pos.append(start[w] + off)
+        span.append(rng.integers(1, wlen[w] - off + 1))
+        kind = rng.integers(0, 5, size=n_filtered)
+        flag.append(np.array([0x4, 0x100, 0x200, 0x400, 0], np.uint16)[kind])
+        mapq.append(np.where(kind == 4, 0, 60).astype(np.uint8))
+    pos, span = np.concatenate(pos), np.concatenate(span)
+    flag, mapq = np.concatenate(flag), np.concatenate(mapq)
+    order = np.argsort(pos, kind="stable")
+    n = pos.shape[0]
+    return po.Reads(pos[order].astype(np.int32), flag[order], mapq[order], np.arange(n + 1, dtype=np.uint32),
+                    (span[order].astype(np.uint32) << 4))             # one M op per record
+
+
 def ref_span(r):
     """Reference bases each record's CIGAR consumes (M, D, N, =, X), per read."""
     consumes = np.array([1, 0, 1, 1, 0, 0, 0, 1, 1, 0, 0, 0, 0, 0, 0, 0], np.int64)

@@ -61,20 +61,8 @@ def test_cell_random_against_printf(seed):
 def test_cell_ties_and_boundaries():
     """Means sitting exactly on (or one unit of the sum away from) a 4-digit
     rounding tie or a x.5 boundary, for every magnitude."""
-    sums, lens = [], []
-    for l in (1, 2, 4, 5, 8, 10, 20, 40, 125, 250, 1000, 2000, 16384):
-        for e in range(-1, 7):
-            for d in (1000, 1001, 1234, 1235, 4999, 5000, 5001, 9998, 9999):
-                for half in (0, 1):
-                    # mean ~ (d + half/2) * 10^(e-3)
-                    num = (2 * d + half) * 10 ** max(e, 0) * l
-                    den = 2 * 10 ** 3 * 10 ** max(-e, 0)
-                    base = num // den
-                    for delta in (-1, 0, 1):
-                        if base + delta >= 0:
-                            sums.append(base + delta)
-                            lens.append(l)
-    s = np.array(sums, np.int64); l = np.array(lens, np.int64)
+    s, l = H.depthwed_tie_grid()
+    assert len(s) == 5564
     assert np.array_equal(cells_c(s, l), cells_py(s, l))
 
 
