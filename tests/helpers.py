@@ -72,6 +72,62 @@ def long_cigar_reads(rng, length, n_ops_list, max_step=40, skip_every=0):
     return po.Reads(pos, flag, mapq, off, cigar)
 
 
+# MAPQ bytes where a kernel's byte handling goes wrong: the sign bit of a byte (127 / 128 / 129) and SAM's
+# "MAPQ unavailable" (255), which `samtools depth -Q` still compares as a number
+EDGE_MAPQ = (0, 1, 127, 128, 129, 254, 255)
+# flag_mask values no longer than the 16-bit flag field (0x8000: its sign bit)
+EDGE_FLAG_MASKS = (0x704, 0, 0x8000, 0x800, 0xFFFF, 0xFFFFFFFF)
+# op codes that consume no reference, none of them counted: I S H P and the unassigned codes 9-15
+NON_CONSUMING_OPS = (1, 4, 5, 6, 9, 10, 11, 12, 13, 14, 15)
+
+
+def edge_reads(rng, length, n, max_ops=7, max_len=300, long_ops=0):
+    """Records that reach the edges of the read filter and of the CIGAR encoding: MAPQ over 0-255 with weight on
+    EDGE_MAPQ; flags over the whole 16-bit field (every single bit, 0xFFFF, the subsets of 0x704, uniform values);
+    every op code 0-15, zero-length ops, and non-consuming ops (I S H P, 9-15) of up to 2^28 - 1 bases; reads of
+    0, 1, 2 and up to max_ops ops, at sorted positions over the whole contig (some hang over its end).
+    long_ops > 0 adds one more read of that many ops (every code, lengths 0-3) at a position in the first half.
+    No two-op read is `0S <n>N`: with SEQ '*' that is SAM's placeholder of a CIGAR stored in the CG tag."""
+    n_long = 1 if long_ops else 0
+    pos = np.sort(rng.integers(0, max(1, length), size=n + n_long)).astype(np.int32)
+    nops = rng.choice(np.arange(max_ops + 1), size=n + n_long,
+                      p=[0.02, 0.38, 0.3] + [0.3 / (max_ops - 2)] * (max_ops - 2))
+    if n_long:
+        k = int(np.searchsorted(pos, length // 2))
+        nops[int(rng.integers(0, max(1, k)))] = long_ops
+    off = np.zeros(n + n_long + 1, np.uint32)
+    off[1:] = np.cumsum(nops)
+    m = int(off[-1])
+    p = np.array([0.35, 0.05, 0.06, 0.03, 0.08, 0.04, 0.03, 0.06, 0.06] + [0.24 / 7] * 7)
+    ops = rng.choice(16, size=m, p=p / p.sum())
+    lens = rng.integers(0, max_len, size=m)
+    lens[rng.random(m) < 0.05] = 0
+    huge = np.isin(ops, NON_CONSUMING_OPS) & (rng.random(m) < 0.15)
+    lens[huge] = rng.choice([(1 << 28) - 1, (1 << 28) - 2, 1 << 27, 1 << 22], size=int(huge.sum()))
+    if n_long:
+        i = int(np.flatnonzero(nops == long_ops)[0])
+        a, b = int(off[i]), int(off[i + 1])
+        ops[a:b] = np.arange(b - a) % 16
+        rng.shuffle(ops[a:b])
+        lens[a:b] = rng.integers(0, 4, size=b - a)
+    two = np.flatnonzero(nops == 2)
+    first = off[two].astype(np.int64)
+    ph = first[(ops[first] == 4) & (lens[first] == 0) & (ops[first + 1] == 3)]
+    lens[ph] = 1
+    cigar = ((lens.astype(np.uint32) << 4) | ops.astype(np.uint32)).astype(np.uint32)
+
+    N = n + n_long
+    kind = rng.choice(5, size=N, p=[0.2, 0.4, 0.15, 0.1, 0.15])
+    single = (1 << rng.integers(0, 16, size=N)).astype(np.int64)
+    sub704 = np.array([sum(b for j, b in enumerate((0x4, 0x100, 0x200, 0x400)) if (s >> j) & 1)
+                       for s in range(16)], np.int64)[rng.integers(0, 16, size=N)]
+    anyf = rng.integers(0, 1 << 16, size=N)
+    flag = np.select([kind == 0, kind == 1, kind == 2, kind == 3],
+                     [0, single, sub704, np.where(rng.random(N) < 0.5, 0xFFFF, 0x8000)], anyf).astype(np.uint16)
+    mapq = np.where(rng.random(N) < 0.5, rng.choice(EDGE_MAPQ, size=N), rng.integers(0, 256, size=N)).astype(np.uint8)
+    return po.Reads(pos, flag, mapq, off, cigar)
+
+
 def oracle_windows(depth, W, start=0):
     """(sums, mins) of W-anchored windows clipped to [start, start+len(depth))."""
     end = start + len(depth)

@@ -49,6 +49,44 @@ def test_c_oracle_matches_independent_counters(name):
                               po.perbase_c(sub, 0, s, e, flag_mask=0))
 
 
+EDGE_Q = (-1, 0, 1, 127, 128, 129, 255, 256)
+
+
+@pytest.mark.parametrize("seed", range(2))
+def test_c_oracle_matches_independent_counters_on_edge_reads(seed):
+    """The reference the GPU edge tests compare with: on H.edge_reads (MAPQ bytes past 127, flags over 16 bits, op
+    codes 9-15, non-consuming ops of 2^28 - 1 bases, a CIGAR of 70 000 ops) the C oracle, its difference-array
+    form, the numpy twin and the brute-force counter agree for every -Q and flag mask the GPU tests use."""
+    rng = np.random.default_rng(90 + seed)
+    L = 3000
+    r = H.edge_reads(rng, L, 500, long_ops=70_000 if seed == 0 else 0)
+    masks = H.EDGE_FLAG_MASKS + tuple(1 << b for b in range(16))
+    cases = [(q, 0x704) for q in EDGE_Q] + [(0, m) for m in masks] + [(129, 0x8000), (255, 0xFFFF)]
+    for q, m in cases:
+        want = po.perbase_bruteforce(r, q, 0, L + 40, flag_mask=m)
+        assert np.array_equal(po.perbase_c(r, q, 0, L + 40, flag_mask=m), want), (q, hex(m))
+        assert np.array_equal(po.perbase_c(r, q, 0, L + 40, flag_mask=m, diff=True), want), (q, hex(m))
+        assert np.array_equal(po.perbase_numpy(r, q, 0, L + 40, flag_mask=m), want), (q, hex(m))
+        s, e = int(rng.integers(0, L)), int(rng.integers(0, L + 40))
+        assert np.array_equal(po.perbase_c(r, q, s, e, flag_mask=m), po.perbase_bruteforce(r, q, s, e, flag_mask=m))
+    # the filter's edges themselves: -Q -1 and 0 keep every MAPQ, 256 none; a mask of 0 keeps every flag
+    kept = lambda q, m: po.perbase_c(r, q, 0, L, flag_mask=m).sum()
+    assert kept(-1, 0) == kept(0, 0) > kept(1, 0) > kept(128, 0) > kept(255, 0) > kept(256, 0) == 0
+    assert kept(0, 0xFFFFFFFF) == kept(0, 0xFFFF) and kept(0, 0x8000) < kept(0, 0)
+    # op codes 9-15 consume nothing and count nothing: the same as I, and the same as leaving them out
+    c = r.cigar.copy()
+    odd = (c & 15) >= 9
+    assert odd.sum() > 200
+    as_ins = po.Reads(r.pos, r.flag, r.mapq, r.cigar_off, np.where(odd, (c & ~np.uint32(15)) | 1, c))
+    keep = np.concatenate([[0], np.cumsum(~odd)]).astype(np.uint32)
+    dropped = po.Reads(r.pos, r.flag, r.mapq, keep[r.cigar_off.astype(np.int64)], c[~odd])
+    for q, m in ((0, 0), (1, 0x704)):
+        want = po.perbase_c(r, q, 0, L, flag_mask=m)
+        assert np.array_equal(po.perbase_c(as_ins, q, 0, L, flag_mask=m), want)
+        assert np.array_equal(po.perbase_c(dropped, q, 0, L, flag_mask=m), want)
+        assert np.array_equal(po.perbase_bruteforce(dropped, q, 0, L, flag_mask=m), want)
+
+
 def test_golden_beds_regenerate():
     """The committed BED fixtures are what the oracle produces today."""
     beds = H.golden_beds()
