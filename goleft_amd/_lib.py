@@ -93,6 +93,9 @@ SYMBOLS = {
     "gd_ingest_feed": (C.c_int, [_P, _P, C.c_size_t]),
     "gd_ingest_feed_fd": (C.c_int, [_P, C.c_int, C.c_uint64, C.c_size_t]),
     "gd_ingest_timing": (C.c_int, [_P, _P, C.c_size_t]),
+    "gd_covstats_begin": (C.c_int, [_P, C.c_int64, C.c_int64]),
+    "gd_covstats_decode": (C.c_int, [_P, C.c_uint64, _P, C.c_size_t, C.c_int, _P]),
+    "gd_covstats_histogram": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
     "gd_ingest_finish": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_uint64)]),
     "gd_ingest_decode": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_uint64)]),
     "gd_ingest_decode_part": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_size_t, C.c_uint64, C.c_uint, C.c_double,

@@ -166,6 +166,7 @@ int gd_ingest_begin(gd_ctx* c, uint64_t n_bytes, uint64_t base_coffset, size_t n
     c->ing_q[c->ing_n++] = g;
     auto bail = [&](int code, const char* msg) { (void)gd_ingest_abort(c); return fail(c, code, "%s", msg); };
     g->n_bytes = n_bytes;
+    g->base = base_coffset;
     g->nm = n_members;
     g->m_coff.resize(n_members); g->m_end.resize(n_members);
     g->out_off.resize(n_members); g->out_len.assign(isize, isize + n_members);

@@ -75,7 +75,7 @@ struct RingSlot {
 
 // State of a device BAM read between gd_ingest_begin and gd_ingest_finish.
 struct IngestState;
-namespace { struct FillPool; }
+namespace { struct FillPool; struct CovState; }
 
 // Device buffers of one pending range (compressed bytes, inflated bytes, member tables): grow-only and
 // kept by the context between ranges -- allocating and freeing gigabytes per range cost 0.1-0.2 s.
@@ -264,6 +264,7 @@ struct gd_ctx {
     size_t push_chunk = 1u << 20;                      // GD_OPT_PUSH_CHUNK: records per staging block of gd_push                             // GD_OPT_PUSH_THREADS: threads of gd_push filling a ring block
     uint32_t* d_scan_tmp = nullptr; size_t cap_scan_tmp = 0;   // launch_scan: block totals
     void* d_rectab = nullptr; size_t cap_rectab = 0;           // ... and the record table the counting walk leaves for the extraction (device, grow-only)
+    CovState* cov = nullptr;                                   // gd_covstats_*: the sampling state and its buffers (gd_api_covstats.inc)
     uint8_t* h_walk = nullptr; size_t cap_walk = 0;            // gd_ingest_decode: per-segment tables of the record walk (page-locked host memory
                                                                // the walk kernels read and write over the link: no copy command)
     uint32_t* h_ingest = nullptr;                              // page-locked: d_ingest's words as the host reads them (gd_copy_words_kernel)
@@ -697,6 +698,7 @@ struct DevBuf {
 struct IngestState {
     static constexpr size_t kStage = 64u << 20;        // bytes per page-locked staging buffer
     uint64_t n_bytes = 0, fed = 0, total = 0;           // compressed bytes announced / received, inflated bytes
+    uint64_t base = 0;                                  // file offset of the range
     size_t nm = 0, next = 0;                            // members, first member not yet handed to the inflate kernel
     std::vector<uint64_t> m_coff, m_end, out_off;       // file offset, end offset in the range, offset in the inflated bytes
     std::vector<uint32_t> out_len;

@@ -453,7 +453,7 @@ bool load_bai(const std::string& bam_path, std::vector<uint8_t>* d)
 }  // namespace
 
 bool BamReader::linear_index(const std::string& bam_path, std::vector<std::vector<uint64_t>>* per_ref, std::string* err,
-                             std::vector<char>* has_chunks, std::vector<uint64_t>* chunk_end)
+                             std::vector<char>* has_chunks, std::vector<uint64_t>* chunk_end, std::vector<int64_t>* n_mapped)
 {
     std::vector<uint8_t> d;
     if (!load_bai(bam_path, &d)) return false;
@@ -465,6 +465,7 @@ bool BamReader::linear_index(const std::string& bam_path, std::vector<std::vecto
     per_ref->assign((size_t)n_ref, std::vector<uint64_t>());
     if (has_chunks) has_chunks->assign((size_t)n_ref, 0);
     if (chunk_end) chunk_end->assign((size_t)n_ref, 0);
+    if (n_mapped) n_mapped->assign((size_t)n_ref, -1);
     size_t p = 8;
     for (int32_t r = 0; r < n_ref; ++r) {
         if (p + 4 > d.size()) { if (err) *err = "truncated BAI"; return false; }
@@ -483,6 +484,8 @@ bool BamReader::linear_index(const std::string& bam_path, std::vector<std::vecto
                         if (e > (*chunk_end)[(size_t)r]) (*chunk_end)[(size_t)r] = e;
                     }
             }
+            if (bin == 37450 && n_chunk == 2 && n_mapped)       // {unmapped begin, end}, {n_mapped, n_unmapped}
+                (*n_mapped)[(size_t)r] = (int64_t)rd64(d.data() + p + 8 + 16);
             p += 8 + 16 * (size_t)n_chunk;
         }
         if (p + 4 > d.size()) { if (err) *err = "truncated BAI"; return false; }

@@ -118,10 +118,11 @@ public:
     // there is no usable index next to the file.  Static: needs no open reader.
     // Optional: has_chunks[r] = reference r has chunks in a real bin (so "no linear index" cannot mean
     // "no records"), chunk_end[r] = the largest chunk end (virtual offset) of its bins: no record of r
-    // lies past the BGZF member that holds it.
+    // lies past the BGZF member that holds it.  n_mapped[r] = the mapped-read count of r's metadata pseudo-bin
+    // (bin 37450, SAMv1 5.2), -1 when r has none.
     static bool linear_index(const std::string& bam_path, std::vector<std::vector<uint64_t>>* per_ref,
                              std::string* err, std::vector<char>* has_chunks = nullptr,
-                             std::vector<uint64_t>* chunk_end = nullptr);
+                             std::vector<uint64_t>* chunk_end = nullptr, std::vector<int64_t>* n_mapped = nullptr);
 
     // Fills `out` with up to max_reads records, all of one contig (a block ends
     // at a contig change).  Records with refID < 0 are skipped and counted.

@@ -541,6 +541,33 @@ int gd_ingest_decode_part(gd_ctx* ctx, int32_t tid, int32_t ref_id, const uint64
  * (allocations, member table), [3] decode: waiting for the inflate launches, [4] decode: the counting walk, [5] decode:
  * allocating the contig's arrays, [6] decode: the extraction (a thread per record over the walk's table).  Fills min(n, 7) values. */
 int gd_ingest_timing(gd_ctx* ctx, double* out, size_t n);
+/* ---- `goleft covstats` (covstats/covstats.go:122-220) on the fed ranges of the device BAM read ----
+ * gd_covstats_begin starts a sampling run: n inserts to sample, the first `skip` records of the stream
+ * skipped.  Then, range after range (gd_ingest_begin + gd_ingest_feed*), gd_covstats_decode walks EVERY
+ * record of the oldest pending range in file order from first_voffset (the first record of the run, or the
+ * previous call's `resume`), across references and through the unplaced tail, and drops the range.
+ * anchors: ascending virtual offsets of record starts (the .bai linear indexes of all references, merged);
+ * those inside the range cut the walk into segments, the rest are ignored.  last_range: the range ends the
+ * file (a record it holds only in part is an error); otherwise such a record is where the next range resumes.
+ * *out: the counts so far; done != 0 once the sampling loop has stopped (no further range is needed). */
+typedef struct gd_covstats_counts {
+    int64_t records;          /* records walked since gd_covstats_begin */
+    int64_t range_records;    /* ... in the last range */
+    int64_t skip_left;        /* records still to be skipped */
+    int64_t unmapped, counted, bad, dup, proper;   /* nU, k, nBad, nDup, nProper of the sampling loop */
+    int64_t sizes, inserts;   /* query lengths and insert sizes sampled */
+    uint64_t resume;          /* virtual offset of the first record the range did not hold completely (or of the member after it) */
+    int32_t done;
+    int32_t reserved;
+} gd_covstats_counts;
+int gd_covstats_begin(gd_ctx* ctx, int64_t n, int64_t skip);
+int gd_covstats_decode(gd_ctx* ctx, uint64_t first_voffset, const uint64_t* anchors, size_t n_anchors, int last_range,
+                       gd_covstats_counts* out);
+/* The sampled values of one kind (which: 0 query lengths, 1 insert sizes, 2 template lengths): *n_bins counts
+ * of the values lo .. lo + n_bins - 1 (bins: NULL or room for *n_bins), and the values outside that window,
+ * unordered (overflow: NULL or room for cap; *n_overflow: how many there are). */
+int gd_covstats_histogram(gd_ctx* ctx, int which, int64_t* lo, size_t* n_bins, uint64_t* bins, int64_t* overflow,
+                          size_t cap, size_t* n_overflow);
 int gd_ingest_abort(gd_ctx* ctx);
 /* Page-locked host memory for the byte range handed to gd_ingest_bgzf (read the file
  * straight into it: the H2D copy then runs at PCIe speed instead of through a bounce

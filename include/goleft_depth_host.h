@@ -131,6 +131,37 @@ int64_t gdh_multidepth_blocks(const uint32_t* any_bits, const uint32_t* suf_bits
                               int32_t max_skip, int32_t min_size, int32_t window, int64_t* starts,
                               int64_t* ends, int64_t cap);
 
+/* ---- `covstats` (covstats/covstats.go): per BAM, coverage and insert-size estimates
+ * from a sample of records read in file order.  argv: [-n N] [-r BED] [-f FASTA] BAMS...
+ * Output: the column header line (written before the arguments are parsed), then one
+ * row per BAM in argument order.  Returns the exit code (1 on an error -- rows already
+ * written stay -- 255 on a usage error). --------------------------------------------- */
+int gdh_covstats_main(int argc, const char* const* argv);
+/* Same, writing to out_path (NULL = stdout). */
+int gdh_covstats_run(int argc, const char* const* argv, const char* out_path);
+/* One kind of sampled value: counts of lo .. lo + n_bins - 1, and the values outside
+ * that window in any order (what gd_covstats_histogram returns). */
+typedef struct gdh_covstats_values {
+    int64_t lo;
+    uint64_t n_bins;
+    const uint64_t* bins;
+    uint64_t n_overflow;
+    const int64_t* overflow;
+} gdh_covstats_values;
+/* The row of one BAM, pure CPU: counts = {nU, k, nBad, nDup, nProper} of the sampling
+ * loop; the sampled query lengths, insert sizes and template lengths; n_mapped of the
+ * .bai; the genome's (or the -r regions') bases.  Writes the row with its newline and
+ * returns its length; -2 when 1 or 2 insert sizes were sampled (the reference panics),
+ * -3 when cap is too small, -1 on bad arguments. */
+int gdh_covstats_finish(const int64_t* counts, const gdh_covstats_values* sizes,
+                        const gdh_covstats_values* inserts, const gdh_covstats_values* tlens,
+                        uint64_t mapped, int64_t genome_bases, const char* bam, const char* names,
+                        char* row, size_t cap);
+/* n_mapped of every reference's .bai pseudo-bin (bin 37450), -1 for a reference without
+ * one; *n_ref = references of the index.  The index is bam_path + ".bai", else the path
+ * with ".bam" replaced by ".bai".  0, or -1 without a usable index. */
+int gdh_bai_mapped(const char* bam_path, int64_t* mapped, size_t cap, size_t* n_ref);
+
 /* ---- BAM decode (replaces the read side of the samtools child) ---------- */
 /* How `goleft-depth` cuts a BAM into device passes (host/gpu_ingest.hpp; exported for tests):
  * start[r] / has[r] describe the n_refs references of the file (offset of the BGZF member of r's first
