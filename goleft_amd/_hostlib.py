@@ -28,6 +28,11 @@ SYMBOLS = {
     "gdh_covstats_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_covstats_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p]),
     "gdh_covstats_finish": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_int64, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]),
+    "gdh_indexcov_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
+    "gdh_indexcov_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
+    "gdh_round3g": (None, [_P, C.c_size_t, _P]),
+    "gdh_fmt3g": (C.c_int, [C.c_uint32, C.c_char_p, C.c_size_t]),
+    "gdh_indexcov_pcs": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     "gdh_bai_mapped": (C.c_int, [C.c_char_p, _P, C.c_size_t, _P]),
     "gdh_plan_ingest_passes": (C.c_size_t, [_P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_uint64, C.c_size_t,
                                             _P, _P, _P, _P]),

@@ -27,6 +27,11 @@ class GdRun(C.Structure):
     _fields_ = [("start", C.c_int32), ("end", C.c_int32), ("cls", C.c_int32)]
 
 
+class GdIndexcovDims(C.Structure):
+    _fields_ = [("n_tiles", C.c_int64), ("n_cells", C.c_int64), ("m", C.c_int64), ("m_pad", C.c_int64),
+                ("n_samples", C.c_int32), ("n_refs", C.c_int32)]
+
+
 class GdStats(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_ops", C.c_uint64), ("n_ref_bases", C.c_uint64),
                 ("n_windows", C.c_uint64), ("n_tiles", C.c_uint64), ("n_runs", C.c_uint64),
@@ -41,6 +46,7 @@ _P = C.c_void_p
 SYMBOLS = {
     "gd_strerror": (C.c_char_p, [C.c_int]),
     "gd_abi_version": (C.c_int, []),
+    "gd_abi_revision": (C.c_int, []),
     "gd_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "gd_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
     "gd_destroy": (None, [_P]),
@@ -96,6 +102,19 @@ SYMBOLS = {
     "gd_covstats_begin": (C.c_int, [_P, C.c_int64, C.c_int64]),
     "gd_covstats_decode": (C.c_int, [_P, C.c_uint64, _P, C.c_size_t, C.c_int, _P]),
     "gd_covstats_histogram": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
+    "gd_indexcov_upload": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "gd_indexcov_get_dims": (C.c_int, [_P, _P, _P, _P, _P]),
+    "gd_indexcov_medians": (C.c_int, [_P, _P]),
+    "gd_indexcov_depths": (C.c_int, [_P, _P, C.c_size_t]),
+    "gd_indexcov_set_depths": (C.c_int, [_P, _P, C.c_size_t]),
+    "gd_indexcov_compute": (C.c_int, [_P, C.c_int]),
+    "gd_indexcov_cells": (C.c_int, [_P, C.c_int64, C.c_int64, _P]),
+    "gd_indexcov_slots": (C.c_int, [_P, _P]),
+    "gd_indexcov_counters": (C.c_int, [_P, _P]),
+    "gd_indexcov_cn": (C.c_int, [_P, _P]),
+    "gd_indexcov_pca8": (C.c_int, [_P, _P]),
+    "gd_indexcov_gram": (C.c_int, [_P, _P]),
+    "gd_indexcov_timing": (C.c_int, [_P, _P, C.c_size_t]),
     "gd_ingest_finish": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_uint64)]),
     "gd_ingest_decode": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_uint64)]),
     "gd_ingest_decode_part": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_size_t, C.c_uint64, C.c_uint, C.c_double,

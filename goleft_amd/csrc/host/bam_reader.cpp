@@ -437,7 +437,8 @@ bool BamReader::open(const std::string& path, int threads, std::string* err)
 namespace {
 bool load_bai(const std::string& bam_path, std::vector<uint8_t>* d)
 {
-    FILE* fi = fopen((bam_path + ".bai").c_str(), "rb");
+    const bool is_index = bam_path.size() > 4 && bam_path.compare(bam_path.size() - 4, 4, ".bai") == 0;
+    FILE* fi = fopen((is_index ? bam_path : bam_path + ".bai").c_str(), "rb");
     if (!fi) {
         std::string alt = bam_path;
         if (alt.size() > 4 && alt.substr(alt.size() - 4) == ".bam") alt = alt.substr(0, alt.size() - 4) + ".bai";
@@ -453,7 +454,8 @@ bool load_bai(const std::string& bam_path, std::vector<uint8_t>* d)
 }  // namespace
 
 bool BamReader::linear_index(const std::string& bam_path, std::vector<std::vector<uint64_t>>* per_ref, std::string* err,
-                             std::vector<char>* has_chunks, std::vector<uint64_t>* chunk_end, std::vector<int64_t>* n_mapped)
+                             std::vector<char>* has_chunks, std::vector<uint64_t>* chunk_end, std::vector<int64_t>* n_mapped,
+                             std::vector<std::vector<uint64_t>>* raw, std::vector<int64_t>* n_unmapped)
 {
     std::vector<uint8_t> d;
     if (!load_bai(bam_path, &d)) return false;
@@ -466,6 +468,8 @@ bool BamReader::linear_index(const std::string& bam_path, std::vector<std::vecto
     if (has_chunks) has_chunks->assign((size_t)n_ref, 0);
     if (chunk_end) chunk_end->assign((size_t)n_ref, 0);
     if (n_mapped) n_mapped->assign((size_t)n_ref, -1);
+    if (n_unmapped) n_unmapped->assign((size_t)n_ref, 0);
+    if (raw) raw->assign((size_t)n_ref, std::vector<uint64_t>());
     size_t p = 8;
     for (int32_t r = 0; r < n_ref; ++r) {
         if (p + 4 > d.size()) { if (err) *err = "truncated BAI"; return false; }
@@ -486,6 +490,8 @@ bool BamReader::linear_index(const std::string& bam_path, std::vector<std::vecto
             }
             if (bin == 37450 && n_chunk == 2 && n_mapped)       // {unmapped begin, end}, {n_mapped, n_unmapped}
                 (*n_mapped)[(size_t)r] = (int64_t)rd64(d.data() + p + 8 + 16);
+            if (bin == 37450 && n_chunk == 2 && n_unmapped)
+                (*n_unmapped)[(size_t)r] = (int64_t)rd64(d.data() + p + 8 + 24);
             p += 8 + 16 * (size_t)n_chunk;
         }
         if (p + 4 > d.size()) { if (err) *err = "truncated BAI"; return false; }
@@ -493,8 +499,10 @@ bool BamReader::linear_index(const std::string& bam_path, std::vector<std::vecto
         p += 4;
         if (n_intv < 0 || (d.size() - p) / 8 < (size_t)n_intv) { if (err) *err = "truncated BAI"; return false; }
         std::vector<uint64_t>& v = (*per_ref)[(size_t)r];
+        if (raw) (*raw)[(size_t)r].reserve((size_t)n_intv);
         for (int32_t i = 0; i < n_intv; ++i) {
             const uint64_t x = rd64(d.data() + p + 8 * (size_t)i);
+            if (raw) (*raw)[(size_t)r].push_back(x);
             if (x != 0 && (v.empty() || x > v.back())) v.push_back(x);   // the index is non-decreasing
         }
         p += 8 * (size_t)n_intv;

@@ -119,10 +119,13 @@ public:
     // Optional: has_chunks[r] = reference r has chunks in a real bin (so "no linear index" cannot mean
     // "no records"), chunk_end[r] = the largest chunk end (virtual offset) of its bins: no record of r
     // lies past the BGZF member that holds it.  n_mapped[r] = the mapped-read count of r's metadata pseudo-bin
-    // (bin 37450, SAMv1 5.2), -1 when r has none.
+    // (bin 37450, SAMv1 5.2), -1 when r has none; n_unmapped[r] = its unmapped-read count (0 when r has none).
+    // raw[r] = the interval array AS STORED, zeros and repeats included (indexcov's tile sizes are the differences of
+    // consecutive entries: a repeated offset is a tile without reads).  A bam_path that ends in ".bai" is the index itself.
     static bool linear_index(const std::string& bam_path, std::vector<std::vector<uint64_t>>* per_ref,
                              std::string* err, std::vector<char>* has_chunks = nullptr,
-                             std::vector<uint64_t>* chunk_end = nullptr, std::vector<int64_t>* n_mapped = nullptr);
+                             std::vector<uint64_t>* chunk_end = nullptr, std::vector<int64_t>* n_mapped = nullptr,
+                             std::vector<std::vector<uint64_t>>* raw = nullptr, std::vector<int64_t>* n_unmapped = nullptr);
 
     // Fills `out` with up to max_reads records, all of one contig (a block ends
     // at a contig change).  Records with refID < 0 are skipped and counted.
@@ -166,5 +169,9 @@ private:
     std::vector<bool> left_;          // references whose run of records has ended (a sorted BAM never returns to one)
     int32_t last_ref_ = -2;           // reference of the last record seen (-2: none yet, or just after a seek)
 };
+
+// indexcov.GetShortName (indexcov/indexcov.go:213-246): the single @RG SM value of the header text, else derived from
+// the file name; false when the header names more than one distinct SM (host/multidepth_host.cpp).
+bool short_name(const std::string& path, const std::string& header, std::string* out);
 
 }  // namespace gdh

@@ -99,9 +99,11 @@ int parse_args(int argc, const char* const* argv, MArgs* a)
     return 0;
 }
 
+}  // namespace
+
 // indexcov.GetShortName(b, false) (indexcov/indexcov.go:213-246): the single @RG SM value,
 // else derived from the file name.  More than one distinct SM is an error.
-bool short_name(const std::string& path, const std::string& header, std::string* out)
+bool gdh::short_name(const std::string& path, const std::string& header, std::string* out)
 {
     std::vector<std::string> sms;
     size_t p = 0;
@@ -139,6 +141,10 @@ bool short_name(const std::string& path, const std::string& header, std::string*
     for (size_t i = 0; i + 1 < parts.size(); ++i) { if (i) out->push_back('-'); out->append(parts[i]); }
     return true;
 }
+
+namespace {
+
+using gdh::short_name;
 
 struct Block { int64_t start, end; };        // 0-based start, 1-based end (:175-180)
 

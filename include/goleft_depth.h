@@ -37,7 +37,12 @@
 extern "C" {
 #endif
 
+/* GD_ABI_VERSION changes when an existing entry point or structure changes; GD_ABI_REVISION counts the releases that only
+ * ADDED entry points since then (revision 1: gd_indexcov_*).  A caller built against (15, r) runs on any (15, r' >= r).
+ * Why indexcov did not become version 16: nothing that existed changed, so callers of ABI 15 need not be turned away, and
+ * tests/test_host_cpu.py holds gd_abi_version() to 15 until something does change. */
 #define GD_ABI_VERSION 15
+#define GD_ABI_REVISION 1
 
 typedef enum {
     GD_OK = 0,
@@ -157,6 +162,7 @@ enum { GD_PATH_AUTO = 0, GD_PATH_TILE = 1, GD_PATH_SCATTER = 2, GD_PATH_CHUNK = 
 
 const char* gd_strerror(int status);
 int         gd_abi_version(void);
+int         gd_abi_revision(void);
 int         gd_device_count(int* n);
 
 /* Create a context bound to one HIP device (hipSetDevice is re-issued inside
@@ -568,6 +574,39 @@ int gd_covstats_decode(gd_ctx* ctx, uint64_t first_voffset, const uint64_t* anch
  * unordered (overflow: NULL or room for cap; *n_overflow: how many there are). */
 int gd_covstats_histogram(gd_ctx* ctx, int which, int64_t* lo, size_t* n_bins, uint64_t* bins, int64_t* overflow,
                           size_t cap, size_t* n_overflow);
+/* ---- `goleft indexcov` (indexcov/indexcov.go, types.go) on the tile sizes of a cohort of .bai linear indexes ----
+ * gd_indexcov_upload takes, for n_samples samples, EVERY tile size of every reference of each index (sizes, the
+ * samples one after the other: sample s owns [sample_off[s], sample_off[s + 1]), never empty, never negative) --
+ * the median is taken over all of them -- and, for the n_refs references that are reported, where the tiles of
+ * (sample s, reference r) lie: tile_off[s * n_refs + r] (into sizes) and tile_cnt[...]; is_sex[r] marks the sex
+ * references.  It computes the medians (Index.init) and the float32 depths (NormalizedDepth) at once; a sample
+ * whose median is 0 has no tiles on any reference from then on.  gd_indexcov_set_depths replaces the depths (the
+ * reference's -n pass runs on the host, in its order).  gd_indexcov_compute makes, per reference r with
+ * longest[r] = the most tiles any sample has: the %.3g cells (cell_off[r] + tile * n_samples + sample; a packed
+ * cell is digits | (exponent + 128) << 16, see gd_round3g.hpp), the 70 CountsAtDepth slots
+ * ([r][sample][70]), per sample the counters {out, low, hi, in} over the non-sex references, GetCN of every sex
+ * reference ([r][sample]; 0 elsewhere), the pca8 bytes ([sample][m], column col_off[r] + tile) and, with_gram != 0,
+ * the exact Gram matrix G = pca8 * pca8^T ([sample][sample], int64). */
+typedef struct gd_indexcov_dims {
+    int64_t n_tiles, n_cells, m, m_pad;
+    int32_t n_samples, n_refs;
+} gd_indexcov_dims;
+int gd_indexcov_upload(gd_ctx* ctx, int32_t n_samples, int32_t n_refs, const int64_t* sample_off, const int64_t* sizes,
+                       const int64_t* tile_off, const int32_t* tile_cnt, const uint8_t* is_sex);
+int gd_indexcov_get_dims(gd_ctx* ctx, gd_indexcov_dims* out, int32_t* longest, int64_t* cell_off, int64_t* col_off);
+int gd_indexcov_medians(gd_ctx* ctx, int64_t* out);
+int gd_indexcov_depths(gd_ctx* ctx, float* out, size_t cap);
+int gd_indexcov_set_depths(gd_ctx* ctx, const float* in, size_t n);
+int gd_indexcov_compute(gd_ctx* ctx, int with_gram);
+int gd_indexcov_cells(gd_ctx* ctx, int64_t first, int64_t n, uint32_t* out);
+int gd_indexcov_slots(gd_ctx* ctx, int32_t* out);
+int gd_indexcov_counters(gd_ctx* ctx, int64_t* out);
+int gd_indexcov_cn(gd_ctx* ctx, double* out);
+int gd_indexcov_pca8(gd_ctx* ctx, uint8_t* out);
+int gd_indexcov_gram(gd_ctx* ctx, int64_t* out);
+/* Seconds of the last upload / compute (measurement only): upload, medians + depths, cells / slots / counters / pca8,
+ * CN, Gram matrix.  Fills min(n, 5) values. */
+int gd_indexcov_timing(gd_ctx* ctx, double* out, size_t n);
 int gd_ingest_abort(gd_ctx* ctx);
 /* Page-locked host memory for the byte range handed to gd_ingest_bgzf (read the file
  * straight into it: the H2D copy then runs at PCIe speed instead of through a bounce

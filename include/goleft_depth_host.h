@@ -162,6 +162,23 @@ int gdh_covstats_finish(const int64_t* counts, const gdh_covstats_values* sizes,
  * with ".bam" replaced by ".bai".  0, or -1 without a usable index. */
 int gdh_bai_mapped(const char* bam_path, int64_t* mapped, size_t cap, size_t* n_ref);
 
+/* ---- `indexcov` (indexcov/indexcov.go, types.go): coverage of a cohort from the .bai linear indexes alone.
+ * argv: -d DIR [-X X,Y] [-p REGEX] [-e] [-n] [-f ref.fai] a.bam|a.bai ...   Writes DIR/<DIR>-indexcov.bed.gz
+ * (BGZF), .roc and .ped; no HTML, PNG or chart output.  .crai / .cram inputs and -c/--chrom are refused.  Returns the
+ * exit code (1 on an error, 255 on a usage error); no .ped is left behind by a failed run. ------------------------- */
+int gdh_indexcov_main(int argc, const char* const* argv);
+int gdh_indexcov_run(int argc, const char* const* argv);
+/* What `%.3g` prints for a float32 (goleft_amd/csrc/gd_round3g.hpp, the host instance of the code the device cell
+ * kernel runs): packed cells digits | (exponent + 128) << 16, and the text of one cell (returns its length, -1 when
+ * cap is too small). */
+void gdh_round3g(const float* x, size_t n, uint32_t* out);
+int gdh_fmt3g(uint32_t cell, char* out, size_t cap);
+/* The first k principal-component projections of the rows of a matrix X ([n][k] into out; sigma: NULL or k singular
+ * values of the column-centred X) from its exact Gram matrix G = X * X^T ([n][n]) alone, in fp64: what gonum's stat.PC
+ * followed by X * V gives, up to the sign of each column.  A component whose singular value is 0 up to rounding is
+ * written as zeros.  0, or -1 on bad arguments. */
+int gdh_indexcov_pcs(const int64_t* G, int n, int k, double* out, double* sigma);
+
 /* ---- BAM decode (replaces the read side of the samtools child) ---------- */
 /* How `goleft-depth` cuts a BAM into device passes (host/gpu_ingest.hpp; exported for tests):
  * start[r] / has[r] describe the n_refs references of the file (offset of the BGZF member of r's first
