@@ -32,6 +32,14 @@ class GdError(RuntimeError):
         self.status = status
 
 
+class CovstatsCounts(C.Structure):
+    """gd_covstats_counts (include/goleft_depth.h)."""
+    _fields_ = [("records", C.c_int64), ("range_records", C.c_int64), ("skip_left", C.c_int64),
+                ("unmapped", C.c_int64), ("counted", C.c_int64), ("bad", C.c_int64), ("dup", C.c_int64),
+                ("proper", C.c_int64), ("sizes", C.c_int64), ("inserts", C.c_int64), ("resume", C.c_uint64),
+                ("done", C.c_int32), ("reserved", C.c_int32)]
+
+
 class DepthEngine:
     """One context == one HIP device."""
 
@@ -502,6 +510,30 @@ class DepthEngine:
 
     def ingest_release(self) -> None:
         self._chk(self._lib.gd_ingest_release(self._ctx))
+
+    def covstats_begin(self, n: int, skip: int) -> None:
+        self._chk(self._lib.gd_covstats_begin(self._ctx, int(n), int(skip)))
+
+    def covstats_decode(self, first_voffset: int, anchors, last_range: bool) -> "CovstatsCounts":
+        """gd_covstats_decode of the oldest pending range; the counts so far."""
+        a = np.ascontiguousarray(anchors, np.uint64)
+        out = CovstatsCounts()
+        self._chk(self._lib.gd_covstats_decode(self._ctx, int(first_voffset), a.ctypes.data if a.size else None, a.size,
+                                               1 if last_range else 0, C.addressof(out)))
+        return out
+
+    def covstats_histogram(self, which: int, cap: int | None = None):
+        """gd_covstats_histogram: (lo, bins[n_bins], overflow values); cap: the room offered for the overflow
+        values (default: what the library reports)."""
+        lo, nb, no = np.zeros(1, np.int64), np.zeros(1, np.uintp), np.zeros(1, np.uintp)
+        self._chk(self._lib.gd_covstats_histogram(self._ctx, which, lo.ctypes.data, nb.ctypes.data, None, None, 0,
+                                                  no.ctypes.data))
+        bins = np.zeros(int(nb[0]), np.uint64)
+        room = int(no[0]) if cap is None else int(cap)
+        ovf = np.zeros(max(room, 1), np.int64)
+        self._chk(self._lib.gd_covstats_histogram(self._ctx, which, lo.ctypes.data, nb.ctypes.data, bins.ctypes.data,
+                                                  ovf.ctypes.data, room, no.ctypes.data))
+        return int(lo[0]), bins, ovf[:int(no[0])]
 
     def ingest_bgzf_refs(self, data: bytes, base_coffset: int, refs, piece: int = 32 << 20):
         """One fed byte range that holds several references: refs = [(tid, ref_id, anchors), ...] in

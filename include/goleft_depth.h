@@ -562,7 +562,12 @@ typedef struct gd_covstats_counts {
     int64_t skip_left;        /* records still to be skipped */
     int64_t unmapped, counted, bad, dup, proper;   /* nU, k, nBad, nDup, nProper of the sampling loop */
     int64_t sizes, inserts;   /* query lengths and insert sizes sampled */
-    uint64_t resume;          /* virtual offset of the first record the range did not hold completely (or of the member after it) */
+    uint64_t resume;          /* virtual offset of the first record the range did not hold completely.  A record that
+                               * starts on a member boundary is spelled (the member that begins there -- of several,
+                               * the last: the one with bytes --, uoffset 0), never (the member before, its ISIZE); when
+                               * every record of the range is whole: (the member that follows the range, 0), which for
+                               * the file's last range is the file's size.  gd_covstats_decode takes either spelling
+                               * as first_voffset. */
     int32_t done;
     int32_t reserved;
 } gd_covstats_counts;

@@ -8,9 +8,11 @@ Restated, quirks included: the 100 000 skipped records; unmapped records not cou
 when no size was sampled; the last -r line without a newline not counted."""
 from __future__ import annotations
 
+import bisect
 import gzip
 import math
 import struct
+import zlib
 
 import numpy as np
 
@@ -28,14 +30,15 @@ class MadFilterPanic(Exception):
 
 # ---- the record stream --------------------------------------------------------------------------------------------
 class Rec:
-    __slots__ = ("ref", "pos", "flag", "next_ref", "next_pos", "tlen", "cigar", "name", "tags", "mapq", "l_seq")
+    __slots__ = ("ref", "pos", "flag", "next_ref", "next_pos", "tlen", "cigar", "name", "tags", "mapq", "l_seq", "raw")
 
     def __init__(self, ref=0, pos=0, flag=0, next_pos=-1, tlen=0, cigar=((0, 100),), name="r", tags=b"", mapq=60,
-                 next_ref=None, l_seq=0):
+                 next_ref=None, l_seq=0, raw=None):
         self.ref, self.pos, self.flag, self.next_pos, self.tlen = ref, pos, flag, next_pos, tlen
         self.cigar = list(cigar)
         self.name, self.tags, self.mapq, self.l_seq = name, tags, mapq, l_seq
         self.next_ref = ref if next_ref is None else next_ref
+        self.raw = raw                                      # the record's bytes as write_bam stores them (raw_rec)
 
 
 def qlen(cigar):
@@ -109,9 +112,11 @@ def bam_stats(recs, n, skip=SKIP):
     sizes, ins, tl = [], [], []
     n_bad = n_unmapped = k = 0
     dup = proper = 0.0
+    stopped = skipped == skip                               # false: the stream ran out (in the skip or in the loop)
     while len(ins) < n:
         rec = next(it, None)
         if rec is None:
+            stopped = False
             break
         if rec.flag & 0x4:
             n_unmapped += 1
@@ -133,7 +138,7 @@ def bam_stats(recs, n, skip=SKIP):
             tl.append(rec.tlen)
     s = dict(insert_mean=0.0, insert_sd=0.0, pct5=0, pct95=0, template_mean=0.0, template_sd=0.0, rl_mean=0.0,
              bad=0.0, unmapped=0.0, proper=proper, dup=dup, max_rl=0, counts=(n_unmapped, k, n_bad, int(dup), int(proper)),
-             sizes=list(sizes), ins=list(ins), tl=list(tl), skip_short=skipped < skip)
+             sizes=list(sizes), ins=list(ins), tl=list(tl), skip_short=skipped < skip, stopped=stopped)
     sizes.sort()
     if sizes:
         tot = float(k + n_unmapped)
@@ -262,10 +267,42 @@ def covstats_rows(bams, n=1000000, skip=SKIP, regions=None):
 
 
 # ---- crafting BAM files ------------------------------------------------------------------------------------------------
-def write_bam(path, refs, recs, header_text=None, block=0xff00, level=1, index=True, pseudo=True):
+def raw_rec(ref=0, pos=0, flag=0, next_pos=-1, tlen=0, cigar=(), name=b"", tags=b"", l_seq=0, next_ref=None, mapq=60,
+            block_size=None, l_read_name=None, n_cigar=None):
+    """A Rec whose bytes are fixed here: `name` is stored as given (no index appended, no NUL added; empty: a 36-byte
+    record), and block_size / l_read_name / n_cigar may lie about what follows (a damaged record)."""
+    cig = np.asarray([(ln << 4) | op for op, ln in cigar], "<u4").tobytes()
+    seq = b"\0" * ((l_seq + 1) // 2) + b"\xff" * l_seq
+    nref = ref if next_ref is None else next_ref
+    body = struct.pack("<iiBBHHHiiii", ref, pos, len(name) if l_read_name is None else l_read_name, mapq, 4680,
+                       len(cigar) if n_cigar is None else n_cigar, flag, l_seq, nref, next_pos, tlen) + name + cig + seq + tags
+    raw = struct.pack("<i", len(body) if block_size is None else block_size) + body
+    return Rec(ref, pos, flag, next_pos, tlen, cigar, name="", tags=tags, mapq=mapq, next_ref=nref, l_seq=l_seq, raw=raw)
+
+
+def bgzf_cut(data, cuts, level=1, sizes=None):
+    """BGZF of `data` with a member boundary at every offset of `cuts` (ascending; an offset given twice: an empty
+    member there) and the EOF marker; sizes: the compressed size of every data member."""
+    def member(chunk):
+        co = zlib.compressobj(level, zlib.DEFLATED, -15)
+        c = co.compress(chunk) + co.flush()
+        return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", len(c) + 25) + c
+                + struct.pack("<II", zlib.crc32(chunk) & 0xFFFFFFFF, len(chunk)))
+    edges = [0] + [int(c) for c in cuts] + [len(data)]
+    assert all(a <= b and b - a < 0x10000 for a, b in zip(edges, edges[1:])), "cuts: ascending, members below 64 KB"
+    out = [member(data[a:b]) for a, b in zip(edges, edges[1:])]
+    if sizes is not None:
+        sizes.extend(len(m) for m in out)
+    out.append(member(b""))
+    return b"".join(out), edges[:-1]
+
+
+def write_bam(path, refs, recs, header_text=None, block=0xff00, level=1, index=True, pseudo=True, cuts=None):
     """A BAM of `recs` in the order given (Rec: ref -1 for unplaced), BGZF members of `block` uncompressed bytes, and
     (index) a .bai whose linear index holds the first record of every 16 kb window of every reference and (pseudo) a
-    pseudo-bin per reference with records: n_mapped = its records without flag 0x4."""
+    pseudo-bin per reference with records: n_mapped = its records without flag 0x4.  cuts: a callable that is given
+    (the header's length, the start of every record, the stream's length) and returns the offsets of the inflated
+    stream at which members begin (bgzf_cut), instead of `block`."""
     if header_text is None:
         header_text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % r for r in refs)
     ht = header_text.encode()
@@ -276,6 +313,12 @@ def write_bam(path, refs, recs, header_text=None, block=0xff00, level=1, index=T
     cur = sum(len(x) for x in out)
     offs = []
     for i, r in enumerate(recs):
+        if r.raw is not None:
+            ref_len = min(sum(ln for op, ln in r.cigar if op in (0, 2, 3, 7, 8)), 1 << 24)   # (the index's windows)
+            out.append(r.raw)
+            offs.append((cur, cur + len(r.raw), max(ref_len, 1)))
+            cur += len(r.raw)
+            continue
         name = (r.name + str(i)).encode() + b"\0"
         cig = np.asarray([(ln << 4) | op for op, ln in r.cigar], "<u4").tobytes()
         ref_len = sum(ln for op, ln in r.cigar if op in (0, 2, 3, 7, 8))
@@ -286,12 +329,23 @@ def write_bam(path, refs, recs, header_text=None, block=0xff00, level=1, index=T
         offs.append((cur, cur + 4 + len(body), max(ref_len, 1)))
         cur += 4 + len(body)
     sizes = []
-    with open(path, "wb") as fh:
-        fh.write(bamio.bgzf_compress(b"".join(out), block=block, level=level, sizes=sizes))
+    if cuts is None:
+        with open(path, "wb") as fh:
+            fh.write(bamio.bgzf_compress(b"".join(out), block=block, level=level, sizes=sizes))
+    else:
+        data = b"".join(out)
+        raw, starts = bgzf_cut(data, cuts(offs[0][0] if offs else len(data), [o[0] for o in offs], len(data)), level, sizes)
+        with open(path, "wb") as fh:
+            fh.write(raw)
     if not index:
         return
     coff = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    voff = lambda o: (int(coff[o // block]) << 16) | (o % block)
+    if cuts is None:
+        voff = lambda o: (int(coff[o // block]) << 16) | (o % block)
+    else:                                                   # the last member that begins at or before o (never an empty one)
+        def voff(o):
+            k = bisect.bisect_right(starts, o) - 1
+            return (int(coff[k]) << 16) | (o - starts[k])
     lin = [dict() for _ in refs]
     chunks = [None] * len(refs)
     mapped = [0] * len(refs)
