@@ -30,6 +30,9 @@ SYMBOLS = {
     "gdh_covstats_finish": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_int64, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]),
     "gdh_indexcov_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_indexcov_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
+    "gdh_indexsplit_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
+    "gdh_indexsplit_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p]),
+    "gdh_samplename_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_round3g": (None, [_P, C.c_size_t, _P]),
     "gdh_fmt3g": (C.c_int, [C.c_uint32, C.c_char_p, C.c_size_t]),
     "gdh_indexcov_pcs": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
@@ -51,6 +54,7 @@ SYMBOLS = {
                                C.POINTER(_P), C.POINTER(_P)]),
     "gdh_bam_n_records": (C.c_uint64, [_P]),
     "gdh_intervals_read": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.POINTER(_P)]),
+    "gdh_intervals_read_lines": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
     "gdh_intervals_free": (None, [_P]),
     "gdh_intervals_overlaps": (C.c_int, [_P, C.c_char_p, C.c_int64, C.c_int64]),
     "gdh_intervals_count": (C.c_size_t, [_P, C.c_char_p]),

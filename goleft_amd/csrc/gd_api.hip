@@ -127,7 +127,7 @@ int gd_create(int device_id, gd_ctx** out)
     return GD_OK;
 }
 
-namespace { static void drop_pool(gd_ctx* c); static void cov_drop(gd_ctx* c); static void ic_drop(gd_ctx* c); }
+namespace { static void drop_pool(gd_ctx* c); static void cov_drop(gd_ctx* c); static void ic_drop(gd_ctx* c); static void is_drop(gd_ctx* c); }
 
 void gd_destroy(gd_ctx* c)
 {
@@ -138,6 +138,7 @@ void gd_destroy(gd_ctx* c)
     (void)gd_ingest_abort(c);
     cov_drop(c);
     ic_drop(c);
+    is_drop(c);
     (void)gd_comm_destroy(c);
     for (hipEvent_t e : c->comm_ev) if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < 8; ++k) {
@@ -831,6 +832,7 @@ int gd_reset(gd_ctx* c)
 #include "gd_api_ingest.inc"
 #include "gd_api_covstats.inc"
 #include "gd_api_indexcov.inc"
+#include "gd_api_indexsplit.inc"
 #include "gd_api_comm.inc"
 
 int gd_device_perbase(gd_ctx* c, int32_t tid, const int32_t** dptr, int64_t* len)

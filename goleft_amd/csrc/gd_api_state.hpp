@@ -75,7 +75,7 @@ struct RingSlot {
 
 // State of a device BAM read between gd_ingest_begin and gd_ingest_finish.
 struct IngestState;
-namespace { struct FillPool; struct CovState; struct IcState; }
+namespace { struct FillPool; struct CovState; struct IcState; struct IsState; }
 
 // Device buffers of one pending range (compressed bytes, inflated bytes, member tables): grow-only and
 // kept by the context between ranges -- allocating and freeing gigabytes per range cost 0.1-0.2 s.
@@ -266,6 +266,7 @@ struct gd_ctx {
     void* d_rectab = nullptr; size_t cap_rectab = 0;           // ... and the record table the counting walk leaves for the extraction (device, grow-only)
     CovState* cov = nullptr;                                   // gd_covstats_*: the sampling state and its buffers (gd_api_covstats.inc)
     IcState* ic = nullptr;                                     // gd_indexcov_*: the cohort's tile sizes and results (gd_api_indexcov.inc)
+    IsState* isp = nullptr;                                    // gd_indexsplit_*: the cohort's cell sums (gd_api_indexsplit.inc)
     uint8_t* h_walk = nullptr; size_t cap_walk = 0;            // gd_ingest_decode: per-segment tables of the record walk (page-locked host memory
                                                                // the walk kernels read and write over the link: no copy command)
     uint32_t* h_ingest = nullptr;                              // page-locked: d_ingest's words as the host reads them (gd_copy_words_kernel)

@@ -331,7 +331,8 @@ int gdh_bam_next(gdh_bam* b, size_t max_reads, int32_t* tid, size_t* n_reads, si
 
 uint64_t gdh_bam_n_records(const gdh_bam* b) { return b ? b->rd.n_records() : 0; }
 
-int gdh_intervals_read(const char* const* paths, int n_paths, gdh_intervals** out)
+// whole_lines: a last line without its newline is dropped, as ReadTree's ReadBytes loop drops it (intervals.go:57-60)
+static int intervals_read(const char* const* paths, int n_paths, bool whole_lines, gdh_intervals** out)
 {
     if (!out || n_paths < 0) return -1;
     gdh_intervals* t = new (std::nothrow) gdh_intervals();
@@ -344,6 +345,7 @@ int gdh_intervals_read(const char* const* paths, int n_paths, gdh_intervals** ou
         size_t cap = 0;
         ssize_t n;
         while ((n = getline(&line, &cap, f)) > 0) {
+            if (whole_lines && line[n - 1] != '\n') break;
             char chrom[4096];
             int64_t s, e;
             if (gdh_chrom_start_end(line, (size_t)n, chrom, sizeof chrom, &s, &e) != 0) {
@@ -365,6 +367,16 @@ int gdh_intervals_read(const char* const* paths, int n_paths, gdh_intervals** ou
     }
     *out = t;
     return 0;
+}
+
+int gdh_intervals_read(const char* const* paths, int n_paths, gdh_intervals** out)
+{
+    return intervals_read(paths, n_paths, false, out);
+}
+
+int gdh_intervals_read_lines(const char* path, gdh_intervals** out)
+{
+    return intervals_read(&path, 1, true, out);
 }
 
 void gdh_intervals_free(gdh_intervals* t) { delete t; }

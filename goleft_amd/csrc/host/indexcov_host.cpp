@@ -31,6 +31,7 @@
 #include "../../../include/goleft_depth_host.h"
 #include "../gd_round3g.hpp"
 #include "bam_reader.hpp"
+#include "index_sizes.hpp"
 
 namespace {
 
@@ -58,11 +59,7 @@ void usage(FILE* f)
           "  No HTML, PNG or chart output is written (index.html, *-roc-*.html, *.png of the reference are out of scope).\n", f);
 }
 
-bool ends_with(const std::string& s, const char* suf)
-{
-    const size_t n = strlen(suf);
-    return s.size() >= n && s.compare(s.size() - n, n, suf) == 0;
-}
+using gdh::ends_with;
 
 int parse_args(int argc, const char* const* argv, IArgs* a)
 {
@@ -126,61 +123,19 @@ std::string base_name(std::string p)
     return p.empty() ? "." : p;
 }
 
-struct Ref { std::string name; int64_t length; };
+using Ref = gdh::FaiRef;
+using gdh::read_fai;
 
-bool read_fai(const std::string& path, std::vector<Ref>* refs)
-{
-    FILE* f = fopen(path.c_str(), "r");
-    if (!f) return false;
-    std::vector<std::pair<int64_t, Ref>> recs;
-    char* line = nullptr;
-    size_t cap = 0;
-    while (getline(&line, &cap, f) > 0) {
-        std::vector<std::string> t;
-        std::string cur;
-        for (const char* p = line; *p && *p != '\n'; ++p) { if (*p == '\t') { t.push_back(cur); cur.clear(); } else cur.push_back(*p); }
-        t.push_back(cur);
-        if (t.size() < 3) continue;
-        recs.push_back({strtoll(t[2].c_str(), nullptr, 10), Ref{t[0], strtoll(t[1].c_str(), nullptr, 10)}});
-    }
-    free(line);
-    fclose(f);
-    std::stable_sort(recs.begin(), recs.end(), [](const auto& x, const auto& y) { return x.first < y.first; });   // ReadFai :293
-    for (auto& r : recs) refs->push_back(r.second);
-    return !refs->empty();
-}
-
-struct Sample {
+struct Sample : gdh::IndexSizes {
     std::string path, name, err;
-    std::vector<std::vector<uint64_t>> raw;      // the interval arrays as stored
-    std::vector<int64_t> ref_off;                // [n_ref + 1] into the sample's sizes
-    std::vector<int64_t> sizes;
-    uint64_t mapped = 0, unmapped = 0;
 };
 
 // readIndex (:471-525) + getSizes (types.go:45-82)
 void read_sample(Sample* s)
 {
     const std::string& b = s->path;
-    std::vector<std::vector<uint64_t>> lin;
-    std::vector<int64_t> nm, nu;
     std::string err;
-    if (!gdh::BamReader::linear_index(b, &lin, &err, nullptr, nullptr, &nm, &s->raw, &nu)) {
-        s->err = "no usable index for " + b + (err.empty() ? "" : ": " + err);
-        return;
-    }
-    for (size_t r = 0; r < nm.size(); ++r)
-        if (nm[r] >= 0) { s->mapped += (uint64_t)nm[r]; s->unmapped += (uint64_t)nu[r]; }
-    s->ref_off.assign(1, 0);
-    for (const auto& iv : s->raw) {
-        for (size_t k = 1; k < iv.size(); ++k) {
-            const int64_t d = (int64_t)iv[k] - (int64_t)iv[k - 1];
-            if (d < 0) { s->err = "expected positive change in vOffset: the linear index of " + b + " decreases"; return; }
-            s->sizes.push_back(d);
-        }
-        s->ref_off.push_back((int64_t)s->sizes.size());
-    }
-    if (s->sizes.empty()) { s->err = "indexcov: no usable chromsomes in bam: " + b; return; }
+    if (!gdh::read_index_sizes(b, s, &s->err)) return;
     if (ends_with(b, ".bai")) {
         gdh::short_name(b, "", &s->name);
     } else {

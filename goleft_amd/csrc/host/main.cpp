@@ -5,6 +5,8 @@
 //   goleft-depth multidepth -c CHROM a.bam b.bam ...            (/root/reference/multidepth, its own binary there)
 //   goleft-depth covstats [-n N] [-r BED] a.bam b.bam ...       (goleft covstats: coverage and insert-size estimates)
 //   goleft-depth indexcov -d DIR [-X X,Y] [-p REGEX] [-n] a.bam b.bam ...   (goleft indexcov: cohort coverage from the .bai indexes)
+//   goleft-depth indexsplit -n N [--fai FAI] [-p BED] a.bam b.bam ...       (goleft indexsplit: N regions of about equal data)
+//   goleft-depth samplename [-e] a.bam                                      (goleft samplename: the @RG SM values)
 //   samtools depth -Q q -d D -r REGION in.bam                   (the same program installed under the NAME samtools,
 //                                                                goleft_amd/shim/samtools: an unmodified goleft finds it on PATH)
 #include <unistd.h>
@@ -58,6 +60,16 @@ int main(int argc, char** argv)
         av.push_back("indexcov");
         for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
         return leave(gdh_indexcov_main((int)av.size(), av.data()));
+    }
+    if (argc > 1 && strcmp(argv[1], "indexsplit") == 0) {
+        av.push_back("indexsplit");
+        for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
+        return leave(gdh_indexsplit_main((int)av.size(), av.data()));
+    }
+    if (argc > 1 && strcmp(argv[1], "samplename") == 0) {
+        av.push_back("samplename");
+        for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
+        return leave(gdh_samplename_main((int)av.size(), av.data()));
     }
     av.push_back("goleft depth");
     int first = 1;

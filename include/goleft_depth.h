@@ -38,11 +38,11 @@ extern "C" {
 #endif
 
 /* GD_ABI_VERSION changes when an existing entry point or structure changes; GD_ABI_REVISION counts the releases that only
- * ADDED entry points since then (revision 1: gd_indexcov_*).  A caller built against (15, r) runs on any (15, r' >= r).
+ * ADDED entry points since then (revision 1: gd_indexcov_*; 2: gd_indexsplit_*).  A caller built against (15, r) runs on any (15, r' >= r).
  * Why indexcov did not become version 16: nothing that existed changed, so callers of ABI 15 need not be turned away, and
  * tests/test_host_cpu.py holds gd_abi_version() to 15 until something does change. */
 #define GD_ABI_VERSION 15
-#define GD_ABI_REVISION 1
+#define GD_ABI_REVISION 2
 
 typedef enum {
     GD_OK = 0,
@@ -612,6 +612,22 @@ int gd_indexcov_gram(gd_ctx* ctx, int64_t* out);
 /* Seconds of the last upload / compute (measurement only): upload, medians + depths, cells / slots / counters / pca8,
  * CN, Gram matrix.  Fills min(n, 5) values. */
 int gd_indexcov_timing(gd_ctx* ctx, double* out, size_t n);
+/* ---- `goleft indexsplit` (indexsplit/indexsplit.go:89-114): the sum of a cohort's tile sizes, cell by cell ----
+ * gd_indexsplit_begin allocates one float64 per cell -- longest[r] cells for each of the n_refs references, one
+ * reference after the other -- and zeroes them; a state of an earlier begin is dropped first.  gd_indexsplit_add
+ * takes a batch of samples in the layout of gd_indexcov_upload (sample_off, sizes, tile_off, tile_cnt; n_refs is
+ * begin's) and adds float64(size) / 1e9 of every tile to its cell, the samples in the order of the calls and then of
+ * the batch: every cell sees the additions the reference makes, in its order, so the sums do not depend on how the
+ * cohort was cut into batches.  A sample may be empty.  A batch is checked before any of it is added: offsets outside
+ * the sample or tile_cnt above longest[r] are GD_E_RANGE, a negative size or a bad sample_off GD_E_INVALID, and the
+ * sums stay as they were.  gd_indexsplit_sums copies the cells out (GD_E_CAPACITY when cap is below their number).
+ * The state goes with the context or with the next gd_indexsplit_begin. */
+int gd_indexsplit_begin(gd_ctx* ctx, int32_t n_refs, const int32_t* longest);
+int gd_indexsplit_add(gd_ctx* ctx, int32_t n_samples, const int64_t* sample_off, const int64_t* sizes,
+                      const int64_t* tile_off, const int32_t* tile_cnt);
+int gd_indexsplit_sums(gd_ctx* ctx, double* out, size_t cap);
+/* Seconds since gd_indexsplit_begin (measurement only): upload, kernel, read-back.  Fills min(n, 3) values. */
+int gd_indexsplit_timing(gd_ctx* ctx, double* out, size_t n);
 int gd_ingest_abort(gd_ctx* ctx);
 /* Page-locked host memory for the byte range handed to gd_ingest_bgzf (read the file
  * straight into it: the H2D copy then runs at PCIe speed instead of through a bounce

@@ -179,6 +179,20 @@ int gdh_fmt3g(uint32_t cell, char* out, size_t cap);
  * written as zeros.  0, or -1 on bad arguments. */
 int gdh_indexcov_pcs(const int64_t* G, int n, int k, double* out, double* sigma);
 
+/* ---- `indexsplit` (indexsplit/indexsplit.go): N regions that hold about the same amount of data across a cohort,
+ * from the .bai linear indexes alone.  argv: -n N [--fai FAI] [-p BED] a.bam|a.bai ...   The references are those of
+ * the first input's header when it is a .bam, else the .fai's.  Rows `chrom \t start \t end \t %.2f sum \t splits`.
+ * .crai / .cram inputs are refused.  Returns the exit code (1 on an error -- an index that cannot be read, a cohort
+ * without data -- with no row written; 255 on a usage error). ---------------------------------------------------- */
+int gdh_indexsplit_main(int argc, const char* const* argv);
+/* Same, writing to out_path (NULL = stdout). */
+int gdh_indexsplit_run(int argc, const char* const* argv, const char* out_path);
+
+/* ---- `samplename` (samplename/samplename.go): the SM values of a BAM header's @RG lines, one per line in order of
+ * first appearance (an empty line when there is none).  argv: [-e] x.bam; -e: exit 2 with the reference's message
+ * unless there is exactly one.  1 when the file cannot be read, 255 on a usage error.  Opens no device. ---------- */
+int gdh_samplename_main(int argc, const char* const* argv);
+
 /* ---- BAM decode (replaces the read side of the samtools child) ---------- */
 /* How `goleft-depth` cuts a BAM into device passes (host/gpu_ingest.hpp; exported for tests):
  * start[r] / has[r] describe the n_refs references of the file (offset of the BGZF member of r's first
@@ -228,6 +242,8 @@ uint64_t gdh_bam_n_records(const gdh_bam* b);
 typedef struct gdh_intervals gdh_intervals;
 /* ReadTree(paths...): BED rows with start >= end are skipped (intervals.go:66). */
 int  gdh_intervals_read(const char* const* paths, int n_paths, gdh_intervals** out);
+/* ReadTree(path) to the letter: a last line that does not end in a newline is not read (intervals.go:57-60). */
+int  gdh_intervals_read_lines(const char* path, gdh_intervals** out);
 void gdh_intervals_free(gdh_intervals* t);
 /* Overlaps(tree[chrom], start, end): half-open overlap test (intervals.go:16-19). */
 int  gdh_intervals_overlaps(const gdh_intervals* t, const char* chrom, int64_t start, int64_t end);
