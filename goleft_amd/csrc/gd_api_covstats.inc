@@ -1,6 +1,7 @@
 // gd_api_covstats.inc -- `goleft covstats` on the fed ranges of the device BAM read: begin (n, skip) / decode (walk,
-// scan, histograms of the oldest pending range) / histogram (part of gd_api.hip, inside extern "C").  The kernels are
-// gd_covstats.hpp's.
+// scan, histograms of the oldest pending range) / histogram (part of gd_api.hip, inside extern "C").  The walk is
+// gd_bamdecode.hpp's, the other kernels gd_covstats.hpp's; what a decode begins with (the oldest range, its inflate, virtual
+// offsets, the walk's page-locked tables) is gd_api_ingest.inc's, shared with the depth read.
 
 namespace {
 
@@ -8,15 +9,12 @@ struct CovState {
     int64_t target = 0, skip_left = 0;
     gd_covstats_counts tot{};                  // over every range decoded since gd_covstats_begin
     std::vector<int64_t> ovf[3];               // overflow values read back after every range
-    // page-locked per-segment tables of the walk (the kernel reads and writes them over the link)
-    uint8_t* h_seg = nullptr; size_t cap_seg = 0;
     void *d_slots = nullptr, *d_recs = nullptr, *d_role = nullptr, *d_tile = nullptr, *d_ovf = nullptr;
     size_t cap_slots = 0, cap_recs = 0, cap_role = 0, cap_tile = 0, cap_ovf = 0;
     unsigned long long* d_acc = nullptr;       // [CS_ACC_WORDS]
     unsigned long long* d_hist = nullptr;      // [3 * CS_HBINS]
     ~CovState()
     {
-        if (h_seg) (void)hipHostFree(h_seg);
         void* frees[] = {d_slots, d_recs, d_role, d_tile, d_ovf, d_acc, d_hist};
         for (void* p : frees) if (p) (void)hipFree(p);
     }
@@ -28,16 +26,6 @@ static void cov_drop(gd_ctx* c)
     (void)hipStreamSynchronize(c->stream);
     delete c->cov;
     c->cov = nullptr;
-}
-
-// The byte offset in the inflated range of virtual offset v; false: v is not inside a member of the range.
-static bool cov_voff(const IngestState* g, uint64_t v, uint64_t* out)
-{
-    const uint64_t coff = v >> 16, uoff = v & 0xffffu;
-    const size_t k = (size_t)(std::lower_bound(g->m_coff.begin(), g->m_coff.end(), coff) - g->m_coff.begin());
-    if (k >= g->nm || g->m_coff[k] != coff || uoff > g->out_len[k]) return false;
-    *out = g->out_off[k] + uoff;
-    return true;
 }
 
 // The virtual offset of byte b of the inflated range (b == total: where the member after the range begins).
@@ -77,19 +65,14 @@ int gd_covstats_decode(gd_ctx* c, uint64_t first_voffset, const uint64_t* anchor
 {
     if (!c || !out || (n_anchors && !anchors)) return GD_E_INVALID;
     if (!c->cov) return fail(c, GD_E_STATE, "gd_covstats_begin has not been called");
-    if (c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
-    if (c->ing_n < 2)
-        if (int r = ingest_join(c)) { (void)gd_ingest_abort(c); return r; }
-    if (int r = set_device(c)) return r;
-    IngestState* g = c->ing_n ? c->ing_q[0] : nullptr;
-    if (!g) return fail(c, GD_E_STATE, "gd_ingest_begin has not been called");
-    struct Guard { gd_ctx* c; bool on; ~Guard() { if (on) (void)gd_ingest_abort(c); } } guard{c, true};
-    if (g->next != g->nm) return fail(c, GD_E_STATE, "only %zu of %zu BGZF members were fed", g->next, g->nm);
+    IngestGuard guard{c, false};
+    IngestState* g = nullptr;
+    if (int r = ingest_oldest(c, &guard, &g)) return r;
     CovState& s = *c->cov;
     const uint64_t total = g->total;
     // ---- segments: the first record, then every anchor of the range behind it -------------------------------
     uint64_t b0 = 0;
-    if (!cov_voff(g, first_voffset, &b0))
+    if (!ingest_voff(g, first_voffset, &b0))
         return fail(c, GD_E_INVALID, "the first record (virtual offset %llu) is not inside a member of the range",
                     (unsigned long long)first_voffset);
     std::vector<uint64_t> beg{b0};
@@ -97,31 +80,16 @@ int gd_covstats_decode(gd_ctx* c, uint64_t first_voffset, const uint64_t* anchor
     for (; a != anchors + n_anchors; ++a) {
         uint64_t b = 0;
         if ((*a >> 16) > g->m_coff[g->nm - 1]) break;       // (behind the range)
-        if (!cov_voff(g, *a, &b) || b >= total) continue;   // (an anchor in a record the range holds only in part)
+        if (!ingest_voff(g, *a, &b) || b >= total) continue;   // (an anchor in a record the range holds only in part)
         if (b > beg.back()) beg.push_back(b);
     }
     const size_t n_seg = beg.size();
     if (n_seg > 0xfffffff0ull) return fail(c, GD_E_RANGE, "too many anchors");
-    const double td0 = ing_now();
-    if (!g->inflated) {
-        for (hipEvent_t e : g->inf_done) HIPCHK(c, hipEventSynchronize(e));
-        for (size_t m = 0; m < g->nm; ++m)
-            if (g->t_status[m] != 0)
-                return fail(c, GD_E_INVALID, "BGZF member at file offset %llu %s (decoder code %u)",
-                            (unsigned long long)g->m_coff[m], g->t_status[m] == 18 ? "fails its CRC32" : "does not inflate", g->t_status[m]);
-        g->inflated = true;
-    }
+    if (int r = ingest_wait_inflated(c, g)) return r;
     const double td1 = ing_now();
-    c->ing_secs[3] += td1 - td0;
-    const size_t seg_bytes = n_seg * (5 * sizeof(uint64_t) + 2 * sizeof(uint32_t));
-    if (seg_bytes > s.cap_seg) {
-        if (s.h_seg) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipHostFree(s.h_seg); s.h_seg = nullptr; s.cap_seg = 0; }
-        const size_t want = std::max<size_t>(2 * seg_bytes + 4096, 1u << 20);
-        if (hipHostMalloc(reinterpret_cast<void**>(&s.h_seg), want, hipHostMallocDefault) != hipSuccess)
-            return fail(c, GD_E_NOMEM, "cannot page-lock the covstats walk's tables");
-        s.cap_seg = want;
-    }
-    uint64_t* t_beg = reinterpret_cast<uint64_t*>(s.h_seg);
+    // the walk's per-segment tables (page-locked: the kernels read and write them over the link)
+    if (int r = ingest_walk_table(c, n_seg * (5 * sizeof(uint64_t) + 2 * sizeof(uint32_t)), "covstats")) return r;
+    uint64_t* t_beg = reinterpret_cast<uint64_t*>(c->h_walk);
     uint64_t* t_end = t_beg + n_seg;
     uint64_t* t_slot = t_end + n_seg;
     uint64_t* t_rbase = t_slot + n_seg;
@@ -146,8 +114,8 @@ int gd_covstats_decode(gd_ctx* c, uint64_t first_voffset, const uint64_t* anchor
     HIPCHK(c, hipStreamSynchronize(c->stream));
     uint64_t N = 0;
     for (size_t i = 0; i < n_seg; ++i) {
-        if (t_flags[i] & 2u) return fail(c, GD_E_INVALID, "corrupt BAM record in covstats segment %zu", i);
-        if (t_flags[i] & 4u) return fail(c, GD_E_INVALID, "anchor %zu is not a record start (stale or foreign index?)", i);
+        if (t_flags[i] & gd::BW_CORRUPT) return fail(c, GD_E_INVALID, "corrupt BAM record in covstats segment %zu", i);
+        if (t_flags[i] & gd::BW_OVERRAN) return fail(c, GD_E_INVALID, "anchor %zu is not a record start (stale or foreign index?)", i);
         if (i + 1 < n_seg && t_endoff[i] != t_end[i])
             return fail(c, GD_E_INVALID, "covstats segment %zu ends inside a record", i);
         t_rbase[i] = N;

@@ -424,69 +424,99 @@ int gd_ingest_feed_fd(gd_ctx* c, int fd, uint64_t offset, size_t n)
     return GD_OK;
 }
 
+// ---- what every decode of a fed range begins with (ingest_decode here, gd_covstats_decode) ----------------------
+// Drops everything pending when a decode fails, unless disarmed.
+struct IngestGuard { gd_ctx* c; bool on; ~IngestGuard() { if (on) (void)gd_ingest_abort(c); } };
+
+// The oldest pending range, ready to decode (every member fed).  From the moment there is a range the guard is armed.
+static int ingest_oldest(gd_ctx* c, IngestGuard* guard, IngestState** out)
+{
+    if (c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
+    if (c->ing_n < 2)                                                 // (with two ranges pending a read in progress fills the newer one)
+        if (int r = ingest_join(c)) { (void)gd_ingest_abort(c); return r; }
+    if (int r = set_device(c)) return r;
+    IngestState* g = c->ing_n ? c->ing_q[0] : nullptr;
+    if (!g) return fail(c, GD_E_STATE, "gd_ingest_begin has not been called");
+    guard->on = true;
+    if (g->next != g->nm) return fail(c, GD_E_STATE, "only %zu of %zu BGZF members were fed", g->next, g->nm);
+    *out = g;
+    return GD_OK;
+}
+
+// Every member of the range is inflated, and inflated well.
+static int ingest_wait_inflated(gd_ctx* c, IngestState* g)
+{
+    const double t0 = ing_now();
+    if (!g->inflated) {
+        for (hipEvent_t e : g->inf_done) HIPCHK(c, hipEventSynchronize(e));
+        for (size_t m = 0; m < g->nm; ++m)                            // (the status words are host memory)
+            if (g->t_status[m] != 0)
+                return fail(c, GD_E_INVALID, "BGZF member at file offset %llu %s (decoder code %u)",
+                            (unsigned long long)g->m_coff[m], g->t_status[m] == 18 ? "fails its CRC32" : "does not inflate", g->t_status[m]);
+        g->inflated = true;
+    }
+    c->ing_secs[3] += ing_now() - t0;
+    return GD_OK;
+}
+
+// The byte offset in the inflated range of virtual offset v; false: v is not inside a member of the range.
+static bool ingest_voff(const IngestState* g, uint64_t v, uint64_t* out)
+{
+    const uint64_t coff = v >> 16, uoff = v & 0xffffu;
+    const size_t k = (size_t)(std::lower_bound(g->m_coff.begin(), g->m_coff.end(), coff) - g->m_coff.begin());
+    if (k >= g->nm || g->m_coff[k] != coff || uoff > g->out_len[k]) return false;
+    *out = g->out_off[k] + uoff;
+    return true;
+}
+
+// A walk's per-segment tables: PAGE-LOCKED HOST memory of the context (c->h_walk, grow-only) that the walk kernels read
+// and write over the link -- four uploads and five read-backs per decode were copy commands that each queued behind the
+// 64 MB pieces of the read in progress; and a per-call device buffer ended in a hipFree, a device-wide wait.  (One table
+// for the depth read and covstats: both decode ing_q[0], so never at once.)
+static int ingest_walk_table(gd_ctx* c, size_t bytes, const char* whose)
+{
+    if (bytes <= c->cap_walk) return GD_OK;
+    if (c->h_walk) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipHostFree(c->h_walk); c->h_walk = nullptr; c->cap_walk = 0; }   // (a kernel of the last call may still read it)
+    const size_t want = std::max<size_t>(2 * bytes + 4096, 2u << 20);   // (rarely again: see IngestBufs::fit_host)
+    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_walk), want, hipHostMallocDefault) != hipSuccess)
+        return fail(c, GD_E_NOMEM, "cannot page-lock the %s walk's tables", whose);
+    c->cap_walk = want;
+    return GD_OK;
+}
+
 // One reference of the fed range -> contig tid.  release: the range is dropped afterwards (always on error).
 static int ingest_decode(gd_ctx* c, int32_t tid, int32_t ref_id, const uint64_t* anchors, size_t n_anchors,
                          uint64_t* n_records, bool release, uint64_t end_anchor = 0, bool append = false,
                          double expect_scale = 0.0)
 {
     if (!c || !anchors || n_anchors == 0) return GD_E_INVALID;
-    if (c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
-    if (c->ing_n < 2)                                                 // (with two ranges pending a read in progress fills the newer one)
-        if (int r = ingest_join(c)) { (void)gd_ingest_abort(c); return r; }
-    if (int r = set_device(c)) return r;
-    IngestState* g = c->ing_n ? c->ing_q[0] : nullptr;                // the oldest pending range
-    if (!g) return fail(c, GD_E_STATE, "gd_ingest_begin has not been called");
-    struct Guard { gd_ctx* c; bool on; ~Guard() { if (on) (void)gd_ingest_abort(c); } } guard{c, true};   // everything pending is dropped on an error
+    IngestGuard guard{c, false};
+    IngestState* g = nullptr;
+    if (int r = ingest_oldest(c, &guard, &g)) return r;
     if (tid < 0 || (size_t)tid >= c->contigs.size()) return fail(c, GD_E_RANGE, "tid %d out of range", tid);
     if (n_anchors > 0xfffffff0ull) return fail(c, GD_E_RANGE, "too many anchors");
-    if (g->next != g->nm) return fail(c, GD_E_STATE, "only %zu of %zu BGZF members were fed", g->next, g->nm);
-    const size_t nm = g->nm;
     const uint64_t total = g->total;
     // ---- anchors (virtual offsets) -> byte offsets in the inflated range ----------------------
     std::vector<uint64_t> seg_beg(n_anchors), seg_end(n_anchors);
     for (size_t i = 0; i < n_anchors; ++i) {
-        const uint64_t coff = anchors[i] >> 16, uoff = anchors[i] & 0xffffu;
-        const size_t k = (size_t)(std::lower_bound(g->m_coff.begin(), g->m_coff.end(), coff) - g->m_coff.begin());
-        if (k >= nm || g->m_coff[k] != coff || uoff > g->out_len[k])
+        if (!ingest_voff(g, anchors[i], &seg_beg[i]))
             return fail(c, GD_E_INVALID, "anchor %zu (virtual offset %llu) is not inside a member of the range", i,
                         (unsigned long long)anchors[i]);
-        seg_beg[i] = g->out_off[k] + uoff;
         if (i && seg_beg[i] <= seg_beg[i - 1]) return fail(c, GD_E_INVALID, "anchors must be strictly ascending");
         if (i) seg_end[i - 1] = seg_beg[i];
     }
     seg_end[n_anchors - 1] = total;                   // a record of another reference ends the last walk earlier
     if (end_anchor) {                                 // one part of a reference: up to the first record of the next part
-        const uint64_t coff = end_anchor >> 16, uoff = end_anchor & 0xffffu;
-        const size_t k = (size_t)(std::lower_bound(g->m_coff.begin(), g->m_coff.end(), coff) - g->m_coff.begin());
-        if (k >= nm || g->m_coff[k] != coff || uoff > g->out_len[k] || g->out_off[k] + uoff <= seg_beg[n_anchors - 1])
+        uint64_t e = 0;
+        if (!ingest_voff(g, end_anchor, &e) || e <= seg_beg[n_anchors - 1])
             return fail(c, GD_E_INVALID, "the part's end (virtual offset %llu) is not inside a member of the range behind its last anchor",
                         (unsigned long long)end_anchor);
-        seg_end[n_anchors - 1] = g->out_off[k] + uoff;
+        seg_end[n_anchors - 1] = e;
     }
-    const double td0 = ing_now();
-    if (!g->inflated) {
-        for (hipEvent_t e : g->inf_done) HIPCHK(c, hipEventSynchronize(e));      // every member of this range is inflated
-        for (size_t m = 0; m < nm; ++m)                                           // (the status words are host memory)
-            if (g->t_status[m] != 0)
-                return fail(c, GD_E_INVALID, "BGZF member at file offset %llu %s (decoder code %u)",
-                            (unsigned long long)g->m_coff[m], g->t_status[m] == 18 ? "fails its CRC32" : "does not inflate", g->t_status[m]);
-        g->inflated = true;
-    }
-
+    if (int r = ingest_wait_inflated(c, g)) return r;
     const double td1 = ing_now();
-    c->ing_secs[3] += td1 - td0;
     // ---- count the records of every anchor segment ----------------------------------------------
-    // the walk's per-segment tables: PAGE-LOCKED HOST memory of the context (grow-only) that the walk kernels read and
-    // write over the link -- four uploads and five read-backs per decode were copy commands that each queued behind the
-    // 64 MB pieces of the read in progress; and a per-call device buffer ended in a hipFree, a device-wide wait
-    const size_t seg_bytes = n_anchors * 6 * sizeof(uint64_t) + n_anchors * 4 * sizeof(uint32_t);
-    if (seg_bytes > c->cap_walk) {
-        if (c->h_walk) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipHostFree(c->h_walk); c->h_walk = nullptr; c->cap_walk = 0; }
-        const size_t want = std::max<size_t>(2 * seg_bytes + 4096, 2u << 20);   // (rarely again: see IngestBufs::fit_host)
-        if (hipHostMalloc(reinterpret_cast<void**>(&c->h_walk), want, hipHostMallocDefault) != hipSuccess)
-            return fail(c, GD_E_NOMEM, "cannot page-lock the record walk's tables");
-        c->cap_walk = want;
-    }
+    if (int r = ingest_walk_table(c, n_anchors * 6 * sizeof(uint64_t) + n_anchors * 4 * sizeof(uint32_t), "record")) return r;
     uint64_t* s_beg = reinterpret_cast<uint64_t*>(c->h_walk);
     uint64_t* s_end = s_beg + n_anchors;
     uint64_t* s_rbase = s_end + n_anchors;
@@ -535,37 +565,29 @@ static int ingest_decode(gd_ctx* c, int32_t tid, int32_t ref_id, const uint64_t*
     hipLaunchKernelGGL(gd::gd_bam_walk_kernel<false>, dim3(seg_grid), dim3(64), 0, ws, bj);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(ws));
-    const uint32_t* const nrec = s_nrec;
-    const uint64_t* const nops = s_nops;
-    const int32_t* const firstp = s_first;
-    const int32_t* const lastp = s_last;
-    const uint32_t* const flags = s_flags;
     const double td2 = ing_now();
     c->ing_secs[4] += td2 - td1;
-    uint64_t* const rbase = s_rbase;                      // (written in place: the extracting walk reads them from there)
-    uint64_t* const obase = s_obase;
-    if (tid < 0 || (size_t)tid >= c->contigs.size()) return fail(c, GD_E_RANGE, "tid %d out of range", tid);
     if (append && c->contigs[tid].adopted) return fail(c, GD_E_STATE, "contig %d holds adopted device records", tid);
     const uint64_t N0 = append ? c->contigs[tid].n_reads : 0, M0 = append ? c->contigs[tid].n_ops : 0;
     uint64_t N = 0, M = 0;
     int32_t prev_last = append ? c->contigs[tid].last_pos : -0x7fffffff;
     bool left = append && c->contigs[tid].ing_left;      // a record of another reference has been met
     for (size_t i = 0; i < n_anchors; ++i) {
-        if (flags[i] & 2u) return fail(c, GD_E_INVALID, "corrupt BAM record in anchor segment %zu", i);
+        if (s_flags[i] & gd::BW_CORRUPT) return fail(c, GD_E_INVALID, "corrupt BAM record in anchor segment %zu", i);
         // a coordinate-sorted BAM holds a reference's records in ONE run: records of this one after a record of
         // another (a walk that a foreign record ended, then a later anchor with records again) are refused, as the
         // host decoder refuses them -- `samtools depth -r` would silently stop at the foreign record
-        if ((left && nrec[i]) || (flags[i] & 16u))
+        if ((left && s_nrec[i]) || (s_flags[i] & gd::BW_REF_RESUMES))
             return fail(c, GD_E_UNSORTED, "contig %d: records continue after a record of another reference (anchor segment %zu)", tid, i);
-        if (flags[i] & 8u) left = true;
-        if (flags[i] & 4u) return fail(c, GD_E_INVALID, "anchor %zu is not a record start (stale or foreign index?)", i + 1);
-        if ((flags[i] & 1u) || (nrec[i] && firstp[i] < prev_last))
+        if (s_flags[i] & gd::BW_LEFT_REF) left = true;
+        if (s_flags[i] & gd::BW_OVERRAN) return fail(c, GD_E_INVALID, "anchor %zu is not a record start (stale or foreign index?)", i + 1);
+        if ((s_flags[i] & gd::BW_UNSORTED) || (s_nrec[i] && s_first[i] < prev_last))
             return fail(c, GD_E_UNSORTED, "contig %d: records not coordinate sorted (anchor segment %zu)", tid, i);
-        if (nrec[i]) prev_last = lastp[i];
-        rbase[i] = N0 + N;
-        obase[i] = M0 + M;
-        N += nrec[i];
-        M += nops[i];
+        if (s_nrec[i]) prev_last = s_last[i];
+        s_rbase[i] = N0 + N;                          // (in place: the extraction reads them from there)
+        s_obase[i] = M0 + M;
+        N += s_nrec[i];
+        M += s_nops[i];
     }
     if (M0 + M > 0xffffffffull) return fail(c, GD_E_RANGE, "more than 2^32 CIGAR ops on contig %d", tid);
     if (N0 + N >= kMaxReadsPerContig) return fail(c, GD_E_RANGE, "more than 2^30 records on contig %d", tid);

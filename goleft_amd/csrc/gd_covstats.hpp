@@ -1,9 +1,9 @@
 // gd_covstats.hpp -- `goleft covstats` on the device: every record of a fed range in file order, the reference's
 // sampling loop as a scan, and histograms of what it samples (covstats/covstats.go:122-220).
-//   gd_cs_walk_kernel     one wave per segment (the LDS-staged walk of gd_bamdecode.hpp), but a segment runs across
-//                         references and through the unplaced tail: it ends at the next anchor or, for the range's last
-//                         segment, at the first record the range does not hold completely.  Every record is extracted to
-//                         a CsRec slot of its segment (room for a record per 36 bytes)
+//   gd_cs_walk_kernel     (gd_bamdecode.hpp: the one record walk under its covstats policy) one wave per segment; a
+//                         segment runs across references and through the unplaced tail: it ends at the next anchor or,
+//                         for the range's last segment, at the first record the range does not hold completely.  Every
+//                         record is extracted to a CsRec slot of its segment (room for a record per 36 bytes)
 //   gd_cs_compact_kernel  the slots of every segment -> one dense array in file order
 //   gd_cs_tile_kernel     per tile of records: how many are "good" (mapped, neither duplicate nor QC-failed) and how
 //                         many are eligible for an insert
@@ -13,32 +13,9 @@
 //   gd_cs_hist_kernel     the counts over [0, stop], and the sizes / inserts / template lengths into dense histograms
 //                         (a wave adds its most common bin with one atomic) with an overflow list for what falls outside
 #pragma once
+#include "gd_bamdecode.hpp"
 
 namespace gd {
-
-// One record as the sampling loop sees it.
-struct CsRec {
-    uint32_t flag;
-    int32_t  pos, next_pos, tlen;
-    uint32_t mlen;                  // the length of the only CIGAR op when that op is M, else CS_NOT_M
-    uint32_t pad;
-    uint64_t qlen;                  // query length of the stored CIGAR: M, I, S, =, X
-};
-constexpr uint32_t CS_NOT_M = 0xffffffffu;
-
-struct CsWalkJob {
-    const uint8_t* data;            // inflated bytes of the range
-    uint64_t n_bytes;
-    const uint64_t* seg_beg;        // [n_seg] first record of the segment
-    const uint64_t* seg_end;        // [n_seg] next anchor (the last segment: n_bytes)
-    const uint64_t* slot_base;      // [n_seg] first slot of the segment in `slots`
-    uint32_t n_seg;
-    uint32_t open_end;              // more of the file follows: the last segment may end in a record cut by the range's end
-    CsRec* slots;
-    uint32_t* n_rec;                // [n_seg]
-    uint64_t* end_off;              // [n_seg] where the walk stopped
-    uint32_t* flags;                // [n_seg] bit1 corrupt record, bit2 the walk overran seg_end (an anchor that is no record start)
-};
 
 // Role bits of a record in the sampling loop (gd_cs_select_kernel).
 enum : uint32_t {
@@ -70,113 +47,10 @@ struct CsScanJob {
     uint64_t ovf_cap;
 };
 
-__device__ __forceinline__ uint32_t cs_ld32(const uint8_t* p)
-{
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-
 __device__ __forceinline__ bool cs_good(const CsRec& r) { return !(r.flag & 0x4u) && !(r.flag & 0x600u); }
 __device__ __forceinline__ bool cs_eligible(const CsRec& r)
 {
     return cs_good(r) && (r.flag & 0x2u) && r.pos < r.next_pos && r.mlen != CS_NOT_M;
-}
-
-// LDS as in gd_bam_walk_kernel: 3 KB of stream + the round's tables.
-__global__ __launch_bounds__(64) void gd_cs_walk_kernel(CsWalkJob j)
-{
-    constexpr int WIN = 3072, REC = 32;
-    __shared__ __attribute__((aligned(16))) uint8_t s_win[WIN];
-    __shared__ uint64_t s_off[REC];
-    __shared__ uint64_t s_wbase;
-    __shared__ uint32_t s_n, s_done, s_bad;
-    const uint32_t s = blockIdx.x;
-    if (s >= j.n_seg) return;
-    const uint32_t lane = threadIdx.x;
-    const bool last = s + 1 == j.n_seg;
-    const uint64_t stop = j.seg_end[s];
-    uint64_t off = j.seg_beg[s];
-    uint32_t fl = 0;
-    uint64_t ri = 0;                                        // records of the segment so far (every lane's copy)
-    CsRec* const out = j.slots + j.slot_base[s];
-    if (lane == 0) { s_wbase = off & ~15ull; s_done = off < stop ? 0u : 1u; s_n = 0; s_bad = 0; }
-    __syncthreads();
-    while (s_done == 0u) {
-        const uint64_t wbase = s_wbase;
-        for (uint32_t i = lane; i < WIN / 16; i += 64) {
-            const uint64_t a = wbase + 16ull * i;
-            uint32_t w[4] = {0, 0, 0, 0};
-            if (a + 16 <= j.n_bytes) __builtin_memcpy(w, j.data + a, 16);
-            else if (a < j.n_bytes) __builtin_memcpy(w, j.data + a, (size_t)(j.n_bytes - a));
-            __builtin_memcpy(s_win + 16u * i, w, 16);
-        }
-        __syncthreads();
-        // lane 0: the block_size chain in LDS.  No refID test: covstats reads every record in file order
-        if (lane == 0) {
-            uint32_t k = 0, done = 0;
-            while (k < (uint32_t)REC) {
-                if (off >= stop) { done = 1; break; }
-                const uint64_t rel = off - wbase;
-                if (rel + 4 > (uint64_t)WIN) break;
-                // a record the range holds only in part: the next range begins with it (the last segment of a range
-                // that is not the file's last); anywhere else the bytes are damaged
-                if (off + 4 > j.n_bytes) { if (!(last && j.open_end)) fl |= 2u; done = 1; break; }
-                const uint32_t block_size = cs_ld32(s_win + rel);
-                if (block_size < 32) { fl |= 2u; done = 1; break; }
-                if (off + 4 + block_size > j.n_bytes) { if (!(last && j.open_end)) fl |= 2u; done = 1; break; }
-                s_off[k++] = off;
-                off += 4ull + block_size;
-            }
-            if (!done && off >= stop) done = 1;
-            s_n = k;
-            s_done = done;
-            s_wbase = off & ~15ull;
-        }
-        __syncthreads();
-        const uint32_t n = s_n;
-        if (lane < n) {
-            const uint64_t o = s_off[lane];
-            const uint32_t block_size = cs_ld32(j.data + o);
-            const uint8_t* const r = j.data + o + 4;
-            const uint32_t l_read_name = r[8];
-            const uint32_t n_cigar = (uint32_t)r[12] | ((uint32_t)r[13] << 8);
-            CsRec c;
-            c.flag = (uint32_t)r[14] | ((uint32_t)r[15] << 8);
-            c.pos = (int32_t)cs_ld32(r + 4);
-            c.next_pos = (int32_t)cs_ld32(r + 24);
-            c.tlen = (int32_t)cs_ld32(r + 28);
-            c.mlen = CS_NOT_M;
-            c.pad = 0;
-            c.qlen = 0;
-            if (32ull + l_read_name + 4ull * n_cigar > block_size) {
-                atomicOr(&s_bad, 1u);
-            } else {
-                // the STORED CIGAR: the reference reads with everything variable-length but the CIGAR omitted, so a
-                // CG:B,I tag is not resolved and the <l_seq>S<ref_len>N placeholder counts as it stands
-                const uint8_t* const cg = r + 32 + l_read_name;
-                for (uint32_t q = 0; q < n_cigar; ++q) {
-                    const uint32_t op = cs_ld32(cg + 4ull * q), t = op & 0xfu;
-                    if (t == 0u || t == 1u || t == 4u || t == 7u || t == 8u) c.qlen += op >> 4;
-                }
-                if (n_cigar == 1u) {
-                    const uint32_t op = cs_ld32(cg);
-                    if ((op & 0xfu) == 0u) c.mlen = op >> 4;
-                }
-            }
-            out[ri + lane] = c;
-        }
-        ri += n;
-        __syncthreads();
-        if (lane == 0 && s_bad) { fl |= 2u; s_done = 1; }
-        __syncthreads();
-    }
-    if (lane == 0) {
-        if (off > stop) fl |= 4u;
-        j.n_rec[s] = (uint32_t)ri;
-        j.end_off[s] = off;
-        j.flags[s] = fl;
-    }
 }
 
 // The segments' slots -> the dense array (a workgroup per segment).

@@ -1,6 +1,7 @@
 """CPU: the device BAM record walk (goleft_amd/csrc/gd_bamdecode.hpp) compiled for the HOST and run lane by lane
-(tests/emul/bamwalk_emul.cpp), the inflated stream and every output array ending exactly at an inaccessible page.  On
-intact streams the two passes deliver what the records say; on damaged streams -- the fields a walk trusts flipped:
+(tests/emul/bamwalk_emul.cpp), the inflated stream and every output array ending exactly at an inaccessible page -- under
+the depth read's policy (the two passes) and under covstats' (every record to a CsRec slot).  On
+intact streams the walks deliver what the records say; on damaged streams -- the fields a walk trusts flipped:
 block_size, refID, POS, l_read_name, n_cigar_op, l_seq, the CIGAR, the CG tag -- the walk must terminate and never
 touch a byte outside the stream or its outputs (a stray access is a segmentation fault of the child process).  The GPU
 twin of this test (tests/test_gpu_bamdecode.py::test_device_bam_walker_mutation_fuzz) compares with the host decoder;
@@ -34,6 +35,8 @@ def _lib():
     lib.emul_bam_walk.argtypes = ([C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32] + [C.c_void_p] * 7 +
                                   [C.c_uint64, C.c_uint64] + [C.c_void_p] * 5)
     lib.emul_bam_walk.restype = C.c_int
+    lib.emul_cs_walk.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint64, C.c_void_p]
+    lib.emul_cs_walk.restype = C.c_int
     lib.emul_bam_walk_mode(C.c_int(MODE))
     return lib
 
@@ -171,4 +174,112 @@ def test_damaged_streams_never_leave_their_buffers(seed):
     r = subprocess.run([sys.executable, "-c", FUZZ % H.ROOT, str(seed)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.returncode, r.stdout[-300:], r.stderr[-2000:])
     clean, refused = int(r.stdout.split()[1]), int(r.stdout.split()[3])
+    assert clean + refused == 120 and refused > 20
+
+
+# ---- the covstats walk (gd_cs_walk_kernel: the same bam_walk under the CsWalk policy) ---------------------------------
+
+CS_REC = np.dtype([("flag", "<u4"), ("pos", "<i4"), ("next_pos", "<i4"), ("tlen", "<i4"), ("mlen", "<u4"), ("pad", "<u4"),
+                   ("qlen", "<u8")])
+CS_NOT_M = 0xffffffff
+CORRUPT, OVERRAN = 2, 4                  # gd::BW_CORRUPT, gd::BW_OVERRAN
+
+
+def cs_walk(data: bytes, anchors, open_end):
+    """The covstats walk over the segments [anchor_i, anchor_i+1) (the last one to the end of the stream).
+    -> (rc, per-segment dict, records in file order or None)"""
+    lib = _lib()
+    raw = np.frombuffer(data, np.uint8)
+    beg = np.asarray(anchors, np.uint64)
+    end = np.concatenate([beg[1:], [len(data)]]).astype(np.uint64)
+    n = len(beg)
+    n_rec = np.zeros(n, np.uint32); end_off = np.zeros(n, np.uint64); flags = np.zeros(n, np.uint32)
+    N = C.c_uint64(0)
+    cap = len(data) // 36 + 1
+    recs = np.zeros(cap, CS_REC)
+    rc = lib.emul_cs_walk(raw.ctypes.data, len(data), beg.ctypes.data, end.ctypes.data, n, open_end, n_rec.ctypes.data,
+                          end_off.ctypes.data, flags.ctypes.data, C.byref(N), cap, recs.ctypes.data)
+    seg = dict(n_rec=n_rec, end_off=end_off, flags=flags, seg_end=end)
+    return rc, seg, (recs[:N.value] if rc == 0 else None)
+
+
+def parse_cs(d: bytes, starts):
+    """What a CsRec must hold for the records at `starts`: a direct parse of the bytes, the STORED CIGAR as it stands."""
+    out = np.zeros(len(starts), CS_REC)
+    for i, p in enumerate(starts):
+        bs, ref, pos, l_name, mapq, bin_, n_cigar, flag, l_seq, next_ref, next_pos, tlen = struct.unpack_from("<iiiBBHHHIiii", d, p)
+        ops = struct.unpack_from("<%dI" % n_cigar, d, p + 36 + l_name)
+        qlen = sum(op >> 4 for op in ops if (op & 0xf) in (0, 1, 4, 7, 8))
+        mlen = ops[0] >> 4 if n_cigar == 1 and (ops[0] & 0xf) == 0 else CS_NOT_M
+        out[i] = (flag, pos, next_pos, tlen, mlen, 0, qlen)
+    return out
+
+
+@pytest.mark.parametrize("long_cigars", [False, True])
+def test_cs_walk_delivers_every_record(tmp_path, long_cigars):
+    data, contigs, reads = make_stream(tmp_path, 1, long_cigars)
+    starts, n_ref = record_starts(data)
+    every = [p for p, ref in starts]                          # ALL references and the unplaced tail
+    assert {ref for p, ref in starts} == {0, 2, -1}
+    want = parse_cs(data, every)
+    if long_cigars:                                           # the <l_seq>S<ref_len>N placeholder counts as stored: its S is the query length
+        ph = [i for i, p in enumerate(every) if struct.unpack_from("<i", data, p)[0] > 4 * 65_535]   # (only a CG:B,I tag is that long)
+        assert ph and all(struct.unpack_from("<H", data, every[i] + 16)[0] == 2 and want["mlen"][i] == CS_NOT_M and
+                          want["qlen"][i] == struct.unpack_from("<I", data, every[i] + 20)[0] for i in ph)
+    for step in (1, 7, 64, len(every)):                       # a segment per record ... one segment for the whole range
+        for open_end in (0, 1):
+            rc, seg, recs = cs_walk(data, every[::step], open_end)
+            assert rc == 0 and not seg["flags"].any()
+            assert int(seg["n_rec"].sum()) == len(every)
+            assert np.array_equal(seg["end_off"], seg["seg_end"])
+            assert np.array_equal(recs, want)
+
+
+def test_cs_walk_a_stream_cut_inside_a_record(tmp_path):
+    data, contigs, reads = make_stream(tmp_path, 1)
+    starts, n_ref = record_starts(data)
+    every = [p for p, ref in starts]
+    k = len(every) - 40
+    for inside in (2, 20, every[k + 1] - every[k] - 1):       # in block_size, in the fixed fields, one byte short of whole
+        d = data[:every[k] + inside]
+        want = parse_cs(d, every[:k])
+        for anchors in (every[:k + 1:7], every[:1]):
+            # the cut record is the last segment's: the next range begins with it when more of the file follows
+            rc, seg, recs = cs_walk(d, anchors, 1)
+            assert rc == 0 and not seg["flags"].any()
+            assert int(seg["end_off"][-1]) == every[k] and np.array_equal(recs, want)
+            rc, seg, recs = cs_walk(d, anchors, 0)
+            assert rc == 1 and seg["flags"][-1] & CORRUPT and not seg["flags"][:-1].any()
+        # the cut inside a segment that is not the last (its end lies behind the stream's): damaged in both modes
+        for open_end in (0, 1):
+            rc, seg, recs = cs_walk(d, [every[0], every[k + 5]], open_end)
+            assert rc == 1 and seg["flags"][0] & CORRUPT
+
+
+def test_cs_walk_an_anchor_that_is_no_record_start(tmp_path):
+    data, contigs, reads = make_stream(tmp_path, 1)
+    starts, n_ref = record_starts(data)
+    every = [p for p, ref in starts]
+    for open_end in (0, 1):
+        # the walk overruns the next anchor (bit 2) or meets a corrupt record (bit 1)
+        rc, seg, _ = cs_walk(data, [every[0], every[5] + 3, every[9]], open_end)
+        assert rc == 1 and (seg["flags"] & (CORRUPT | OVERRAN)).any()
+
+
+# The same damage as FUZZ (fields, seeds, cases), the covstats walk over it; every other case with more of the file to follow.
+_DEPTH_CALL = FUZZ[FUZZ.index("    rc, seg, arr = T.walk("):FUZZ.index("    else:\n        refused += 1")]
+FUZZ_CS = FUZZ.replace(_DEPTH_CALL, """    rc, seg, recs = T.cs_walk(bytes(d), anchors, case %% 2)
+    if rc == 0:
+        clean += 1
+        assert len(recs) == int(seg["n_rec"].sum()) and int(seg["end_off"][-1]) <= len(d)
+""")
+
+
+@pytest.mark.parametrize("seed", range(4))
+def test_damaged_streams_never_leave_the_cs_walks_buffers(seed):
+    r = subprocess.run([sys.executable, "-c", FUZZ_CS % H.ROOT, str(seed)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.returncode, r.stdout[-300:], r.stderr[-2000:])
+    clean, refused = int(r.stdout.split()[1]), int(r.stdout.split()[3])
+    # (this walk has no refID or sortedness test and refuses fewer than the depth walk: 73 / 88 / 70 / 76 of 120 for the
+    # four seeds, where the depth walk refuses 95 / 103 / 88 / 93)
     assert clean + refused == 120 and refused > 20

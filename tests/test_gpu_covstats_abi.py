@@ -23,7 +23,7 @@ from oracle import bamio
 from tests import covstats_ref as R
 
 GD_E_INVALID, GD_E_STATE, GD_E_CAPACITY = -1, -4, -8
-WIN, REC = 3072, 32                      # gd_cs_walk_kernel: bytes of stream in LDS, records per round
+WIN, REC = 3072, 32                      # BW_WIN, BW_REC of gd_bamdecode.hpp (the one walk, gd_cs_walk_kernel included): bytes of stream in LDS, records per round
 SLOT_BYTES = 36                          # gd_covstats_decode: a slot per 36 bytes of a segment, plus one
 CS_TILE, CS_HBINS = 1024, 1 << 16        # gd_covstats.hpp
 LO = (0, -(CS_HBINS // 2), -(CS_HBINS // 2))   # CS_LO_SIZE, CS_LO_INS, CS_LO_TL
