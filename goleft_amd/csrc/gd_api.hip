@@ -141,16 +141,13 @@ void gd_destroy(gd_ctx* c)
     is_drop(c);
     (void)gd_comm_destroy(c);
     for (hipEvent_t e : c->comm_ev) if (e) (void)hipEventDestroy(e);
-    for (int k = 0; k < 8; ++k) {
+    for (int k = 0; k < 2; ++k) {
         if (c->ing_stage[k]) (void)hipHostFree(c->ing_stage[k]);
         if (c->ing_staged[k]) (void)hipEventDestroy(c->ing_staged[k]);
+        if (c->ing_hp_done[k]) (void)hipEventDestroy(c->ing_hp_done[k]);
     }
     for (hipStream_t st : c->ing_stream) if (st) (void)hipStreamDestroy(st);
-    for (hipStream_t st : c->ing_dma) if (st) (void)hipStreamDestroy(st);
     if (c->ing_hp) (void)hipStreamDestroy(c->ing_hp);
-    if (c->ing_walk) (void)hipStreamDestroy(c->ing_walk);
-    if (c->ing_walk_ev) (void)hipEventDestroy(c->ing_walk_ev);
-    for (auto& evs : c->ing_dma_ev) for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
     for (auto& b : c->ing_bufs) b.drop_all();
     if (c->h_walk) (void)hipHostFree(c->h_walk);
     if (c->d_rectab) (void)hipFree(c->d_rectab);
@@ -892,26 +889,16 @@ int gd_wait_event(gd_ctx* c, void* ev)
     return GD_OK;
 }
 
+// What the retired options (include/goleft_depth.h) were at in every library that shipped.
+static int retired_option_default(int option)
+{
+    return option == GD_OPT_INGEST_PIECE_STREAMS ? 1 : option == GD_OPT_INGEST_BATCHES ? 8 : 0;
+}
+
 int gd_set_option(gd_ctx* c, int option, int64_t value)
 {
     if (c && c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
     if (!c) return GD_E_INVALID;
-#ifndef GD_MEASURE
-    // The switches of measurement builds (-DGD_MEASURE; include/goleft_depth.h lists them apart): every one of them was measured
-    // neutral or worse (DESIGN.md / HISTORY.md), a release library holds them at their defaults and says so when asked for
-    // anything else.
-    {
-        bool other = false;
-        switch (option) {
-        case GD_OPT_INGEST_DMA: other = value > 1; break;
-        case GD_OPT_INGEST_PIECE_STREAMS: other = value != 1; break;
-        case GD_OPT_INGEST_HYBRID: case GD_OPT_INGEST_WALK_CUS: case GD_OPT_INFLATE_LDS_PAD: other = value != 0; break;
-        case GD_OPT_INGEST_BATCHES: other = value != 8; break;
-        default: break;
-        }
-        if (other) return fail(c, GD_E_INVALID, "option %d = %lld is a switch of measurement builds (-DGD_MEASURE); this library keeps it at its default", option, (long long)value);
-    }
-#endif
     switch (option) {
     case GD_OPT_NT_STORES: c->tile_opt = value ? 1 : 0; break;
     case GD_OPT_FAST_KERNEL: c->fast_kernel = value != 0; break;
@@ -926,8 +913,8 @@ int gd_set_option(gd_ctx* c, int option, int64_t value)
         break;
     case GD_OPT_INGEST_CRC: c->ingest_crc = value != 0; break;
     case GD_OPT_INGEST_DMA:
-        if (value < 0 || value > 4) return fail(c, GD_E_INVALID, "ingest DMA streams: 1 .. 4 (0: a copy kernel on a high-priority stream)");
-        c->ing_dma_n = (int)value;
+        if (value != 0 && value != 1) return fail(c, GD_E_INVALID, "ingest DMA: 1 (a copy command) or 0 (a copy kernel on a high-priority stream)");
+        c->ing_copy_engine = value == 1;
         break;
     case GD_OPT_BAM_REFS:
         if (value < 0 || value > 0x7fffffff) return fail(c, GD_E_INVALID, "BAM references: 0 (unknown) .. 2^31 - 1");
@@ -950,7 +937,6 @@ int gd_set_option(gd_ctx* c, int option, int64_t value)
         if (value != 0 && value != 1) return fail(c, GD_E_INVALID, "commit check: 0 (host, in gd_commit) or 1 (device, deferred)");
         c->commit_check_device = value == 1;
         break;
-    case GD_OPT_INGEST_HYBRID: c->ing_hybrid = value != 0; break;
     case GD_OPT_INGEST_CU_SPLIT:
         if (value < 0 || value > 64 || value == 1) return fail(c, GD_E_INVALID, "ingest CU split: 0 (off) or 2 .. 64");
         if (c->ing_stream[0] || c->ing_hp) return fail(c, GD_E_STATE, "the ingest streams exist already: set GD_OPT_INGEST_CU_SPLIT before the first gd_ingest_begin");
@@ -960,26 +946,15 @@ int gd_set_option(gd_ctx* c, int option, int64_t value)
         if (value < 0) return fail(c, GD_E_INVALID, "ingest range hint: bytes >= 0");
         c->ing_range_hint = (uint64_t)value;
         break;
-    case GD_OPT_INFLATE_LDS_PAD:
-        if (value < 0 || value > 120 * 1024) return fail(c, GD_E_INVALID, "inflate LDS pad: 0 .. 122880 bytes");
-        c->inflate_pad = (unsigned)value;
-        break;
-    case GD_OPT_INGEST_BATCHES:
-        if (value < 1 || value > 64) return fail(c, GD_E_INVALID, "ingest batches: 1 .. 64 inflate launches per range");
-        c->ing_batches = (int)value;
-        break;
-    case GD_OPT_INGEST_WALK_CUS:
-        if (c->ing_walk) return fail(c, GD_E_STATE, "the ingest streams exist already: set GD_OPT_INGEST_WALK_CUS before the first gd_ingest_begin");
-        c->ing_walk_cus = value != 0;
-        break;
     case GD_OPT_INFLATE_KERNEL:
         if (value < 0 || value > 1) return fail(c, GD_E_INVALID, "inflate kernel: 0 (a lane per member) or 1 (a workgroup per member)");
         c->inflate_kernel = (int)value;
         break;
-    case GD_OPT_INGEST_PIECE_STREAMS:
-        if (value < 1 || value > 4) return fail(c, GD_E_INVALID, "ingest piece streams: 1 .. 4");
-        if (c->ing_n) return fail(c, GD_E_STATE, "a device BAM read is pending");
-        c->ing_piece_streams = (int)value;
+    // retired (include/goleft_depth.h): the number is reserved and only the default is accepted
+    case GD_OPT_INGEST_PIECE_STREAMS: case GD_OPT_INFLATE_LDS_PAD: case GD_OPT_INGEST_HYBRID: case GD_OPT_INGEST_BATCHES:
+    case GD_OPT_INGEST_WALK_CUS:
+        if (value != retired_option_default(option))
+            return fail(c, GD_E_INVALID, "option %d is retired: only its default, %d, is accepted", option, retired_option_default(option));
         break;
     default: return fail(c, GD_E_INVALID, "unknown option %d", option);
     }
@@ -996,21 +971,18 @@ int gd_get_option(gd_ctx* c, int option, int64_t* value)
     case GD_OPT_COPY_THREADS: *value = c->ing_copy_threads; break;
     case GD_OPT_H2D_KERNEL: *value = c->h2d_kernel ? (int64_t)std::max(1u, c->h2d_grid) : 0; break;
     case GD_OPT_INGEST_CRC: *value = c->ingest_crc; break;
-    case GD_OPT_INGEST_DMA: *value = c->ing_dma_n; break;
+    case GD_OPT_INGEST_DMA: *value = c->ing_copy_engine; break;
     case GD_OPT_BAM_REFS: *value = c->bam_n_ref; break;
     case GD_OPT_PUSH_CHUNK: *value = (int64_t)c->push_chunk; break;
     case GD_OPT_PUSH_THREADS: *value = c->push_threads; break;
     case GD_OPT_INGEST_INDEX: *value = c->ingest_index; break;
     case GD_OPT_COMMIT_CHECK: *value = c->commit_check_device; break;
     case GD_OPT_INGEST_COPY_GRID: *value = c->ing_copy_grid; break;
-    case GD_OPT_INGEST_HYBRID: *value = c->ing_hybrid; break;
     case GD_OPT_INGEST_CU_SPLIT: *value = c->ing_cu_split; break;
     case GD_OPT_INGEST_RANGE_HINT: *value = (int64_t)c->ing_range_hint; break;
-    case GD_OPT_INFLATE_LDS_PAD: *value = c->inflate_pad; break;
-    case GD_OPT_INGEST_BATCHES: *value = c->ing_batches; break;
-    case GD_OPT_INGEST_WALK_CUS: *value = c->ing_walk_cus; break;
     case GD_OPT_INFLATE_KERNEL: *value = c->inflate_kernel; break;
-    case GD_OPT_INGEST_PIECE_STREAMS: *value = c->ing_piece_streams; break;
+    case GD_OPT_INGEST_PIECE_STREAMS: case GD_OPT_INFLATE_LDS_PAD: case GD_OPT_INGEST_HYBRID: case GD_OPT_INGEST_BATCHES:
+    case GD_OPT_INGEST_WALK_CUS: *value = retired_option_default(option); break;
     default: return fail(c, GD_E_INVALID, "unknown option %d", option);
     }
     return GD_OK;

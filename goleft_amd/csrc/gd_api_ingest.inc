@@ -39,7 +39,7 @@ int gd_inflate_bgzf(gd_ctx* c, const uint8_t* data, size_t n_bytes, size_t n_mem
     j.crc = crc ? t_crc : nullptr;
     j.out = d_out; j.status = t_status; j.n = (uint32_t)n_members;
     if (c->profiling) (void)hipEventRecord(c->ev[0], c->stream);
-    gd::inflate_launch(j, c->stream, c->inflate_pad, c->inflate_kernel);
+    gd::inflate_launch(j, c->stream, c->inflate_kernel);
     if (c->profiling) (void)hipEventRecord(c->ev[1], c->stream);
     hipError_t e6 = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
     hipError_t e7 = hipMemcpyAsync(status, t_status, n_members * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
@@ -102,8 +102,6 @@ int gd_ingest_abort(gd_ctx* c)
     (void)ingest_join(c);
     if (c->ing_n == 0) return GD_OK;
     (void)hipSetDevice(c->device);
-    for (hipStream_t s : c->ing_dma)
-        if (s) (void)hipStreamSynchronize(s);
     if (c->ing_hp) (void)hipStreamSynchronize(c->ing_hp);
     (void)hipStreamSynchronize(c->copy_stream);
     (void)hipStreamSynchronize(c->stream);
@@ -148,14 +146,7 @@ int gd_ingest_begin(gd_ctx* c, uint64_t n_bytes, uint64_t base_coffset, size_t n
     // range nor the staging buffers; its error surfaces at the next gd_ingest_feed*)
     const bool reading = c->ing_feeder.joinable();
     if (int r = set_device(c)) return r;
-    const double tb0 = ing_now();
-    struct Tb { gd_ctx* c; double t0; ~Tb() { c->ing_secs[2] += ing_now() - t0; } } tb{c, tb0};
-#ifdef GD_MEASURE
-    double tm_last = tb0;
-#define GD_BEGIN_MARK(what) do { const double t_ = ing_now(); fprintf(stderr, "[begin %p] %-28s %.4f s\n", (void*)g, what, t_ - tm_last); tm_last = t_; } while (0)
-#else
-#define GD_BEGIN_MARK(what)
-#endif
+    struct Tb { gd_ctx* c; double t0; ~Tb() { c->ing_secs[2] += ing_now() - t0; } } tb{c, ing_now()};
     if (n_members > 0xfffffff0ull) return fail(c, GD_E_RANGE, "too many BGZF members");
     // a range that was not fed to its end is an abandoned read: start over.  A completely fed one may
     // wait for its decode while this one is fed.
@@ -176,7 +167,6 @@ int gd_ingest_begin(gd_ctx* c, uint64_t n_bytes, uint64_t base_coffset, size_t n
         if (!b.busy) { g->bufs = &b; break; }
     if (!g->bufs) return bail(GD_E_STATE, "no free range buffers (internal error)");
     g->bufs->busy = true;
-    GD_BEGIN_MARK("state, set claimed");
     if (!IngestBufs::fit_host(&g->bufs->tab, &g->bufs->cap_tab, tab_bytes))
         return bail(GD_E_NOMEM, "cannot page-lock the BGZF member table");
     g->t_in_off = static_cast<uint64_t*>(g->bufs->tab);
@@ -202,7 +192,6 @@ int gd_ingest_begin(gd_ctx* c, uint64_t n_bytes, uint64_t base_coffset, size_t n
         total += isize[m];
     }
     g->total = total;
-    GD_BEGIN_MARK("member table");
     // GD_OPT_INGEST_RANGE_HINT: the caller knows the largest range it is going to feed -- both buffer sets are allocated
     // for THAT on their first use (the inflated size scaled by this range's ratio), so that no later, larger range frees and
     // allocates again (a hipFree waits for the whole device, the other range's kernels included; and on some boxes
@@ -227,18 +216,16 @@ int gd_ingest_begin(gd_ctx* c, uint64_t n_bytes, uint64_t base_coffset, size_t n
         return bail(GD_E_NOMEM, "device allocation for the BAM decode failed");
     g->d_in = static_cast<uint8_t*>(g->bufs->in);
     g->d_out = static_cast<uint8_t*>(g->bufs->out);
-    GD_BEGIN_MARK("device buffers");
-    for (int k = 0; k < 2 * std::max(1, c->ing_piece_streams); ++k)
+    for (int k = 0; k < 2; ++k)
         if ((!c->ing_stage[k] &&
              hipHostMalloc(reinterpret_cast<void**>(&c->ing_stage[k]), IngestState::kStage, hipHostMallocDefault) != hipSuccess) ||
             (!c->ing_staged[k] && hipEventCreateWithFlags(&c->ing_staged[k], hipEventDisableTiming | hipEventBlockingSync) != hipSuccess))
             return bail(GD_E_NOMEM, "cannot allocate the page-locked staging buffers");
-    GD_BEGIN_MARK("staging");
     // GD_OPT_INGEST_CU_SPLIT = n > 0 (with GD_OPT_INGEST_DMA = 0): every n-th CU belongs to the copy kernel that pulls the
     // staged pieces over the link, the others to the inflate launches -- a copy kernel reaches twice a copy engine's rate
     // on an idle device and loses to it only because the inflate workgroups leave it no room
     std::vector<uint32_t> mask_copy, mask_rest;
-    if (c->ing_cu_split > 0 && c->ing_dma_n == 0) {
+    if (c->ing_cu_split > 0 && !c->ing_copy_engine) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount >= 2 * c->ing_cu_split) {
             const int ncu = prop.multiProcessorCount, words = (ncu + 31) / 32;
@@ -255,157 +242,146 @@ int gd_ingest_begin(gd_ctx* c, uint64_t n_bytes, uint64_t base_coffset, size_t n
     if (!mask_copy.empty() && !c->ing_hp &&
         hipExtStreamCreateWithCUMask(&c->ing_hp, (uint32_t)mask_copy.size(), mask_copy.data()) != hipSuccess)
         return bail(GD_E_HIP, "cannot create a CU-masked stream");
-    if (!mask_copy.empty() && c->ing_walk_cus && !c->ing_walk &&
-        hipExtStreamCreateWithCUMask(&c->ing_walk, (uint32_t)mask_copy.size(), mask_copy.data()) != hipSuccess)
-        return bail(GD_E_HIP, "cannot create a CU-masked stream");
-    GD_BEGIN_MARK("streams");
     return GD_OK;
 }
-#undef GD_BEGIN_MARK
 
+// Fills staging buffer k with the next `piece` bytes: from memory (bytes != nullptr; the caller's pointer is not
+// retained), else from `offset` of `fd`.
+static int ingest_fill(gd_ctx* c, int k, const uint8_t* bytes, int fd, uint64_t offset, size_t piece)
+{
+    if (!bytes) {
+        FillPool* pool = ctx_pool(c);
+        const size_t nt = (size_t)std::max(1, c->push_threads);
+        const size_t slice = ((piece / nt) + 4095) & ~(size_t)4095;
+        std::vector<FillPool::Item> items;
+        for (size_t b = 0; b < piece; b += std::max<size_t>(slice, 4096)) {
+            const size_t e = std::min(piece, b + std::max<size_t>(slice, 4096));
+            items.push_back(FillPool::Item{c->ing_stage[k] + b, reinterpret_cast<const void*>((uintptr_t)(offset + b)), e - b,
+                                           (uint32_t)fd, 5, 0});
+        }
+        if (pool) {
+            pool->bad.store(0);
+            pool->spin_limit.store(500, std::memory_order_relaxed);
+            pool->run(std::move(items));
+            pool->spin_limit.store(20000, std::memory_order_relaxed);
+            if (pool->bad.load()) return fail(c, GD_E_INVALID, "the file ended early or could not be read");
+        } else {
+            FillPool one;
+            for (const FillPool::Item& it : items) one.run_item(it);
+            if (one.bad.load()) return fail(c, GD_E_INVALID, "the file ended early or could not be read");
+        }
+    } else if (c->ing_copy_threads > 1 && piece >= (8u << 20)) {
+        const int nt = c->ing_copy_threads;
+        const size_t slice = ((piece / (size_t)nt) + 4095) & ~(size_t)4095;
+        std::vector<std::thread> th;
+        for (int t = 1; t < nt; ++t) {
+            const size_t b = std::min(piece, slice * t), e = std::min(piece, slice * (t + 1));
+            if (e > b) th.emplace_back([=]() { memcpy(c->ing_stage[k] + b, bytes + b, e - b); });
+        }
+        memcpy(c->ing_stage[k], bytes, std::min(piece, slice));
+        for (auto& t : th) t.join();
+    } else {
+        memcpy(c->ing_stage[k], bytes, piece);
+    }
+    return GD_OK;
+}
+
+// Sends staging buffer k's piece behind the bytes the range already holds; ing_staged[k] on the copy stream says it has
+// arrived.  A copy command (the library's default), or with GD_OPT_INGEST_DMA = 0 a copy kernel on ing_hp -- a
+// high-priority stream, or with GD_OPT_INGEST_CU_SPLIT the CU-masked one gd_ingest_begin made (a copy kernel reaches twice
+// a copy engine's rate on an idle device and loses to it only where the inflate workgroups leave it no room).
+static int ingest_send(gd_ctx* c, IngestState* g, int k, size_t piece)
+{
+    if (c->ing_copy_engine) {
+        HIPCHK(c, hipMemcpyAsync(g->d_in + g->fed, c->ing_stage[k], piece, hipMemcpyHostToDevice, c->copy_stream));
+    } else {
+        if (!c->ing_hp) {
+            int lo = 0, hi = 0;
+            (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
+            HIPCHK(c, hipStreamCreateWithPriority(&c->ing_hp, hipStreamNonBlocking, hi));
+        }
+        gd::H2DJob hj{};
+        hj.seg[0] = gd::H2DSeg{g->d_in + g->fed, c->ing_stage[k], piece};
+        hipLaunchKernelGGL(gd::gd_h2d_kernel, dim3(c->ing_copy_grid), dim3(256), 0, c->ing_hp, hj);
+        if (!c->ing_hp_done[k]) HIPCHK(c, hipEventCreateWithFlags(&c->ing_hp_done[k], hipEventDisableTiming));
+        HIPCHK(c, hipEventRecord(c->ing_hp_done[k], c->ing_hp));
+        HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ing_hp_done[k], 0));
+    }
+    HIPCHK(c, hipEventRecord(c->ing_staged[k], c->copy_stream));
+    c->ing_stage_used[k] = true;
+    g->fed += piece;
+    return GD_OK;
+}
+
+// Inflates the members that are now completely on the device, behind the copy: an eighth of the range at a time (or
+// whatever is left once every byte is in).
+static int ingest_inflate_complete(gd_ctx* c, IngestState* g)
+{
+    size_t last = g->next;
+    while (last < g->nm && g->m_end[last] <= g->fed) ++last;
+    const size_t quota = std::max<size_t>((g->nm + 7) / 8, 1);
+    if (last == g->next || (last - g->next < quota && last != g->nm)) return GD_OK;
+    hipStream_t is = c->ing_stream[c->ing_launch_seq++ % 8u];
+    ++g->n_launch;
+    for (int b = 0; b < 2; ++b)                              // (both pieces that may still be in flight)
+        if (c->ing_stage_used[b]) HIPCHK(c, hipStreamWaitEvent(is, c->ing_staged[b], 0));
+    gd::InflateJob ij{};
+    ij.comp = g->d_in;
+    ij.in_off = g->t_in_off + g->next; ij.in_len = g->t_in_len + g->next;
+    ij.out_off = g->t_out_off + g->next; ij.out_len = g->t_out_len + g->next;
+    ij.crc = c->ingest_crc ? g->t_crc + g->next : nullptr; ij.out = g->d_out; ij.status = g->t_status + g->next;
+    ij.n = (uint32_t)(last - g->next);
+    gd::inflate_launch(ij, is, c->inflate_kernel);
+    hipEvent_t done = nullptr;
+    HIPCHK(c, hipEventCreateWithFlags(&done, hipEventDisableTiming | hipEventBlockingSync));   // (waited for by the decoding thread for tens of milliseconds: asleep, not spinning)
+    g->inf_done.push_back(done);
+    HIPCHK(c, hipEventRecord(done, is));
+    g->next = last;
+    return GD_OK;
+}
+
+// The bytes go through the two page-locked staging buffers in turn, a piece of at most IngestState::kStage each.
 // bytes != nullptr: from memory; else n bytes from `offset` of `fd`
 static int ingest_feed(gd_ctx* c, IngestState* g, const uint8_t* bytes, int fd, uint64_t offset, size_t n)
 {
     if (int r = set_device(c)) return r;
     // (the feeder thread keeps its own timers: the caller's thread adds to ing_secs meanwhile)
     double* const secs = tl_ingest_feeder ? c->ing_feeder_secs : c->ing_secs;
-    size_t done = 0;
-    while (done < n) {
+    for (size_t done = 0; done < n;) {
         const size_t piece = std::min(n - done, IngestState::kStage);
-        const int nstreams = std::max(1, c->ing_piece_streams), nbuf = 2 * nstreams;
-        const int k = nstreams > 1 ? (int)(c->ing_piece_seq % (uint64_t)nbuf) : c->ing_cur;
-        // the stream this piece leaves on: with several, whole pieces alternate over them (stream 0 is the copy stream)
-        hipStream_t up = c->copy_stream;
-        if (nstreams > 1) {
-            const int si = (int)(c->ing_piece_seq % (uint64_t)nstreams);
-            if (si > 0) {
-                if (!c->ing_dma[si - 1]) HIPCHK(c, hipStreamCreateWithFlags(&c->ing_dma[si - 1], hipStreamNonBlocking));
-                up = c->ing_dma[si - 1];
-            }
-        }
+        const int k = c->ing_cur;
         const double tw0 = ing_now();
         if (c->ing_stage_used[k]) HIPCHK(c, hipEventSynchronize(c->ing_staged[k]));   // its previous H2D has left the buffer
         const double tw1 = ing_now();
         secs[1] += tw1 - tw0;
-        // the caller's pointer is not retained
-        if (!bytes) {
-            FillPool* pool = ctx_pool(c);
-            const size_t nt = (size_t)std::max(1, c->push_threads);
-            const size_t slice = ((piece / nt) + 4095) & ~(size_t)4095;
-            std::vector<FillPool::Item> items;
-            for (size_t b = 0; b < piece; b += std::max<size_t>(slice, 4096)) {
-                const size_t e = std::min(piece, b + std::max<size_t>(slice, 4096));
-                items.push_back(FillPool::Item{c->ing_stage[k] + b, reinterpret_cast<const void*>((uintptr_t)(offset + done + b)), e - b,
-                                               (uint32_t)fd, 5, 0});
-            }
-            if (pool) {
-                pool->bad.store(0);
-                pool->spin_limit.store(500, std::memory_order_relaxed);
-                pool->run(std::move(items));
-                pool->spin_limit.store(20000, std::memory_order_relaxed);
-                if (pool->bad.load()) return fail(c, GD_E_INVALID, "the file ended early or could not be read");
-            } else {
-                FillPool one;
-                for (const FillPool::Item& it : items) one.run_item(it);
-                if (one.bad.load()) return fail(c, GD_E_INVALID, "the file ended early or could not be read");
-            }
-        } else if (c->ing_copy_threads > 1 && piece >= (8u << 20)) {
-            const int nt = c->ing_copy_threads;
-            const size_t slice = ((piece / (size_t)nt) + 4095) & ~(size_t)4095;
-            std::vector<std::thread> th;
-            for (int t = 1; t < nt; ++t) {
-                const size_t b = std::min(piece, slice * t), e = std::min(piece, slice * (t + 1));
-                if (e > b) th.emplace_back([=]() { memcpy(c->ing_stage[k] + b, bytes + done + b, e - b); });
-            }
-            memcpy(c->ing_stage[k], bytes + done, std::min(piece, slice));
-            for (auto& t : th) t.join();
-        } else {
-            memcpy(c->ing_stage[k], bytes + done, piece);
-        }
+        if (int r = ingest_fill(c, k, bytes ? bytes + done : nullptr, fd, offset + done, piece)) return r;
         secs[0] += ing_now() - tw1;
-        if (nstreams > 1) {
-            if (c->ing_hybrid && up != c->copy_stream) {
-                // every other piece leaves through a copy KERNEL (workgroups reading the page-locked buffer over the link)
-                // while the copy engine moves the pieces between them: two different machines on one link
-                gd::H2DJob hj{};
-                hj.seg[0] = gd::H2DSeg{g->d_in + g->fed, c->ing_stage[k], piece};
-                hipLaunchKernelGGL(gd::gd_h2d_kernel, dim3(c->h2d_grid), dim3(256), 0, up, hj);
-                HIPCHK(c, hipGetLastError());
-            } else {
-                HIPCHK(c, hipMemcpyAsync(g->d_in + g->fed, c->ing_stage[k], piece, hipMemcpyHostToDevice, up));
-            }
-        } else if (c->ing_dma_n == 0) {
-            if (!c->ing_hp) {
-                int lo = 0, hi = 0;
-                (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-                HIPCHK(c, hipStreamCreateWithPriority(&c->ing_hp, hipStreamNonBlocking, hi));
-            }
-            gd::H2DJob hj{};
-            hj.seg[0] = gd::H2DSeg{g->d_in + g->fed, c->ing_stage[k], piece};
-            hipLaunchKernelGGL(gd::gd_h2d_kernel, dim3(c->ing_copy_grid), dim3(256), 0, c->ing_hp, hj);
-            if (!c->ing_dma_ev[k][0]) HIPCHK(c, hipEventCreateWithFlags(&c->ing_dma_ev[k][0], hipEventDisableTiming));
-            HIPCHK(c, hipEventRecord(c->ing_dma_ev[k][0], c->ing_hp));
-            HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ing_dma_ev[k][0], 0));
-        } else {
-            // One DMA engine moves ~25 GB/s, the link twice that: the piece leaves in slices on several streams.  (A
-            // copy kernel -- what gd_commit uses -- loses here: the inflate waves leave it no room.)
-            const int ns = piece >= (8u << 20) ? std::max(1, std::min(c->ing_dma_n, 4)) : 1;
-            const size_t sl = ((piece / (size_t)ns) + 4095) & ~(size_t)4095;
-            for (int s2 = 1; s2 < ns; ++s2) {
-                const size_t b = std::min(piece, sl * s2), e = std::min(piece, sl * (s2 + 1));
-                if (e <= b) continue;
-                if (!c->ing_dma[s2 - 1]) HIPCHK(c, hipStreamCreateWithFlags(&c->ing_dma[s2 - 1], hipStreamNonBlocking));
-                if (!c->ing_dma_ev[k][s2 - 1]) HIPCHK(c, hipEventCreateWithFlags(&c->ing_dma_ev[k][s2 - 1], hipEventDisableTiming));
-                HIPCHK(c, hipMemcpyAsync(g->d_in + g->fed + b, c->ing_stage[k] + b, e - b, hipMemcpyHostToDevice, c->ing_dma[s2 - 1]));
-                HIPCHK(c, hipEventRecord(c->ing_dma_ev[k][s2 - 1], c->ing_dma[s2 - 1]));
-            }
-            HIPCHK(c, hipMemcpyAsync(g->d_in + g->fed, c->ing_stage[k], std::min(piece, sl), hipMemcpyHostToDevice, c->copy_stream));
-            for (int s2 = 1; s2 < ns; ++s2)
-                if (c->ing_dma_ev[k][s2 - 1] && std::min(piece, sl * s2) < piece)
-                    HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ing_dma_ev[k][s2 - 1], 0));
-        }
-        HIPCHK(c, hipEventRecord(c->ing_staged[k], up));                       // every slice of the piece has arrived
-        c->ing_stage_used[k] = true;
+        if (int r = ingest_send(c, g, k, piece)) return r;
         c->ing_cur ^= 1;
-        ++c->ing_piece_seq;
-        g->fed += piece;
         done += piece;
-        // inflate the members that are now completely on the device, behind the copy: an eighth of
-        // the range at a time (or whatever is left once every byte is in)
-        size_t last = g->next;
-        while (last < g->nm && g->m_end[last] <= g->fed) ++last;
-        const size_t quota = std::max<size_t>((g->nm + (size_t)c->ing_batches - 1) / (size_t)c->ing_batches, 1);
-        if (last > g->next && (last - g->next >= quota || last == g->nm) ) {
-            hipStream_t is = c->ing_stream[c->ing_launch_seq++ % 8u];
-            ++g->n_launch;
-            // (pieces on different streams may land out of order: every piece still in flight must have arrived)
-            for (int b = 0; b < nbuf; ++b)
-                if (c->ing_stage_used[b]) HIPCHK(c, hipStreamWaitEvent(is, c->ing_staged[b], 0));
-            gd::InflateJob ij{};
-            ij.comp = g->d_in;
-            ij.in_off = g->t_in_off + g->next; ij.in_len = g->t_in_len + g->next;
-            ij.out_off = g->t_out_off + g->next; ij.out_len = g->t_out_len + g->next;
-            ij.crc = c->ingest_crc ? g->t_crc + g->next : nullptr; ij.out = g->d_out; ij.status = g->t_status + g->next;
-            ij.n = (uint32_t)(last - g->next);
-            gd::inflate_launch(ij, is, c->inflate_pad, c->inflate_kernel);
-            hipEvent_t done = nullptr;
-            HIPCHK(c, hipEventCreateWithFlags(&done, hipEventDisableTiming | hipEventBlockingSync));   // (waited for by the decoding thread for tens of milliseconds: asleep, not spinning)
-            g->inf_done.push_back(done);
-            HIPCHK(c, hipEventRecord(done, is));
-            g->next = last;
-        }
+        if (int r = ingest_inflate_complete(c, g)) return r;
     }
+    return GD_OK;
+}
+
+// What gd_ingest_feed and gd_ingest_feed_fd begin with: the read in progress has ended, and the newest range has room
+// for n more bytes.
+static int ingest_feed_target(gd_ctx* c, size_t n, IngestState** out)
+{
+    if (int r = ingest_join(c)) { (void)gd_ingest_abort(c); return r; }
+    if (c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
+    IngestState* g = c->ing_n ? c->ing_q[c->ing_n - 1] : nullptr;
+    if (!g) return fail(c, GD_E_STATE, "gd_ingest_begin has not been called");
+    if (g->fed + n > g->n_bytes) return fail(c, GD_E_RANGE, "more bytes fed than announced");
+    *out = g;
     return GD_OK;
 }
 
 int gd_ingest_feed(gd_ctx* c, const uint8_t* bytes, size_t n)
 {
     if (!c || (n && !bytes)) return GD_E_INVALID;
-    if (int r = ingest_join(c)) { (void)gd_ingest_abort(c); return r; }
-    if (c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
-    IngestState* g = c->ing_n ? c->ing_q[c->ing_n - 1] : nullptr;
-    if (!g) return fail(c, GD_E_STATE, "gd_ingest_begin has not been called");
-    if (g->fed + n > g->n_bytes) return fail(c, GD_E_RANGE, "more bytes fed than announced");
+    IngestState* g = nullptr;
+    if (int r = ingest_feed_target(c, n, &g)) return r;
     return ingest_feed(c, g, bytes, -1, 0, n);
 }
 
@@ -414,11 +390,8 @@ int gd_ingest_feed(gd_ctx* c, const uint8_t* bytes, size_t n)
 int gd_ingest_feed_fd(gd_ctx* c, int fd, uint64_t offset, size_t n)
 {
     if (!c || fd < 0) return GD_E_INVALID;
-    if (int r = ingest_join(c)) { (void)gd_ingest_abort(c); return r; }
-    if (c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
-    IngestState* g = c->ing_n ? c->ing_q[c->ing_n - 1] : nullptr;
-    if (!g) return fail(c, GD_E_STATE, "gd_ingest_begin has not been called");
-    if (g->fed + n > g->n_bytes) return fail(c, GD_E_RANGE, "more bytes fed than announced");
+    IngestState* g = nullptr;
+    if (int r = ingest_feed_target(c, n, &g)) return r;
     c->ing_feeder_rc = GD_OK;
     c->ing_feeder = std::thread([c, g, fd, offset, n]() { tl_ingest_feeder = true; c->ing_feeder_rc = ingest_feed(c, g, nullptr, fd, offset, n); });
     return GD_OK;
@@ -554,17 +527,9 @@ static int ingest_decode(gd_ctx* c, int32_t tid, int32_t ref_id, const uint64_t*
         }
     }
     const unsigned seg_grid = (unsigned)n_anchors;         // one wave per anchor segment
-    // GD_OPT_INGEST_WALK_CUS: the walks on the copy kernel's CUs (their LDS is free; beside four inflate workgroups a CU
-    // has room for ONE walk workgroup) -- a stream of their own, ordered with the compute stream by events
-    hipStream_t ws = c->ing_walk ? c->ing_walk : c->stream;
-    if (ws != c->stream) {
-        if (!c->ing_walk_ev) HIPCHK(c, hipEventCreateWithFlags(&c->ing_walk_ev, hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(c->ing_walk_ev, c->stream));       // (what the compute stream still does to the contig's arrays)
-        HIPCHK(c, hipStreamWaitEvent(ws, c->ing_walk_ev, 0));
-    }
-    hipLaunchKernelGGL(gd::gd_bam_walk_kernel<false>, dim3(seg_grid), dim3(64), 0, ws, bj);
+    hipLaunchKernelGGL(gd::gd_bam_walk_kernel<false>, dim3(seg_grid), dim3(64), 0, c->stream, bj);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(ws));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     const double td2 = ing_now();
     c->ing_secs[4] += td2 - td1;
     if (append && c->contigs[tid].adopted) return fail(c, GD_E_STATE, "contig %d holds adopted device records", tid);
@@ -620,17 +585,9 @@ static int ingest_decode(gd_ctx* c, int32_t tid, int32_t ref_id, const uint64_t*
         c->ing_secs[5] += ing_now() - td2;
         bj.rec_base = s_rbase; bj.op_base = s_obase;
         bj.pos = h.pos; bj.flag = h.flag; bj.mapq = h.mapq; bj.cigar_off = h.off; bj.cigar = h.cigar;
-        if (ws != c->stream) {                              // (reserve_records / free_contig above ran on the compute stream)
-            HIPCHK(c, hipEventRecord(c->ing_walk_ev, c->stream));
-            HIPCHK(c, hipStreamWaitEvent(ws, c->ing_walk_ev, 0));
-        }
-        if (bj.tab) hipLaunchKernelGGL(gd::gd_bam_extract_tab_kernel, dim3(seg_grid), dim3(256), 0, ws, bj);
-        else hipLaunchKernelGGL(gd::gd_bam_walk_kernel<true>, dim3(seg_grid), dim3(64), 0, ws, bj);
+        if (bj.tab) hipLaunchKernelGGL(gd::gd_bam_extract_tab_kernel, dim3(seg_grid), dim3(256), 0, c->stream, bj);
+        else hipLaunchKernelGGL(gd::gd_bam_walk_kernel<true>, dim3(seg_grid), dim3(64), 0, c->stream, bj);
         HIPCHK(c, hipGetLastError());
-        if (ws != c->stream) {
-            HIPCHK(c, hipEventRecord(c->ing_walk_ev, ws));
-            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ing_walk_ev, 0));
-        }
         HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h.off + N0 + N), (int)(uint32_t)(M0 + M), 1, c->stream));   // (a fill kernel, not a copy command)
         // position index + spans of what the walk just wrote (its order and offsets were checked by the walk itself)
         const int32_t before = h.last_pos;
@@ -727,19 +684,3 @@ int gd_ingest_bgzf(gd_ctx* c, int32_t tid, int32_t ref_id, const uint8_t* data, 
     if (int r = gd_ingest_feed(c, data, n_bytes)) { (void)gd_ingest_abort(c); return r; }
     return gd_ingest_finish(c, tid, ref_id, anchors, n_anchors, n_records);
 }
-
-#ifdef GD_MEASURE
-// MEASUREMENT BUILDS ONLY (see gd_inflate.hpp): the section cycles of every gd_inflate_kernel wave since the last call.
-extern "C" int gd_debug_inflate_sections(unsigned long long* out16)
-{
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_inflate_sections), 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    unsigned long long zero[16] = {0};
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_inflate_sections), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
-}
-extern "C" int gd_debug_inflate_b2(unsigned long long* out8)
-{
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(gd::g_inflate_b2), 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    unsigned long long zero[8] = {0};
-    return hipMemcpyToSymbol(HIP_SYMBOL(gd::g_inflate_b2), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
-}
-#endif

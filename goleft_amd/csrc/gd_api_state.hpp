@@ -229,26 +229,18 @@ struct gd_ctx {
     int ing_feeder_rc = 0;
     std::string ing_feeder_err;                         // what the feeder thread's failure said (published by ingest_join)
     double ing_feeder_secs[2] = {0, 0};                 // its share of gd_ingest_timing [0], [1] (merged by ingest_join)
-    bool ing_stage_used[8] = {false, false, false, false, false, false, false, false};
-    int ing_cur = 0;
+    bool ing_stage_used[2] = {false, false};
+    int ing_cur = 0;                                   // the staging buffer the next piece goes through
     IngestBufs ing_bufs[kIngestDepth];
     // staging of the device BAM read, created by the first gd_ingest_begin and kept until gd_destroy
     // (page-locking 128 MB per contig would cost more than many contigs' whole decode)
-    uint8_t* ing_stage[8] = {};                        // page-locked staging buffers: two per upload stream
-    hipEvent_t ing_staged[8] = {};
-    int ing_piece_streams = 1;                         // GD_OPT_INGEST_PIECE_STREAMS: whole pieces alternate over this many streams (copy engines)
-    uint64_t ing_piece_seq = 0;
+    uint8_t* ing_stage[2] = {};                        // page-locked staging buffers: one is filled while the other's piece leaves
+    hipEvent_t ing_staged[2] = {};                     // ... recorded on the copy stream: the buffer's piece has arrived
     int ing_cu_split = 0;                              // GD_OPT_INGEST_CU_SPLIT: every n-th CU for the copy kernel, the rest for the inflate launches
-    bool ing_hybrid = false;                           // GD_OPT_INGEST_HYBRID: with two piece streams, the second one's pieces leave through a copy kernel
-    hipStream_t ing_dma[3] = {nullptr, nullptr, nullptr};   // GD_OPT_INGEST_DMA > 1: a staged piece leaves in slices on several streams (DMA engines)
-    hipEvent_t ing_dma_ev[8][3] = {};
-    int ing_dma_n = 1;
-    hipStream_t ing_walk = nullptr;                     // GD_OPT_INGEST_WALK_CUS: the record walks' stream, masked to the copy kernel's CUs
-    int ing_walk_cus = 0;
-    hipEvent_t ing_walk_ev = nullptr;
-    int ing_batches = 8;                                // GD_OPT_INGEST_BATCHES
+    bool ing_copy_engine = true;                       // GD_OPT_INGEST_DMA: a staged piece leaves with a copy command (1) or with a copy kernel on ing_hp (0)
     unsigned ing_copy_grid = 16;                        // GD_OPT_INGEST_COPY_GRID: workgroups of the copy kernel that pulls a staged piece over the link
-    hipStream_t ing_hp = nullptr;                       // GD_OPT_INGEST_DMA 0: the piece leaves with a copy kernel on a high-priority stream
+    hipStream_t ing_hp = nullptr;                       // GD_OPT_INGEST_DMA 0: the copy kernel's stream, high priority or (GD_OPT_INGEST_CU_SPLIT) CU-masked
+    hipEvent_t ing_hp_done[2] = {};                     // ... the copy stream waits for these before it records ing_staged[k]
     hipStream_t ing_stream[8] = {};                     // inflate launches rotate over these (two pending ranges x 4)
     unsigned ing_launch_seq = 0;
     int ing_copy_threads = 1;                          // GD_OPT_COPY_THREADS: threads filling the staging buffer
@@ -257,7 +249,6 @@ struct gd_ctx {
     bool ingest_crc = true;                            // GD_OPT_INGEST_CRC
     uint64_t ing_range_hint = 0;                       // GD_OPT_INGEST_RANGE_HINT: bytes of the largest range the caller will feed
     int inflate_kernel = 0;                            // GD_OPT_INFLATE_KERNEL
-    unsigned inflate_pad = 0;                          // GD_OPT_INFLATE_LDS_PAD: extra LDS per inflate workgroup (occupancy limiter)
     int32_t bam_n_ref = 0;                             // GD_OPT_BAM_REFS: references of the BAM being read (0: unknown)
     int push_threads = 16;
     FillPool* pool = nullptr; int pool_workers = 0;    // host worker threads (gd_push fills, gd_commit validates), created on first use

@@ -49,8 +49,8 @@
 // 82.8 -> 54.3 ms for those 108 k members, WRITE_SIZE 66 -> 8.1 GB (1.15 x the output), FETCH_SIZE 126 -> 92 GB
 // (profiles/r10u_…, r10v_…, r10w_inflate_output_ring.txt).
 //
-// Round 5: what bounds it (profiles/r12j_..., r12k_..., r12l_..., r12m_...).  The section counters of the measurement build
-// (-DGD_MEASURE) put an iteration at ~4 400 cycles, 0.4 % of them waiting for the two loads: a wave issues one
+// Round 5: what bounds it (profiles/r12j_..., r12k_..., r12l_..., r12m_...).  The section counters of a measurement build
+// (HISTORY.md) put an iteration at ~4 400 cycles, 0.4 % of them waiting for the two loads: a wave issues one
 // instruction per four cycles whatever its kind, and the ~750 instructions of an iteration (450 vector, 250 scalar, 50 LDS /
 // memory) plus the dependent LDS look-ups of three Huffman decodes are those cycles -- at ONE wave per SIMD, because 608 bytes
 // of LDS per member allow four waves per CU.  A kernel that split a member's work over two waves with the same LDS (a decoder
@@ -70,15 +70,6 @@
 #define GD_INFLATE_PROBE(what, value)
 #endif
 
-// MEASUREMENT BUILDS ONLY (-DGD_MEASURE; tools/r12_inflate_sections.sh): the cycles a wave spends in each section of
-// the symbol loop, summed over all waves into g_inflate_sections (read back through gd_debug_inflate_sections).  The
-// product is compiled without it.
-#ifdef GD_MEASURE
-__device__ unsigned long long g_inflate_sections[16];
-#define GD_INF_T(k) do { const uint64_t t_ = __builtin_readcyclecounter(); tsum[k] += t_ - tlast; tlast = t_; } while (0)
-#else
-#define GD_INF_T(k)
-#endif
 
 namespace gd {
 
@@ -324,9 +315,6 @@ __global__ __launch_bounds__(INF_LANES) void gd_inflate_kernel(InflateJob job)
     uint8_t* const out_al = out - obase;                   // 64-byte aligned: block [fl, fl + 64) lives at out_al + fl
     uint32_t fl = 0;
     uint32_t E0 = 0;                                       // the four bytes before T: bytes [o - 20, o - 16)
-#ifdef GD_MEASURE
-    uint64_t tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter(), titer = 0;
-#endif
     auto ring_byte = [&](uint32_t a) -> uint32_t { return (s_ring[((a >> 2) & 31u) * 64u] >> (8u * (a & 3u))) & 0xffu; };
     // the bytes [lo, hi) of the ring to memory, one by one (a member's first block when the member starts inside it, its
     // last bytes, what is pending when a stored block starts)
@@ -469,7 +457,6 @@ __global__ __launch_bounds__(INF_LANES) void gd_inflate_kernel(InflateJob job)
                 want_in = false;                           // (16 bytes asked for before the header belong behind the OLD window)
             }
         }
-        GD_INF_T(0);
 
         // ---- (1) what the loads issued at (0) do not cover: a chunk whose source lies in the ring, the window's dwords ----
         GD_INFLATE_PROBE(2, from_mem ? 1u : (cload ? 2u : 0u));
@@ -512,13 +499,11 @@ __global__ __launch_bounds__(INF_LANES) void gd_inflate_kernel(InflateJob job)
         const uint32_t e2 = ds < 4u ? 0u : (ds >> 1) - 1u;
         const uint32_t mdist = ds < 4u ? 1u + ds : 1u + ((2u + (ds & 1u)) << e2) + ((lo2 >> l2) & ((1u << e2) - 1u));
         const uint32_t used2 = used1 + l2 + e2;            // <= 48
-        GD_INF_T(1);
         // Both loads are waited for HERE, by every lane: their uses below sit in branches (a lane without a chunk to append,
         // without a slot to fill, skips them), and a load the compiler cannot prove finished on every path costs a
         // `s_waitcnt vmcnt(0)` at the top of the next iteration -- in front of that iteration's loads, behind the block
         // stores of this one.  (gfx9 encoding: vmcnt 0, expcnt and lgkmcnt untouched.)
         __builtin_amdgcn_s_waitcnt(0x0F70);
-        GD_INF_T(2);
 
         // ---- (3) the chunk loaded (or built) in the previous iteration goes into T ----
         const bool cp = cpend;
@@ -573,7 +558,6 @@ __global__ __launch_bounds__(INF_LANES) void gd_inflate_kernel(InflateJob job)
             }
             if (mode == DONE) p = in_beg;
         }
-        GD_INF_T(3);
         // ---- (6) refill from the word loaded at the top (before the store: nothing else is in flight then) ----
         if (want_in) { win_put(win_hi, in16); win_hi += 16u; }   // (the slot's first byte is >= 32 bytes ahead: nobody reads it yet)
         if (mode != DONE) {
@@ -585,7 +569,6 @@ __global__ __launch_bounds__(INF_LANES) void gd_inflate_kernel(InflateJob job)
             if (p > in_end + 16) { err = 1; mode = DONE; p = in_beg; }   // ran off the member's input
         }
 
-        GD_INF_T(4);
         // what this iteration produced goes into the ring: the 20 bytes [o - 20, o) (E0, T) as five aligned dwords from the
         // dword that holds byte o - 20 on -- up to three bytes more than T needs on either side: in front bytes that are
         // there already, behind bytes that the next write replaces before anything reads them
@@ -617,7 +600,6 @@ __global__ __launch_bounds__(INF_LANES) void gd_inflate_kernel(InflateJob job)
             }
         }
         if (flush) pend = 0;
-        GD_INF_T(5);
 
         // ---- (5) a match in progress: its next chunk, loaded (next iteration) after the store above ----
         csmall = false;
@@ -645,17 +627,7 @@ __global__ __launch_bounds__(INF_LANES) void gd_inflate_kernel(InflateJob job)
             cpend = true;
             if (rem == 0u) mode = DECODE;
         }
-        GD_INF_T(6);
-#ifdef GD_MEASURE
-        ++titer;
-#endif
     }
-#ifdef GD_MEASURE
-    if (lane == 0) {
-        for (int k = 0; k < 7; ++k) atomicAdd(&::g_inflate_sections[k], (unsigned long long)tsum[k]);
-        atomicAdd(&::g_inflate_sections[7], (unsigned long long)titer);
-    }
-#endif
     // the member's last bytes: what never completed a 64-byte block
     if (mine && err == 0u) ring_bytes_out(fl > obase ? fl : obase, obase + olen);
     if (mine) job.status[m] = err;
@@ -834,8 +806,7 @@ constexpr int INF_WAVE_NW = GD_INF_WAVE_NW;                             // waves
 // that one left (WV_FALLBACK), the CRC check.
 // kernel (GD_OPT_INFLATE_KERNEL): 0 -- the lane-per-member kernel alone, the default; 1 -- the workgroup-per-member kernel first
 // (round 6: a sixth of the memory traffic, but slower on an MI355X -- DESIGN.md 3.5), the lane-per-member kernel for what it left.
-// lds_pad: bytes of LDS a lane-per-member workgroup claims on top of its own 38 KB -- an occupancy limiter for measurements.
-inline void inflate_launch(const InflateJob& job_in, hipStream_t stream, unsigned lds_pad = 0, int kernel = 0)
+inline void inflate_launch(const InflateJob& job_in, hipStream_t stream, int kernel = 0)
 {
     InflateJob job = job_in;
     if (job.n == 0) return;
@@ -845,7 +816,7 @@ inline void inflate_launch(const InflateJob& job_in, hipStream_t stream, unsigne
     } else {
         job.only_status = 0;
     }
-    hipLaunchKernelGGL(gd_inflate_kernel, dim3((job.n + INF_LANES - 1) / INF_LANES), dim3(INF_LANES), lds_pad, stream, job);
+    hipLaunchKernelGGL(gd_inflate_kernel, dim3((job.n + INF_LANES - 1) / INF_LANES), dim3(INF_LANES), 0, stream, job);
     if (job.crc && INF_CRC_WAVE) {
         const unsigned groups = (job.n + 3u) / 4u;
         hipLaunchKernelGGL(gd_inflate_crc_wave_kernel, dim3(groups < 8192u ? groups : 8192u), dim3(256), 0, stream, job);

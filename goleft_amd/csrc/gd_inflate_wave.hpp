@@ -327,19 +327,6 @@ __device__ __forceinline__ WvRun wv_run(const uint8_t* in, uint32_t start, uint3
     return r;
 }
 
-// MEASUREMENT BUILDS ONLY (-DGD_MEASURE): the cycles a workgroup spends in each phase, summed into g_inflate_sections[8..15]
-#ifdef GD_MEASURE
-#define WV_T(k) do { const uint64_t t_ = __builtin_readcyclecounter(); wsum[k] += t_ - wlast; wlast = t_; } while (0)
-// ... and inside pass B2 (g_inflate_b2): cycles of the bitmap expansion, of a batch's set-up, of its rounds; windows, batches, rounds
-__device__ unsigned long long g_inflate_b2[8];
-#define WV_B(k) do { const uint64_t t_ = __builtin_readcyclecounter(); bsum[k] += t_ - blast; blast = t_; } while (0)
-#define WV_BN(k) (++bsum[k])
-#else
-#define WV_T(k)
-#define WV_B(k)
-#define WV_BN(k)
-#endif
-
 template <int NW>
 __global__ __launch_bounds__(64 * NW, (NW + 1) / 2) void gd_inflate_wave_kernel(InflateJob job)
 {
@@ -372,10 +359,6 @@ __global__ __launch_bounds__(64 * NW, (NW + 1) / 2) void gd_inflate_wave_kernel(
         }
         reinterpret_cast<uint32_t*>(X + WX_PERM)[i] = w;
     }
-#ifdef GD_MEASURE
-    uint64_t wsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, wlast = __builtin_readcyclecounter();
-    uint64_t bsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, blast = 0;
-#endif
     uint32_t bitpos = 0, opos = 0;
     bool fallback = olen > 65536u || ilen > (1u << 20);
     bool done = false;
@@ -528,7 +511,6 @@ __global__ __launch_bounds__(64 * NW, (NW + 1) / 2) void gd_inflate_wave_kernel(
             }
         }
         __syncthreads();
-        WV_T(0);
         const uint32_t type = misc[WM_TYPE], fin = misc[WM_FINAL], nlen = misc[WM_NLEN];
         bitpos = misc[WM_HDREND];
         if (misc[WM_ERR] != 0u || bitpos > endbits) { fallback = true; break; }
@@ -664,7 +646,6 @@ __global__ __launch_bounds__(64 * NW, (NW + 1) / 2) void gd_inflate_wave_kernel(
         }
         (void)nlen;
         __syncthreads();
-        WV_T(1);
 
         // ================= pass A: where every lane's subsequence really starts, and what it produces =================
         const uint32_t body = bitpos;
@@ -709,7 +690,6 @@ __global__ __launch_bounds__(64 * NW, (NW + 1) / 2) void gd_inflate_wave_kernel(
             __syncthreads();
         }
         if (fallback) break;
-        WV_T(2);
         // ================= the lanes' output offsets: an exclusive scan =================
         // a lane counts when every lane in front of it crossed into its successor; value: bytes | (blocks what follows) << 31
         {
@@ -743,14 +723,12 @@ __global__ __launch_bounds__(64 * NW, (NW + 1) / 2) void gd_inflate_wave_kernel(
             // ================= pass B1: literals to their place, matches as pieces =================
             for (int i = tid; i < 2048 / 4; i += NL) reinterpret_cast<inf_v4*>(X + WX_BITMAP)[i] = inf_v4{0, 0, 0, 0};
             __syncthreads();
-            WV_T(3);
             uint32_t fail = 0;
             const bool go = valid && (st == WS_CROSSED || st == WS_EOB);
             const WvRun r = wv_run<true>(in, mystart, bound, endbits, go, sm, XO, opos + excl, fail);
             if (fail || (go && (r.cnt != (mine & 0xffffffu) || r.state != st))) misc[WM_FAIL] = 1u;
             __syncthreads();
             if (misc[WM_FAIL]) { fallback = true; break; }
-            WV_T(4);
             // ================= pass B2: the pieces in output order =================
             // (the lanes' arrays are free until the next block's pass A: they hold the piece starts of the window being resolved)
             if (wave == 0) {
@@ -758,11 +736,7 @@ __global__ __launch_bounds__(64 * NW, (NW + 1) / 2) void gd_inflate_wave_kernel(
                 uint16_t* const stage = reinterpret_cast<uint16_t*>(sm + WV_LANE);   // [704]: pieces are >= 3 bytes, a window is 2 KB
                 const uint32_t w_lo = opos >> 5, w_hi = (opos + total + 31u) >> 5;
                 uint32_t carry_end = 0;                    // end of the last piece of the batch before
-#ifdef GD_MEASURE
-                blast = __builtin_readcyclecounter();
-#endif
                 for (uint32_t w0 = w_lo; w0 < w_hi; w0 += 64u) {
-                    WV_BN(3);
                     uint32_t word = w0 + (uint32_t)lane < w_hi ? bitmap[w0 + (uint32_t)lane] : 0u;
                     const uint32_t c = (uint32_t)__popc(word);
                     const uint32_t incl2 = wv_wave_incl_scan(c, lane);
@@ -776,9 +750,7 @@ __global__ __launch_bounds__(64 * NW, (NW + 1) / 2) void gd_inflate_wave_kernel(
                         }
                     }
                     WV_WAVE_SYNC();
-                    WV_B(0);
                     for (uint32_t s0 = 0; s0 < npc; s0 += 64u) {
-                        WV_BN(4);
                         const bool act = s0 + (uint32_t)lane < npc;
                         const uint32_t dst = act ? stage[s0 + (uint32_t)lane] : 0xfffffu;
                         const uint32_t tok = act ? wv_load4(out + dst) & 0xffffffu : 0u;
@@ -816,9 +788,7 @@ __global__ __launch_bounds__(64 * NW, (NW + 1) / 2) void gd_inflate_wave_kernel(
                         uint8_t* const a2 = a4 + (n & 4u);
                         uint8_t* const a1 = a2 + (n & 2u);
                         uint64_t U = __ballot(act);
-                        WV_B(1);
                         while (U) {
-                            WV_BN(5);
                             const uint32_t first = (uint32_t)__builtin_ctzll(U);
                             const uint32_t F = WV_READLANE(dst, first);
                             const uint64_t R = (__ballot(s_hi <= F) | MG | (1ull << first)) & U;
@@ -848,13 +818,11 @@ __global__ __launch_bounds__(64 * NW, (NW + 1) / 2) void gd_inflate_wave_kernel(
                             U &= ~R;
                             WV_WAVE_SYNC();
                         }
-                        WV_B(2);
                         carry_end = WV_READLANE(endv, (npc - s0 < 64u ? npc - s0 : 64u) - 1u);
                     }
                 }
             }
             __syncthreads();
-            WV_T(5);
             opos += total;
             bitpos = misc[WM_ENDPOS];
             if (fin) done = true;
@@ -877,14 +845,6 @@ __global__ __launch_bounds__(64 * NW, (NW + 1) / 2) void gd_inflate_wave_kernel(
         if (tail0 + (uint32_t)tid < olen && tid < 16) g[tail0 + tid] = out[tail0 + tid];
     }
     if (tid == 0) job.status[m] = fallback ? WV_FALLBACK : 0u;
-#ifdef GD_MEASURE
-    WV_T(6);
-    if (tid == 0) {
-        for (int k = 0; k < 7; ++k) atomicAdd(&::g_inflate_sections[8 + k], (unsigned long long)wsum[k]);
-        atomicAdd(&::g_inflate_sections[15], 1ull);
-        for (int k = 0; k < 6; ++k) atomicAdd(&gd::g_inflate_b2[k], (unsigned long long)bsum[k]);
-    }
-#endif
 }
 
 }  // namespace gd

@@ -200,7 +200,7 @@ enum { GD_OPT_NT_STORES = 3,        /* 1 (default): non-temporal per-base stores
                                        does; 0: the file is trusted (a second pass over the inflated bytes is saved) */
        GD_OPT_INGEST_DMA = 13,      /* gd_ingest_feed*: how a staged piece crosses the link: 1 (default) a copy command on one stream;
                                        0: a copy kernel on a high-priority stream (what the CLI uses, with GD_OPT_INGEST_CU_SPLIT).
-                                       (2 .. 4, slices of a piece on several streams, measured slower: measurement builds only) */
+                                       (2 .. 4 were slices of a piece on several streams, measured slower and retired: GD_E_INVALID) */
        GD_OPT_INGEST_INDEX = 14,    /* 1 (default): records are indexed as they arrive -- gd_adopt_device's check pass, a pass over
                                        every committed block once it has landed, the device BAM read's write pass: a position
                                        index (first read at or past every 64th position: the prep kernel looks its tiles' read
@@ -234,15 +234,15 @@ enum { GD_OPT_NT_STORES = 3,        /* 1 (default): non-temporal per-base stores
                                        needs a gd_reset then).  For producers that are short of CPU -- a decoder's threads --
                                        and do not need the verdict block by block; gdh_produce_in_place runs this way */
 
-       /* ---- MEASUREMENT BUILDS ONLY (the library compiled with -DGD_MEASURE) ----
-        * Each of these was built, measured neutral or worse on an MI355X and left at its default (HISTORY.md has the numbers).
-        * A release library accepts the default value and answers GD_E_INVALID to any other; it also contains none of the
-        * timing code of such builds (section cycle counters in the inflate kernels, marks in gd_ingest_begin). */
-       GD_OPT_INGEST_PIECE_STREAMS = 15, /* whole staged pieces alternate over this many streams: 1 (default) .. 4 */
-       GD_OPT_INFLATE_LDS_PAD = 16,   /* bytes of LDS a lane-per-member inflate workgroup claims on top of its own (an occupancy limiter): 0 */
-       GD_OPT_INGEST_HYBRID = 17,     /* with several piece streams: the pieces of every stream but the first leave through a copy kernel: 0 */
-       GD_OPT_INGEST_BATCHES = 21,    /* inflate launches per fed range: 8 */
-       GD_OPT_INGEST_WALK_CUS = 22 }; /* with GD_OPT_INGEST_CU_SPLIT: the record walks on the copy kernel's CUs: 0 */
+       /* ---- RETIRED ----
+        * Switches of link and occupancy experiments that were measured neutral or worse on an MI355X; their code is gone
+        * (HISTORY.md has what each one was, and the numbers).  The number stays reserved: gd_set_option accepts the default
+        * given here and answers GD_E_INVALID to any other value, gd_get_option returns the default. */
+       GD_OPT_INGEST_PIECE_STREAMS = 15, /* 1 */
+       GD_OPT_INFLATE_LDS_PAD = 16,   /* 0 */
+       GD_OPT_INGEST_HYBRID = 17,     /* 0 */
+       GD_OPT_INGEST_BATCHES = 21,    /* 8 */
+       GD_OPT_INGEST_WALK_CUS = 22 }; /* 0 */
 int gd_set_option(gd_ctx* ctx, int option, int64_t value);
 /* The value an option has now (a library that scopes a setting puts it back afterwards). */
 int gd_get_option(gd_ctx* ctx, int option, int64_t* value);

@@ -566,10 +566,10 @@ def test_inflate_a_member_of_fifty_thousand_empty_blocks(kernel):
     assert got == payload + b"ACGT" * 1000
 
 
-def test_measurement_switches_are_refused_by_a_release_library():
-    """include/goleft_depth.h lists the switches of measurement builds (-DGD_MEASURE) apart: the library that ships keeps them at
-    their defaults, accepts the default and answers GD_E_INVALID to anything else (a cgo host could set a
-    switch that was only ever meant for a measurement)."""
+def test_retired_switches_accept_only_their_defaults():
+    """include/goleft_depth.h lists the retired switches apart (link and occupancy experiments whose code is gone): the
+    library keeps their numbers, accepts the default and answers GD_E_INVALID to anything else (a cgo
+    host could set a switch that was only ever meant for a measurement)."""
     from goleft_amd.engine import DepthEngine, GdError
     with DepthEngine(0) as eng:
         for opt, v in ((15, 2), (16, 4096), (17, 1), (21, 4), (22, 1), (13, 3)):
@@ -578,3 +578,86 @@ def test_measurement_switches_are_refused_by_a_release_library():
             assert ei.value.status == -1, (opt, v, ei.value.status)
         for opt, v in ((15, 1), (16, 0), (17, 0), (21, 8), (22, 0), (13, 0), (13, 1)):
             eng.set_option(opt, v)
+
+
+def _bgzf_member_ends(data: bytes):
+    """File offsets at which the BGZF members of `data` end (bamio writes BC as the only extra subfield)."""
+    ends, off = [], 0
+    while off < len(data):
+        off += struct.unpack_from("<H", data, off + 16)[0] + 1
+        ends.append(off)
+    return ends
+
+
+@pytest.fixture(scope="module")
+def feed_routes_bam(tmp_path_factory):
+    """One contig of 700 kb with random short reads and a second small one, as test_ingest_many_anchors_and_long_cigars
+    writes it; checked on the CPU to hold at least 17 BGZF members -- an eighth of the range is then three members or
+    more, several inflate launches start while the file is still being fed, and the last one takes a remainder."""
+    rng = np.random.default_rng(57)
+    lens = [700_000, 20_000]
+    contigs = [("c1", lens[0]), ("c2", lens[1])]
+    reads = {0: H.random_reads(rng, lens[0], 60_000, max_len=120), 1: H.random_reads(rng, lens[1], 1_500, max_len=120)}
+    p = str(tmp_path_factory.mktemp("feed_routes") / "r.bam")
+    bamio.write_bam(p, contigs, reads, unplaced=3, index=True)
+    data = open(p, "rb").read()
+    ends = _bgzf_member_ends(data)
+    assert len(ends) >= 17 and ends[-1] == len(data), len(ends)
+    want = {t: po.perbase_c(reads[t], 1, 0, lens[t]) for t in reads}
+    return lens, reads, data, ends, bamio.read_bai_linear(p + ".bai"), want
+
+
+OPT_INGEST_DMA, OPT_INGEST_CU_SPLIT = 13, 19
+# how a staged piece leaves: a copy command (the library's default); a copy kernel on a high-priority stream; that kernel on
+# every 8th CU with the inflate streams masked to the others (what the CLI sets)
+FEED_ROUTES = {"copy-command": (1, 0), "copy-kernel": (0, 0), "copy-kernel-cu-split": (0, 8)}
+
+
+def _feed_route_engine(eng, route, lens):
+    dma, split = FEED_ROUTES[route]
+    eng.set_option(OPT_INGEST_DMA, dma)
+    eng.set_option(OPT_INGEST_CU_SPLIT, split)               # (before the first gd_ingest_begin: hence an engine per case)
+    eng.set_params(window_size=100, min_mapq=1, min_cov=4)
+    eng.set_contigs(lens)
+
+
+@pytest.mark.parametrize("piece", [1 << 30, 4096], ids=["one-piece", "4096"])
+@pytest.mark.parametrize("route", list(FEED_ROUTES))
+def test_ingest_feed_routes(feed_routes_bam, route, piece):
+    """Each of gd_ingest_feed's three routes for a staged piece, through the ABI: the file whole and in pieces of 4096 bytes
+    (the two staging buffers in turn, members complete at arbitrary feed boundaries, inflate launches mid-feed)."""
+    from goleft_amd.engine import DepthEngine
+    lens, reads, data, ends, lin, want = feed_routes_bam
+    assert len(ends) >= 17
+    with DepthEngine(0) as eng:
+        _feed_route_engine(eng, route, lens)
+        for tid in (0, 1):
+            assert eng.ingest_bgzf_stream(tid, data, 0, lin[tid], piece) == reads[tid].n
+        eng.compute()
+        for tid in (0, 1):
+            assert np.array_equal(eng.perbase(tid), want[tid]), tid
+        assert (eng.get_option(OPT_INGEST_DMA), eng.get_option(OPT_INGEST_CU_SPLIT)) == FEED_ROUTES[route]
+
+
+@pytest.mark.parametrize("route", ["copy-kernel", "copy-kernel-cu-split"])
+def test_ingest_feed_routes_two_ranges(feed_routes_bam, route):
+    """The copy-kernel routes with two ranges fed before the first is decoded (as test_ingest_two_ranges_pending feeds
+    them); the first range takes an ODD number of pieces, so the second one starts on the other staging buffer."""
+    from goleft_amd.engine import DepthEngine
+    lens, reads, data, ends, lin, want = feed_routes_bam
+    start1 = int(lin[1][0]) >> 16                            # the member reference 1's records start in
+    used0 = max(e for e in ends if e <= start1 + 65536 + 26)  # what ingest_feed_range feeds of the first slice: whole members
+    piece0 = -(-used0 // 5)
+    assert -(-used0 // piece0) == 5
+    with DepthEngine(0) as eng:
+        _feed_route_engine(eng, route, lens)
+        eng.ingest_feed_range(data[:start1 + 65536 + 26], 0, piece=piece0)       # reference 0
+        eng.ingest_feed_range(data[start1:], start1, piece=4096)                 # reference 1
+        assert eng.ingest_decode(0, 0, lin[0]) == reads[0].n
+        eng.ingest_release()
+        assert eng.ingest_decode(1, 1, lin[1]) == reads[1].n
+        eng.ingest_release()
+        eng.compute()
+        for tid in (0, 1):
+            assert np.array_equal(eng.perbase(tid), want[tid]), tid
+        assert (eng.get_option(OPT_INGEST_DMA), eng.get_option(OPT_INGEST_CU_SPLIT)) == FEED_ROUTES[route]

@@ -80,7 +80,7 @@ def main():
                                env=dict(os.environ, GOLEFT_DEPTH_TIMING="1", GOLEFT_INGEST_TIMING="1", **env), stderr=subprocess.PIPE)
             dt = time.perf_counter() - t0
             assert p.returncode == 0, p.stderr.decode()
-            if os.environ.get("SCOPE3_KEEP_STDERR"):       # (measurement builds print marks of their own)
+            if os.environ.get("SCOPE3_KEEP_STDERR"):       # (the timing lines of every run, kept)
                 with open(os.environ["SCOPE3_KEEP_STDERR"], "a") as f:
                     f.write("== %s %s run %d\n%s\n" % (decoder, env, rep, p.stderr.decode()))
             lines = p.stderr.decode().strip().splitlines()
