@@ -3,13 +3,13 @@ exact formatting, the restatement (tests/indexcov_ref.py) against hand-computed 
 to the principal components against numpy's SVD, and the new ABI symbols."""
 import ctypes as C
 import os
-from fractions import Fraction
 
 import numpy as np
 import pytest
 
 from goleft_amd import _hostlib, _lib
 from tests import indexcov_ref as R
+from tests.indexcov_shapes import notation_edges, tie_neighbourhood, tiny_quotients
 
 
 def digits(x):
@@ -43,22 +43,6 @@ def check(values):
         assert text(c) == "%.3g" % float(np.float32(x)), x
 
 
-def tie_neighbourhood():
-    """Every float32 in 1e-5 .. 5e4 that is a three-digit tie (d.dd5 x 10^e exactly) or the float32 next to one."""
-    out = []
-    for e in range(-5, 5):
-        for d in range(100, 1000):
-            tie = Fraction(2 * d + 1, 2) * Fraction(10) ** (e - 2)
-            if tie > 50000:
-                continue
-            f = np.float32(float(tie))                       # a float32 beside the tie (or the tie itself)
-            lo, hi = np.nextafter(f, np.float32(0)), np.nextafter(f, np.float32(np.inf))
-            out += [lo, f, hi]
-            if Fraction(float(f)) == tie:                    # representable: one more on each side
-                out += [np.nextafter(lo, np.float32(0)), np.nextafter(hi, np.float32(np.inf))]
-    return np.array(out, np.float32)
-
-
 def test_round3g_ties_and_their_neighbours():
     v = tie_neighbourhood()
     assert len(v) > 27000
@@ -68,14 +52,9 @@ def test_round3g_ties_and_their_neighbours():
 
 
 def test_round3g_notation_boundaries_and_small_quotients():
-    edge = [9.995e-5, 0.0001, 999.5, 1000, 50000, 0, 0.00099951, 0.001, 9.99e-5, 1e-5, 99.95, 100, 0.5, 1, 8, 1.15, 12.25,
-            10.25, 122.5, 123.5, 1005, 10050, 49950, 999.49994, 999.50006]
-    for x in list(edge):
-        f = np.float32(x)
-        edge += [np.nextafter(f, np.float32(0)), np.nextafter(f, np.float32(np.inf))]
-    check([x for x in edge if x >= 0])
-    tiny = [np.float32(1) / np.float32(3e30), np.float32(1e-38), np.float32(1.4e-45), np.float32(7e-45), np.float32(1.17549435e-38),
-            np.float32(3.3e-33), np.float32(9.995e-31), np.float32(5e-324), np.float32(1e-20), np.float32(2.5e-12)]
+    check(notation_edges())
+    tiny = tiny_quotients()
+    assert sum(0 < float(x) < 1.17549435e-38 for x in tiny) >= 2 and 0.0 in [float(x) for x in tiny]
     check(tiny)
     assert text(digits([50000])[0]) == "5e+04" and text(digits([0.0001])[0]) == "0.0001" and text(digits([1000])[0]) == "1e+03"
 
