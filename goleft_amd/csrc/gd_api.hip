@@ -414,7 +414,7 @@ static int index_records(gd_ctx* c, ContigHost& h, size_t r0, size_t r1, int32_t
     const bool idx = c->ingest_index && h.ridx_reads == r0;      // (an index with a hole is no index)
     if (idx && !h.ridx) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&h.ridx), n_idx * sizeof(uint32_t)));
     if (!idx && !check) return GD_OK;
-    gd::norm::IndexJob j{};
+    gd::IndexJob j{};
     j.pos = h.pos; j.off = h.off; j.cigar = h.cigar;
     j.ridx = idx ? h.ridx : nullptr;
     j.n_idx = (uint32_t)n_idx;
@@ -427,7 +427,7 @@ static int index_records(gd_ctx* c, ContigHost& h, size_t r0, size_t r1, int32_t
     j.check = check ? 1u : 0u;
     // spans are measured for short-read shaped data only (a lane walks its read's ops one by one)
     j.walk_ops = (c->ingest_index && h.n_ops <= 6 * r1) ? 1u : 0u;          // (r1 = the contig's records once this block is in)
-    hipLaunchKernelGGL(gd::norm::gd_index_records_kernel, dim3((unsigned)((r1 - r0 + 255) / 256)), dim3(256), 0, st, j);
+    hipLaunchKernelGGL(gd::gd_index_records_kernel, dim3((unsigned)((r1 - r0 + 255) / 256)), dim3(256), 0, st, j);
     HIPCHK(c, hipGetLastError());
     if (idx) h.ridx_reads = r1;
     if (j.walk_ops) c->ingest_span_dirty = true;
@@ -662,7 +662,7 @@ static int commit_block(gd_ctx* c, const gd_batch* b, int32_t tid, size_t n_read
     s.busy = true;
     if (h.ck_ok) {                          // the long-read structures no longer cover the stream
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        drop_norm(h);
+        drop_ck(h);
     }
     h.n_reads += n_reads;
     h.n_ops += n_ops;
@@ -1006,8 +1006,7 @@ int gd_set_profiling(gd_ctx* c, int on)
 {
     if (!c) return GD_E_INVALID;
     c->profiling = on != 0;
-    c->kernel_ms[GD_K_NORM] = 0;                        // accumulate over the contigs normalised / checkpointed
-    c->kernel_ms[GD_K_CKPT] = 0;                        // from now on
+    c->kernel_ms[GD_K_CKPT] = 0;                        // accumulates over the contigs checkpointed from now on
     return GD_OK;
 }
 

@@ -38,7 +38,6 @@ static void compute_build_table(gd_ctx* c, ComputeState& S)
         d.pos = h.pos; d.flag = h.flag; d.mapq = h.mapq;
         d.off = h.off;
         d.cigar = h.cigar;
-        d.rec = nullptr;
         d.pidx = h.ridx && h.n_reads && h.ridx_reads == h.n_reads ? h.ridx : nullptr;
         d.pidx_last = (uint32_t)std::min<int64_t>((int64_t)h.last_pos >> 6, (h.length >> 6) + 1);
         d.pad_ = 0;
@@ -100,9 +99,8 @@ static int compute_prepare(gd_ctx* c, ComputeState& S)
     if (S.tids.empty()) { S.tids.resize(c->contigs.size()); for (size_t i = 0; i < S.tids.size(); ++i) S.tids[i] = (int32_t)i; }
     for (auto& h : c->contigs) { h.base_off = h.win_off = -1; h.n_win = 0; h.run_beg = h.run_end = 0; }
     {
-        const float norm_ms = c->kernel_ms[GD_K_NORM], ck_ms = c->kernel_ms[GD_K_CKPT];   // ingest-time work
+        const float ck_ms = c->kernel_ms[GD_K_CKPT];     // ingest-time work
         memset(c->kernel_ms, 0, sizeof c->kernel_ms);
-        c->kernel_ms[GD_K_NORM] = norm_ms;
         c->kernel_ms[GD_K_CKPT] = ck_ms;
     }
     S.n_reads = S.n_ops = 0;
@@ -234,9 +232,7 @@ static int compute_enqueue(gd_ctx* c, ComputeState& S)
     }
     // The straight-line tile kernel reads the records as they arrived (no pass over the records before the first --
     // usually the only -- compute of an input); contig arrays its vector loads cannot take: the generic kernel.
-    uint32_t fast = 0;
-    if (!scatter && !chunk && c->fast_kernel) fast = S.raw_aligned ? 2u : 0u;
-    job.fast = fast;
+    job.fast = !scatter && !chunk && c->fast_kernel && S.raw_aligned;
     compute_build_table(c, S);
     if (job.fast) {
         if (int r = ensure_dev(c, &c->d_ftiles, &c->cap_ftiles, (size_t)c->n_tiles)) return r;
@@ -261,10 +257,10 @@ static int compute_enqueue(gd_ctx* c, ComputeState& S)
         // the look-back IS the largest span (exact, known since the records arrived)
         job.lookback = std::max(64, (int32_t)((S.chunk_span + 63) & ~63));
         if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-        launch_prep<4096>(c, job);
+        launch_prep(c, job);
         c->slow_counter_clean = true;
         if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-        launch_ltile<4096, 256>(c, job);
+        launch_ltile(c, job);
         if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
         hipLaunchKernelGGL(gd::gd_runs_order_kernel, dim3(runs_grid), dim3(gd::SUPER), 0,
                            c->stream, c->d_chunks, job.run_cap, c->d_tile_cnt, c->d_tile_off,
@@ -295,18 +291,17 @@ static int compute_enqueue(gd_ctx* c, ComputeState& S)
         } else {
             if (c->ran_sums_only) job.fast = 0;              // the sums-only kernel reads the generic tile table
             if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-            launch_prep<4096>(c, job);
+            launch_prep(c, job);
             c->slow_counter_clean = true;
             if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-            launch_tile<4096, 256>(c, job);
+            launch_tile(c, job);
             if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
             if (!c->ran_sums_only)                           // no class runs in sums-only mode
                 hipLaunchKernelGGL(gd::gd_runs_order_kernel, dim3(runs_grid), dim3(gd::SUPER), 0,
                                    c->stream, c->d_chunks, job.run_cap, c->d_tile_cnt, c->d_tile_off,
                                    c->d_super_cnt, c->d_ordered, (int)c->n_tiles);
             if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-            S.it_kernel = c->ran_sums_only ? GD_TK_TILE_SUMS : job.fast == 1u ? GD_TK_FAST : job.fast == 2u ? GD_TK_FAST_RAW
-                                                                                                            : GD_TK_GENERIC;
+            S.it_kernel = c->ran_sums_only ? GD_TK_TILE_SUMS : job.fast ? GD_TK_FAST_RAW : GD_TK_GENERIC;
         }
     } else {
         if (int r = ensure_dev(c, &c->d_status, &c->cap_status, (size_t)c->n_tiles)) return r;
@@ -328,7 +323,7 @@ static int compute_enqueue(gd_ctx* c, ComputeState& S)
             hipLaunchKernelGGL(gd::gd_expand_scatter_kernel, dim3(grid), dim3(256), 0, c->stream, job);
         }
         if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-        hipLaunchKernelGGL((gd::gd_scan_kernel<4096, 256>), dim3((unsigned)c->n_tiles), dim3(256), 0, c->stream, job);
+        hipLaunchKernelGGL(gd::gd_scan_kernel, dim3((unsigned)c->n_tiles), dim3(gd::shape::NT), 0, c->stream, job);
         if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
         hipLaunchKernelGGL(gd::gd_runs_order_kernel, dim3(runs_grid), dim3(gd::SUPER), 0,
                            c->stream, c->d_chunks, job.run_cap, c->d_tile_cnt, c->d_tile_off,
@@ -472,9 +467,6 @@ static int compute_publish(gd_ctx* c, ComputeState& S)
     if ((uint32_t)c->stats.n_slow_tiles > c->slow_grid * 4u) c->slow_grid = std::min<uint32_t>(2048u, (uint32_t)c->stats.n_slow_tiles);
     c->stats.n_canonical_ops = 0;
     c->stats.n_deletions = 0;
-    if (!S.used_scatter)
-        for (const gd::ContigDev& d : c->h_ctgs)
-            if (d.rec) c->stats.n_canonical_ops += d.n_ops;
     if (S.used_chunk)
         for (int32_t tid : c->job_tids) c->stats.n_deletions += c->contigs[tid].n_dels;
     if (S.used_scatter) c->stats.max_span_seen = 0;   // not measured on this path
@@ -561,7 +553,7 @@ int gd_drop_derived(gd_ctx* c)
     if (c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
     if (int r = set_device(c)) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (auto& h : c->contigs) drop_norm(h);
+    for (auto& h : c->contigs) drop_ck(h);
     c->computed = false;
     return GD_OK;
 }

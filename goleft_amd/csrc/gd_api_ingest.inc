@@ -566,7 +566,7 @@ static int ingest_decode(gd_ctx* c, int32_t tid, int32_t ref_id, const uint64_t*
         h.length = len;
     } else if (h.ck_ok) {                     // derived structures no longer cover the stream
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        drop_norm(h);
+        drop_ck(h);
     }
     if (N) {
         // one allocation for the whole reference when the caller knows what to expect (a reference read in parts),

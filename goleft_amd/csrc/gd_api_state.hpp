@@ -15,8 +15,7 @@ constexpr int kRingSlots = 4;
 constexpr size_t kSpecBounds = 4096;     // boundaries copied to the host before their count is known (one synchronisation)
 constexpr int kDefaultLookback = 512;
 constexpr uint64_t kMaxReadsPerContig = 1ull << 30;
-constexpr int kTileT = 4096;              // reference positions per tile, 256 threads each: the one shape that is built (8192
-                                           // positions and 512 threads were measured slower on every workload and retired)
+constexpr int kTileT = gd::shape::T;       // reference positions per tile (gd_kernels.hpp: the one shape that is built)
 constexpr int kAutoLongSpan = 32768;      // GD_PATH_AUTO leaves the short-read tile path above this read span
 constexpr int kMaxSpan = 1 << 27;   // tile-relative byte offsets of the tile kernel stay in 32 bits
 
@@ -164,7 +163,7 @@ struct gd_ctx {
     // tuning knobs (gd_set_option; defaults are what the measurements of DESIGN.md section 4 chose)
     bool fast_kernel = true;            // GD_OPT_FAST_KERNEL: the straight-line tile kernel (gd_tile_fast.hpp) for
                                         // ordinary tiles, the generic one for the rest; 0 = generic for every tile
-    std::vector<uint8_t> batch_tab, batch_tab_ck;   // host copies of the job tables of the last norm_batch / ck batch
+    std::vector<uint8_t> batch_tab_ck;  // host copy of the job table of the last ck batch
     uint32_t* h_batch = nullptr; size_t cap_h_batch = 0;   // pinned: per-contig totals / status words coming back
     int tile_opt = 1;                   // bit 0: non-temporal per-base stores (2 % faster: the vector is
                                         // never re-read by the kernel)
@@ -346,11 +345,9 @@ void drop_ck(ContigHost& h)
     h.ck_ok = false;
 }
 
-void drop_norm(ContigHost& h) { drop_ck(h); }   // everything derived from the records
-
 void free_contig(ContigHost& h)
 {
-    drop_norm(h);
+    drop_ck(h);
     if (!h.adopted) {
         if (h.pos) (void)hipFree(h.pos);
         if (h.flag) (void)hipFree(h.flag);
@@ -358,7 +355,6 @@ void free_contig(ContigHost& h)
         if (h.off) (void)hipFree(h.off);
         if (h.cigar) (void)hipFree(h.cigar);
     }
-    drop_ck(h);
     if (h.ridx) (void)hipFree(h.ridx);
     h.ridx = nullptr; h.ridx_reads = 0;
     h.ing_left = false;
@@ -398,7 +394,6 @@ int set_device(gd_ctx* c)
     return GD_OK;
 }
 
-template <int T>
 void launch_prep(gd_ctx* c, const gd::Job& job)
 {
     // one thread per tile; the same threads grid-stride over the window arrays (a thread per window made a 30x
@@ -406,19 +401,34 @@ void launch_prep(gd_ctx* c, const gd::Job& job)
     int64_t work = std::max<int64_t>(job.n_tiles, std::min<int64_t>(job.n_win_total / 8, 1 << 20));
     int blocks = (int)((work + 255) / 256);
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(gd::gd_prep_kernel<T>, dim3(blocks), dim3(256), 0, c->stream, job);
+    hipLaunchKernelGGL(gd::gd_prep_kernel, dim3(blocks), dim3(256), 0, c->stream, job);
 }
 
-template <int T, int NT>
+// The per-base store mode of a tile kernel (its OPT / ST template parameter), chosen at launch: f gets it as a
+// compile-time constant -- 2: no per-base output, 1: non-temporal stores (GD_OPT_NT_STORES), 0: plain stores.
+template <class F>
+void with_store_mode(const gd_ctx* c, F&& f)
+{
+    if (!c->keep_perbase) f(std::integral_constant<int, 2>{});
+    else if (c->tile_opt & 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 0>{});
+}
+
 void launch_tile(gd_ctx* c, const gd::Job& job)
 {
     // 8 XCDs: the grid is 8 equal slices of the tile list (see the kernel)
     const unsigned grid = (unsigned)(((job.n_tiles + 7) / 8) * 8);
+    const dim3 block(gd::shape::NT);
     if (c->ran_sums_only) {                                 // decided by gd_compute for this run
-        hipLaunchKernelGGL((gd::gd_tile_sums_kernel<4096, 256>), dim3(grid), dim3(256), 0, c->stream, job);
+        hipLaunchKernelGGL(gd::gd_tile_sums_kernel, dim3(grid), block, 0, c->stream, job);
         return;
     }
-    if (job.fast) {
+    with_store_mode(c, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        if (!job.fast) {
+            hipLaunchKernelGGL(gd::gd_tile_kernel<M>, dim3(grid), block, 0, c->stream, job);
+            return;
+        }
         // ordinary tiles: the straight-line kernel; the tiles gd_prep_kernel listed as `slow` (clipped at a
         // contig end, deeper than one batch of reads, more ops than the staging area): the generic one
         // The slow list (a few dozen workgroups of a large, cold kernel) goes FIRST: launched after the
@@ -426,53 +436,32 @@ void launch_tile(gd_ctx* c, const gd::Job& job)
         // write-back of that kernel's per-base stores; in front of it, it costs a few microseconds
         // (profiles/r02d_slow_first.txt; a side stream next to the straight-line kernel bought nothing).
         const unsigned sgrid = c->slow_grid;                 // strides over the slow list (usually one tile per contig)
-        if (!c->keep_perbase)
-            hipLaunchKernelGGL((gd::gd_tile_slow_kernel<4096, 256, 2>), dim3(sgrid), dim3(256), 0, c->stream, job);
-        else if (c->tile_opt & 1)
-            hipLaunchKernelGGL((gd::gd_tile_slow_kernel<4096, 256, 1>), dim3(sgrid), dim3(256), 0, c->stream, job);
-        else
-            hipLaunchKernelGGL((gd::gd_tile_slow_kernel<4096, 256, 0>), dim3(sgrid), dim3(256), 0, c->stream, job);
-        if (job.fast == 2u) {                                // the records as they arrived
-            if (!c->keep_perbase)
-                hipLaunchKernelGGL((gd::fast::gd_tile_fast_kernel<2>), dim3(grid), dim3(256), 0, c->stream, job);
-            else if (c->tile_opt & 1)
-                hipLaunchKernelGGL((gd::fast::gd_tile_fast_kernel<1>), dim3(grid), dim3(256), 0, c->stream, job);
-            else
-                hipLaunchKernelGGL((gd::fast::gd_tile_fast_kernel<0>), dim3(grid), dim3(256), 0, c->stream, job);
-            return;
-        }
-        return;
-    }
-    if (!c->keep_perbase)
-        hipLaunchKernelGGL((gd::gd_tile_kernel<T, NT, 2>), dim3(grid), dim3(NT), 0, c->stream, job);
-    else if (c->tile_opt & 1)
-        hipLaunchKernelGGL((gd::gd_tile_kernel<T, NT, 1>), dim3(grid), dim3(NT), 0, c->stream, job);
-    else
-        hipLaunchKernelGGL((gd::gd_tile_kernel<T, NT, 0>), dim3(grid), dim3(NT), 0, c->stream, job);
+        hipLaunchKernelGGL(gd::gd_tile_slow_kernel<M>, dim3(sgrid), block, 0, c->stream, job);
+        hipLaunchKernelGGL(gd::fast::gd_tile_fast_kernel<M>, dim3(grid), block, 0, c->stream, job);
+    });
 }
 
-template <int T, int NT>
 void launch_ltile(gd_ctx* c, const gd::Job& job)
 {
     const unsigned grid = (unsigned)(((job.n_tiles + 7) / 8) * 8);
-    if (!c->keep_perbase)
-        hipLaunchKernelGGL((gd::gd_ltile2_kernel<T, NT, 2>), dim3(grid), dim3(NT), 0, c->stream, job);
-    else
-        hipLaunchKernelGGL((gd::gd_ltile2_kernel<T, NT, 0>), dim3(grid), dim3(NT), 0, c->stream, job);
+    with_store_mode(c, [&](auto m) {
+        constexpr int M = decltype(m)::value == 1 ? 0 : decltype(m)::value;   // (built with plain stores and with none)
+        hipLaunchKernelGGL(gd::gd_ltile2_kernel<M>, dim3(grid), dim3(gd::shape::NT), 0, c->stream, job);
+    });
 }
 
 // In-place exclusive scan of v[0..n) on the compute stream, v[n] = total (v has n + 1 elements).
 int launch_scan(gd_ctx* c, uint32_t* v, uint32_t n)
 {
-    if (n <= 4u * gd::norm::SCAN_BLOCK) {
-        hipLaunchKernelGGL(gd::norm::gd_unit_scan_kernel, dim3(1), dim3(1024), 0, c->stream, v, n);
+    if (n <= 4u * gd::SCAN_BLOCK) {
+        hipLaunchKernelGGL(gd::gd_unit_scan_kernel, dim3(1), dim3(1024), 0, c->stream, v, n);
         return GD_OK;
     }
-    const uint32_t nb = (n + gd::norm::SCAN_BLOCK - 1u) / gd::norm::SCAN_BLOCK;
+    const uint32_t nb = (n + gd::SCAN_BLOCK - 1u) / gd::SCAN_BLOCK;
     if (int r = ensure_dev(c, &c->d_scan_tmp, &c->cap_scan_tmp, (size_t)nb + 1)) return r;
-    hipLaunchKernelGGL(gd::norm::gd_scan_totals_kernel, dim3(nb), dim3(256), 0, c->stream, v, n, c->d_scan_tmp);
-    hipLaunchKernelGGL(gd::norm::gd_unit_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_scan_tmp, nb);
-    hipLaunchKernelGGL(gd::norm::gd_scan_apply_kernel, dim3(nb), dim3(256), 0, c->stream, v, n, c->d_scan_tmp, nb);
+    hipLaunchKernelGGL(gd::gd_scan_totals_kernel, dim3(nb), dim3(256), 0, c->stream, v, n, c->d_scan_tmp);
+    hipLaunchKernelGGL(gd::gd_unit_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_scan_tmp, nb);
+    hipLaunchKernelGGL(gd::gd_scan_apply_kernel, dim3(nb), dim3(256), 0, c->stream, v, n, c->d_scan_tmp, nb);
     return GD_OK;
 }
 
@@ -514,7 +503,6 @@ int batch_host(gd_ctx* c, size_t words)
 // records as they arrived: ONE allocation sized from the record counts alone (deletion lists: half the ops + a slot per
 // read; tile indexes: an entry per 64 ops + three per read -- gd_chunk.hpp pt_slot), ONE pass (gd_dels_raw_kernel fills the
 // index as it walks), one small kernel that puts every contig's deletion total and largest span into page-locked memory.
-// Until round 5 the index was three more launches with a host synchronisation and a second allocation between them.
 struct CkPending {
     std::vector<ContigHost*> hs;
     BlockRef blk;
@@ -550,7 +538,7 @@ int ck_enqueue(gd_ctx* c, const std::vector<ContigHost*>& hs, CkPending* P)
     if (units > (1ull << 26) - 64) return fail(c, GD_E_RANGE, "too many records in one batch (internal error)");
     P->n_units = (uint32_t)units;
     P->o_jobs = cv.take(nj * sizeof(gd::DelJob) + (nj + 1) * sizeof(uint32_t));   // the jobs, then ubeg
-    P->o_tot = cv.take(3 * nj * sizeof(uint32_t));               // [unused][deletions][largest span] per contig
+    P->o_tot = cv.take(2 * nj * sizeof(uint32_t));               // [deletions x n][largest spans x n]
     if (int r = batch_block(c, std::move(keep), cv.at, &P->blk)) return r;
     char* const base = static_cast<char*>(P->blk->p);
     // job table (host copy kept in the context until the next batch)
@@ -570,7 +558,6 @@ int ck_enqueue(gd_ctx* c, const std::vector<ContigHost*>& hs, CkPending* P)
         j.lfq = reinterpret_cast<uint32_t*>(base + P->o_lfq[k]);
         j.dl = reinterpret_cast<uint2*>(base + P->o_dl[k]);
         j.ndel = reinterpret_cast<uint32_t*>(base + P->o_ndel[k]);
-        j.del_total = reinterpret_cast<uint32_t*>(base + P->o_tot) + nj + k;
         j.max_span = reinterpret_cast<int32_t*>(j.lrec + n + 1);
         j.pck = reinterpret_cast<uint32_t*>(base + P->o_pck[k]);
         j.total = reinterpret_cast<uint32_t*>(base + P->o_tot) + k;
@@ -586,7 +573,7 @@ int ck_enqueue(gd_ctx* c, const std::vector<ContigHost*>& hs, CkPending* P)
     B.n_jobs = (uint32_t)nj; B.n_units = P->n_units;
     for (size_t k = 0; k < nj; ++k)                          // lrec[n], lrec[n + 1] (the span accumulator)
         HIPCHK(c, hipMemsetAsync(base + P->o_lrec[k] + hs[k]->n_reads * sizeof(uint4), 0, 2 * sizeof(uint4), c->stream));
-    HIPCHK(c, hipMemsetAsync(base + P->o_tot, 0, 2 * nj * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(base + P->o_tot, 0, nj * sizeof(uint32_t), c->stream));   // (gd_ptile_totals_kernel writes the spans)
     if (P->n_units)
         hipLaunchKernelGGL(gd::gd_dels_raw_kernel, dim3((P->n_units + 3u) / 4u), dim3(256), 0, c->stream, B);
     hipLaunchKernelGGL(gd::gd_ptile_totals_kernel, dim3((unsigned)((nj + 255) / 256)), dim3(256), 0, c->stream, B);
@@ -594,15 +581,15 @@ int ck_enqueue(gd_ctx* c, const std::vector<ContigHost*>& hs, CkPending* P)
     return GD_OK;
 }
 
-// host words the totals of a ck batch take in gd_ctx::h_batch: [n_jobs unused][n_jobs deletion counts][n_jobs spans]
+// host words the totals of a ck batch take in gd_ctx::h_batch: [n_jobs deletion counts][n_jobs spans]
 int ck_readback(gd_ctx* c, const CkPending& P, uint32_t* dst)
 {
     const size_t nj = P.hs.size();
     if (nj == 0) return GD_OK;
     char* const base = static_cast<char*>(P.blk->p);
-    // (dst is page-locked: a one-wave kernel stores the 3 n words there -- no copy commands; there used to be 1 + n of them)
+    // (dst is page-locked: a one-wave kernel stores the 2 n words there -- no copy commands; there used to be 1 + n of them)
     hipLaunchKernelGGL(gd::gd_copy_words_kernel, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<const uint32_t*>(base + P.o_tot), dst,
-                       (uint32_t)(3 * nj));
+                       (uint32_t)(2 * nj));
     HIPCHK(c, hipGetLastError());
     return GD_OK;
 }
@@ -617,8 +604,8 @@ int ck_finish(gd_ctx* c, CkPending& P, const uint32_t* tot)
         ContigHost& h = *P.hs[k];
         h.ck_blk = P.blk;
         h.lrec = jobs[k].lrec; h.lfq = jobs[k].lfq; h.dl = jobs[k].dl; h.pck = jobs[k].pck; h.ndel = jobs[k].ndel;
-        h.max_span = (int32_t)tot[2 * nj + k];
-        h.n_dels = tot[nj + k];
+        h.max_span = (int32_t)tot[nj + k];
+        h.n_dels = tot[k];
         h.ck_ok = true;
     }
     return GD_OK;
@@ -633,7 +620,7 @@ int ck_batch(gd_ctx* c, const std::vector<ContigHost*>& hs)
     if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
     CkPending P;
     if (int r = ck_enqueue(c, hs, &P)) return r;
-    if (int r = batch_host(c, 3 * hs.size())) return r;
+    if (int r = batch_host(c, 2 * hs.size())) return r;
     if (int r = ck_readback(c, P, c->h_batch)) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (int r = ck_finish(c, P, c->h_batch)) return r;

@@ -41,7 +41,7 @@ namespace gd {
 
 constexpr uint32_t DL_CHUNK = 64;             // deletions per queued piece
 constexpr int PT_SHIFT = 12;                  // the tile index has one entry per 4096 reference positions
-constexpr int DL_UNROLL = 4;                  // 64-op groups in flight per wave in gd_dels_kernel
+constexpr int DL_UNROLL = 4;                  // 64-op groups in flight per wave in wave_dels
 
 __device__ __forceinline__ uint32_t sat_pos(uint32_t v) { return v < POS_CAP ? v : POS_CAP; }
 
@@ -71,20 +71,17 @@ struct DelJob {
     uint32_t* lfq;            // n_reads: flag << 8 | MAPQ (the filter is applied per tile)
     uint2*    dl;             // deletion lists {start, length}: (n_ops >> 1) + n_reads + 1 entries
     uint32_t* ndel;           // n_reads: deletions of each read
-    uint32_t* del_total;      // out: deletions of the contig
     int32_t*  max_span;       // atomicMax of end - pos
     // the tile index (PT kernels below)
     uint32_t* pck;            // the index: (n_ops >> 6) + 3 n_reads + 4 entries, read r's at pt_slot(off[r], r)
-    uint32_t* total;          // out: [n_jobs] deletions of the contig, [2 n_jobs] its largest span ([0 .. n_jobs) is reserved: the layout is the host's)
+    uint32_t* total;          // out: [0] deletions of the contig, [n_jobs] its largest span (the host reads [deletions x n][spans x n])
 };
 constexpr uint32_t PT_NONE = 0xffffffffu;
 constexpr uint32_t PT_SEARCH = 0xfffffffeu;   // the read has deletions but no tile index (its slots were too few): the tile kernel bisects its list
 
-// Round 5: the tile index is filled BY THE PASS THAT WRITES THE DELETION LISTS.  It used to be three more launches (entries
-// per read, a scan over the 64-read units, a fill pass in which every read bisected its own list per boundary) with a host
-// synchronisation and an allocation between them -- 1.6-2.3 ms of an 8.2 ms preparation, and the only reason the first
-// compute's enqueue could not run through.  The walk knows where every deletion starts as it goes: entry k of a read =
-// deletions that start before boundary ((pos >> 12) + k) << 12, and a group of ops that covers the reference positions
+// The tile index is filled BY THE PASS THAT WRITES THE DELETION LISTS (no launch, host synchronisation or allocation of
+// its own, so the first compute's enqueue runs through).  The walk knows where every deletion starts as it goes: entry k of
+// a read = deletions that start before boundary ((pos >> 12) + k) << 12, and a group of ops that covers the reference positions
 // (cur, cur + tot] fixes exactly the boundaries inside that range -- deletions of earlier groups start before them, later
 // ones behind.  A group crosses a boundary once in five (4096 bases, ~13 per op): one scalar compare per group otherwise.
 // Where the entries live needs no prefix sum either: read r of a contig owns the slots (o >> 6) + 3 r .. ((o + n) >> 6) + 3 r + 2
@@ -108,12 +105,11 @@ struct DelBatch {
 };
 
 
-// ---- the same structures straight from the records AS THEY ARRIVED ------------------------------------------------
-// One pass over the original CIGARs (round 2 went through a rewritten, "canonical" copy of the CIGARs first: a 20x ONT
-// genome's 19 GB of ops read twice and 10 GB written and read again before the first deletion list existed -- 24 + 3 ms in
-// front of a 4.6 ms tile kernel; a run computes its input once).  The merging walk below keeps that copy's rules without
-// writing it: I/S/H/P and zero-length ops vanish, neighbouring D/N ops merge into ONE
-// deletion, one that no M follows is dropped, and a read ends where its last M ends.
+// ---- the structures straight from the records AS THEY ARRIVED: one pass over the original CIGARs ----------------------
+
+// The merging walks: I/S/H/P and zero-length ops vanish, neighbouring D/N ops merge into ONE deletion, one that no M follows
+// is dropped, and a read ends where its last M ends.  The fallback for a read whose D/N ops outnumber its slots
+// (gd_dels_raw_kernel): merged runs always fit, at most half the ops are deletions then.
 
 // one lane, op by op (short CIGARs; ops longer than 2^22 bases or runs that overflow)
 __device__ __forceinline__ uint32_t serial_dels(const uint32_t* __restrict__ ops, uint32_t n, uint32_t pos,
@@ -138,8 +134,8 @@ __device__ __forceinline__ uint32_t serial_dels(const uint32_t* __restrict__ ops
     return w;
 }
 
-// a whole wave, 64 ops at a time (wave_canonical's run logic: heads from ballots, run lengths as differences of one
-// wave prefix sum).  `overflow`: an op longer than 2^22 bases or a run past the 28-bit range -- the caller walks that
+// The merging walk by a whole wave, 64 ops at a time (heads from ballots, run lengths as differences of one wave prefix
+// sum).  `overflow`: an op longer than 2^22 bases or a run past the 28-bit range -- the caller walks that
 // read with serial_dels (what it wrote before noticing is overwritten).  A run's length is a plain 32-bit sum: it cannot
 // pass the position cap the walk checks (a deletion is {start, length} in 32 bits each; no 28-bit op field to fit).
 __device__ __forceinline__ uint32_t wave_dels(const uint32_t* __restrict__ ops, uint32_t n, int lane, uint32_t pos,
@@ -270,7 +266,7 @@ __device__ __forceinline__ uint32_t serial_dels_plain(const uint32_t* __restrict
     return w;                                                          // > cap: the caller walks the read again
 }
 
-// Round 6: FOUR CONSECUTIVE ops per lane.  The walk above it replaced took a batch of 256 ops as four groups of 64 -- one op per
+// FOUR CONSECUTIVE ops per lane.  The walk it replaced took a batch of 256 ops as four groups of 64 -- one op per
 // lane and group: four wave prefix sums, four ballots, four rank computations and four boundary tests per batch, ~175
 // instructions -- and the pass is bound by exactly that (18.7 M batches per genome x 175 instructions is 5.4 of its 7.0 ms at
 // one vector instruction per four cycles and SIMD; halving its list bytes changed nothing, HISTORY.md).  Here a lane loads its
@@ -354,7 +350,7 @@ __global__ __launch_bounds__(256) void gd_dels_raw_kernel(DelBatch B)
     const int lane = threadIdx.x & 63;
     const uint32_t gunit = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (gunit >= B.n_units) return;
-    const uint32_t ji = (uint32_t)__builtin_amdgcn_readfirstlane((int)norm::batch_find(B.ubeg, B.n_jobs, gunit));
+    const uint32_t ji = (uint32_t)__builtin_amdgcn_readfirstlane((int)batch_find(B.ubeg, B.n_jobs, gunit));
     const DelJob job = B.jobs[ji];
     const uint32_t unit = gunit - B.ubeg[ji];
     const uint32_t r = unit * 64u + (uint32_t)lane;
@@ -415,18 +411,17 @@ __global__ __launch_bounds__(256) void gd_dels_raw_kernel(DelBatch B)
     const uint32_t smax = wave_max_u32(endp - p);
     if (lane == 0 && smax != 0u) atomicMax(job.max_span, (int32_t)smax);
     const uint32_t dsum = (uint32_t)wave_total((int)nd);
-    if (lane == 0 && dsum != 0u) atomicAdd(job.del_total, dsum);
+    if (lane == 0 && dsum != 0u) atomicAdd(job.total, dsum);
 }
 
-// Every contig's largest span next to its deletion total ([unused x n][deletions x n][spans x n]): ONE read-back for the
+// Every contig's largest span next to its deletion total ([deletions x n][spans x n]): ONE read-back for the
 // batch instead of one 4-byte copy per contig.
 __global__ __launch_bounds__(256) void gd_ptile_totals_kernel(DelBatch B)
 {
     const uint32_t ji = blockIdx.x * 256u + threadIdx.x;
     if (ji >= B.n_jobs) return;
     const DelJob job = B.jobs[ji];
-    *job.total = 0u;
-    job.total[2u * B.n_jobs] = (uint32_t)*job.max_span;
+    job.total[B.n_jobs] = (uint32_t)*job.max_span;
 }
 
 // deletions of a sorted list that start before `bound` (a read without a tile index: PT_SEARCH)
@@ -459,14 +454,10 @@ __device__ __forceinline__ void del_mark(int32_t* s_diff, bool del, uint32_t s, 
     }
 }
 
-template <int T, int NT, int OPT>
-__global__ __launch_bounds__(NT) void gd_ltile2_kernel(Job job)
+template <int OPT>
+__global__ __launch_bounds__(shape::NT) void gd_ltile2_kernel(Job job)
 {
-    constexpr int NW = NT / WAVE;
-    constexpr int CHUNK = T / NW;
-    constexpr int ROWS = CHUNK / 256;
-    constexpr int NWORDS = T / 32;
-    static_assert(CHUNK % 256 == 0, "wave chunk must be whole rows");
+    using namespace shape;
     static_assert(T % (1 << PT_SHIFT) == 0 && WAVE <= LQ_CAP, "tiles start on index boundaries; a round fits the queue");
 
     __shared__ __attribute__((aligned(16))) int32_t s_diffp[T + 4];  // [3] = index -1
@@ -611,23 +602,21 @@ __global__ __launch_bounds__(NT) void gd_ltile2_kernel(Job job)
         B.W = job.W; B.mincov = job.mincov; B.maxmean = job.maxmean; B.step = job.step;
         // a read covers a position at most once: depth <= candidate reads
         const bool wide = nrd >= (1u << 22);
-        if constexpr (ROWS == 4) {
-            if (tlen == T && !wide) {                     // workgroup uniform: the single-pass form
-                PhaseBRows R;
-                const int tot = phase_b_scan<ROWS>(B, R);
-                if (lane == 0) s_wtot[wv] = tot;
-                __syncthreads();
-                int carry = s_diff[-1];                    // depth at t0-1
+        if (tlen == T && !wide) {                         // workgroup uniform: the single-pass form
+            PhaseBRows R;
+            const int tot = phase_b_scan(B, R);
+            if (lane == 0) s_wtot[wv] = tot;
+            __syncthreads();
+            int carry = s_diff[-1];                        // depth at t0-1
 #pragma unroll
-                for (int v = 0; v < NW - 1; ++v) carry += v < wv ? s_wtot[v] : 0;
-                B.carry = carry;
-                phase_b_finish<ROWS, OPT>(B, R, job.w_magic, job.w_shift, job.s_magic, job.s_shift);
-                __syncthreads();
-                phase_c<T, NT>(job, tile, t0, ti.ctg, tid, lane, wv, s_bmap, s_clo, s_chi, s_wcnt, &s_hasb, &s_base);
-                return;
-            }
+            for (int v = 0; v < NW - 1; ++v) carry += v < wv ? s_wtot[v] : 0;
+            B.carry = carry;
+            phase_b_finish<OPT>(B, R, job.w_magic, job.w_shift, job.s_magic, job.s_shift);
+            __syncthreads();
+            phase_c(job, tile, t0, ti.ctg, tid, lane, wv, s_bmap, s_clo, s_chi, s_wcnt, &s_hasb, &s_base);
+            return;
         }
-        // clipped / very deep tiles and other tile shapes: totals pass, then row by row
+        // clipped / very deep tiles: totals pass, then row by row
         {
             int tot = 0;
 #pragma unroll
@@ -643,12 +632,11 @@ __global__ __launch_bounds__(NT) void gd_ltile2_kernel(Job job)
 #pragma unroll
         for (int v = 0; v < NW - 1; ++v) carry += v < wv ? s_wtot[v] : 0;
         B.carry = carry;
-        if (tlen == T && !wide) phase_b_rows<ROWS, true, false, OPT>(B);
-        else                    phase_b_rows<ROWS, false, true, OPT>(B);
+        phase_b_rows<false, true, OPT>(B);
     }
     __syncthreads();
 
-    phase_c<T, NT>(job, tile, t0, ti.ctg, tid, lane, wv, s_bmap, s_clo, s_chi, s_wcnt, &s_hasb, &s_base);
+    phase_c(job, tile, t0, ti.ctg, tid, lane, wv, s_bmap, s_clo, s_chi, s_wcnt, &s_hasb, &s_base);
 }
 
 }  // namespace gd

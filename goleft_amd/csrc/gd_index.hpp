@@ -8,14 +8,9 @@
 //                             runs with the data's look-back (no re-run);
 //   batch_find                the job a 64-read unit of a batch belongs to (gd_chunk.hpp);
 //   gd_unit_scan / gd_scan_*  exclusive prefix sums over small device arrays (multidepth's block finder, gd_api_aux.inc).
-// (Until round 5 this file was gd_normalize.hpp and also held the canonical-record kernels: a rewritten copy of the
-// records for a host that computes the same records many times.  No caller in the reference does -- a `goleft depth` run
-// computes each input once, /root/reference/depth/depth.go:392-421 -- and every path reads the records as they arrived;
-// they were removed.)
 #pragma once
 
 namespace gd {
-namespace norm {
 
 // last j with beg[j] <= x (beg[0] = 0, n >= 1, entries ascending)
 __device__ __forceinline__ uint32_t batch_find(const uint32_t* __restrict__ beg, uint32_t n, uint32_t x)
@@ -54,7 +49,7 @@ __global__ __launch_bounds__(1024) void gd_unit_scan_kernel(uint32_t* __restrict
 
 // The same scan for large arrays, three launches: totals of blocks of SCAN_BLOCK elements (SB1), the scan of
 // those totals by gd_unit_scan_kernel, then every block scans itself from its offset (SB2).  One workgroup alone
-// took 0.69 ms for chr1's 780 k units -- 17 of the 28 ms a genome's normalisation took.
+// took 0.69 ms for chr1's 780 k units.
 constexpr uint32_t SCAN_BLOCK = 4096;      // elements per workgroup: 256 threads x 16
 
 __global__ __launch_bounds__(256) void gd_scan_totals_kernel(const uint32_t* __restrict__ v, uint32_t n,
@@ -179,5 +174,4 @@ __global__ __launch_bounds__(256) void gd_index_records_kernel(IndexJob j)
     }
 }
 
-}  // namespace norm
 }  // namespace gd

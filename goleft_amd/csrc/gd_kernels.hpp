@@ -1,33 +1,38 @@
 // gd_kernels.hpp -- hand-written CDNA4 (gfx950) kernels of the per-base depth engine.
 //
 // Replaces the arithmetic that the reference delegates to `samtools depth`
-// (call site /root/reference/depth/depth.go:45) plus the per-line reductions of
-// its `callback` closure (depth/depth.go:238-364: window mean :293-305, class
-// run-length encoding :307-323, getCovClass :223-234).
+// (call site depth/depth.go:45) plus the per-line reductions of its `callback`
+// closure (depth/depth.go:238-364: window mean :293-305, class run-length
+// encoding :307-323, getCovClass :223-234).
 //
-// Data-parallel shape (integer, HBM-bound, no MFMA):
-//   K0 gd_prep_kernel   one thread per LDS tile: contig lookup + two binary
-//                       searches of the coordinate-sorted `pos` array (first
-//                       read that can reach the tile, first read past it);
-//                       also initialises the window accumulators.
-//   K1 gd_tile_kernel   one workgroup per tile of T reference positions:
-//                       (A) lanes walk CIGARs of the tile's reads, merge
-//                           adjacent M/=/X ops into reference intervals, clip
-//                           to the tile and ds_add +1/-1 into an int32 LDS
-//                           difference array (order independent => bit exact);
-//                       (B) each wave64 scans its quarter of the tile with a
-//                           DPP wavefront scan, rows of 256 positions, and
-//                           streams int32x4 per lane to HBM (1 KiB per
-//                           wave-instruction, the only large HBM stream);
-//                           fused in the same registers: per-window int64
-//                           sum / int32 min (flushed with one wave reduction
-//                           per window boundary) and the coverage-class
-//                           boundary detection;
-//                       (C) tiles that contain class boundaries compact them
-//                           from an LDS bitmap into a global chunk.
-//   K2 gd_runs_scan / gd_runs_gather   order the per-tile chunks.
-//   K3 gd_region_* kernels             --bed mode reductions over the resident
-//                                      per-base vector.
+// Data-parallel shape (integer, HBM-bound, no MFMA); one tile is shape::T reference
+// positions, one workgroup of shape::NT threads:
+//   K0 gd_prep_kernel   one thread per tile: contig lookup + the tile's read range
+//                       [lo, hi) in the coordinate-sorted `pos` array (from the
+//                       position index of gd_index.hpp, or by search); also
+//                       initialises the window accumulators.  A fast run gets one
+//                       resolved TileFast record per ordinary tile and a compacted
+//                       slow list of the others.
+//   K1 the tile kernels, one workgroup per tile:
+//        gd_tile_fast_kernel   ordinary tiles of the short-read path (gd_tile_fast.hpp)
+//        gd_tile_slow_kernel   the slow list of a fast run          (gd_tile_generic.hpp)
+//        gd_tile_kernel        every tile, when the fast kernel is off or the record
+//                              arrays are not aligned for its vector loads
+//        gd_tile_sums_kernel   sums-only output per tile; gd_sums_stream_kernel
+//                              (gd_sums_stream.hpp) streams the records instead
+//        gd_ltile2_kernel      the long-read path, from the deletion lists that
+//                              gd_dels_raw_kernel builds (gd_chunk.hpp)
+//        gd_expand_scatter_kernel + gd_scan_kernel   the scatter path (gd_scatter.hpp)
+//      All share the phases: (A) +1/-1 marks per counted interval in an int32 LDS
+//      difference array (order independent => bit exact); (B) each wave64 scans its
+//      quarter of the tile in rows of 256 positions with DPP scans, streams int32x4
+//      per lane to HBM (the only large HBM stream) and, in the same registers,
+//      reduces per-window int64 sum / int32 min and detects coverage-class
+//      boundaries; (C) tiles with class boundaries compact them from an LDS bitmap
+//      into a global chunk.
+//   K2 gd_runs_order_kernel   orders the per-tile chunks.
+//   K3 gd_region_* / gd_regions_* kernels   --bed mode reductions over the resident
+//                                           per-base vector.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -36,6 +41,20 @@
 namespace gd {
 
 constexpr int WAVE = 64;
+
+// The one tile shape that is built (8192 positions and 512 threads were measured slower on every workload and
+// retired).  Kernels and device functions that depend on it say `using namespace shape;`.
+namespace shape {
+constexpr int T = 4096;                // reference positions per tile
+constexpr int NT = 256;                // threads of a tile's workgroup
+constexpr int NW = NT / WAVE;          // 4 waves
+constexpr int CHUNK = T / NW;          // 1024 positions per wave
+constexpr int ROWS = CHUNK / 256;      // 4 rows of 256 positions per wave
+constexpr int NWORDS = T / 32;         // words of a bitmap with one bit per position
+static_assert(CHUNK % 256 == 0, "wave chunk must be whole rows");
+static_assert(ROWS == 4, "scan4 interleaves exactly four rows");
+}  // namespace shape
+
 constexpr int SUPER = 1024;   // tiles per ordering group (one workgroup of gd_runs_order_kernel)
 
 // One contig as the device sees it.
@@ -61,7 +80,6 @@ struct ContigDev {
     const uint2*    dl;       // deletion lists {start, length}
     const uint32_t* pck;      // tile indexes: deletions starting before every 4096-base boundary a read spans
     const uint32_t* ndel;     // deletions of every read (the tile kernel bisects the list of a read without an index)
-    const uint32_t* rec;      // (unused since round 5: the record words of canonical records) always null
     const uint32_t* pidx;     // position index: first read with pos >= 64 k (gd_pidx_kernel, or gd_index_records_kernel as the
                               // records arrived); null: search `pos`
     uint32_t pidx_last;       // entries above this one read as n_reads (an index built block by block has no tail)
@@ -100,10 +118,10 @@ struct __attribute__((aligned(16))) TileInfo {
 // nrd == 0xffffffff: the tile is on the slow list (job.tiles[0 .. n_slow)) instead.
 struct __attribute__((aligned(16))) TileFast {
     const int32_t*  pos;      // at read lo
-    const uint32_t* rec;      // record words (flag | MAPQ | op count), at read lo; fast == 2: the CSR offsets, at read lo
+    const uint32_t* off;      // the CSR offsets, at read lo (entry nrd, the end of the last read, is read too)
     const uint32_t* cig;      // the ops as they arrived, at op clo
-    const uint16_t* flag;     // fast == 2: at read lo
-    const uint8_t*  mapq;     // fast == 2: at read lo
+    const uint16_t* flag;     // at read lo
+    const uint8_t*  mapq;     // at read lo
     int32_t*  out;            // per-base output at t0 (null: windows-only)
     int64_t*  wsum;           // the contig's window sums
     int32_t*  wmin;
@@ -119,6 +137,8 @@ struct __attribute__((aligned(16))) TileFast {
 };
 constexpr int FAST_BIG = 0x3fffffff;
 constexpr int FAST_FAR = FAST_BIG - 65536;
+constexpr int FAST_CQ = 1280;             // ops of an ordinary tile: gd_tile_fast_kernel's staging area (1024 would put 1-2 % of
+                                          // a 30x genome's tiles on the slow list)
 
 // Device-side counters, read back once per gd_compute.
 struct Counters {
@@ -153,15 +173,14 @@ struct Job {
     int32_t   maxmean;
     uint32_t  flag_mask;
     int32_t   lookback;
-    int32_t   reserved0;
     int64_t   step;
     uint32_t  n_units;        // scatter path: 64-read units over all contigs
     uint32_t  n_groups;       // sums-only stream: 4096-read units over all contigs
     unsigned long long* tile_status;   // scatter path: look-back status word per tile
     uint32_t  w_magic, w_shift;   // floor(x / W)    = (x * w_magic) >> w_shift for x < 2^31
     uint32_t  s_magic, s_shift;   // floor(x / step) likewise (step clamped to 2^31-1)
-    uint32_t  fast;               // 1: ordinary tiles get a TileFast record, the rest go to the slow list;
-                                  // 2: the same over the records as they arrived (gd_tile_fast_kernel<ST, true>)
+    uint32_t  fast;               // nonzero: ordinary tiles get a TileFast record (gd_tile_fast_kernel), the rest go
+                                  // to the slow list (gd_tile_slow_kernel)
     uint32_t  parity;             // which Counters::n_slow this compute uses
     TileFast* ftiles;             // n_tiles records (fast run)
 };
@@ -251,9 +270,9 @@ __device__ __forceinline__ uint32_t lower_bound_hint(const int32_t* a, uint32_t 
 // ---------------------------------------------------------------------------
 // K0: tile table + accumulator init
 // ---------------------------------------------------------------------------
-template <int T>
 __global__ void gd_prep_kernel(Job job)
 {
+    using namespace shape;
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
     for (int64_t w = gid; w < job.n_win_total; w += gsz) {
@@ -326,19 +345,18 @@ __global__ void gd_prep_kernel(Job job)
         }
         ti.lo = lo;
     }
-    if (job.fast == 2u) ti.lo &= ~3u;   // the raw straight-line kernel loads four reads per lane with aligned vector loads
+    if (job.fast) ti.lo &= ~3u;   // the straight-line kernel loads four reads per lane with aligned vector loads
     ti.clo = c.n_reads ? c.off[ti.lo] : 0u;
     ti.chi = c.n_reads ? c.off[ti.hi] : 0u;
     if (!job.fast) { job.tiles[t] = ti; return; }
     // fast run: an ordinary tile gets its resolved record; anything else joins the slow list
     TileFast tf;
     const uint32_t nrd = ti.hi - ti.lo, nst = ti.chi - ti.clo;
-    const bool ordinary = tend - ti.t0 == T && nrd <= 1024u && nst <= (job.fast == 2u ? 1280u : 1024u);
+    const bool ordinary = tend - ti.t0 == T && nrd <= 1024u && nst <= (uint32_t)FAST_CQ;
     tf.nrd = 0xffffffffu;
     if (ordinary) {
         tf.pos = c.pos + ti.lo; tf.cig = c.cigar + ti.clo;
-        if (job.fast == 2u) { tf.rec = c.off + ti.lo; tf.flag = c.flag + ti.lo; tf.mapq = c.mapq + ti.lo; }
-        else { tf.rec = c.rec + ti.lo; tf.flag = nullptr; tf.mapq = nullptr; }
+        tf.off = c.off + ti.lo; tf.flag = c.flag + ti.lo; tf.mapq = c.mapq + ti.lo;
         tf.out = job.perbase ? job.perbase + c.base_off + ti.t0 : nullptr;
         tf.wsum = job.win_sum + c.win_off;
         tf.wmin = job.win_min + c.win_off;

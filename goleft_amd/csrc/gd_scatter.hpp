@@ -166,15 +166,10 @@ __global__ __launch_bounds__(256) void gd_expand_scatter_kernel(Job job)
 }
 
 // LK2: difference array -> depth in place, windows, class boundaries.
-template <int T, int NT>
-__global__ __launch_bounds__(NT) void gd_scan_kernel(Job job)
+__global__ __launch_bounds__(shape::NT) void gd_scan_kernel(Job job)
 {
-    constexpr int NW = NT / WAVE;
-    constexpr int CHUNK = T / NW;
-    constexpr int ROWS = CHUNK / 256;
-    constexpr int NWORDS = T / 32;
+    using namespace shape;
     constexpr unsigned long long ST_AGG = 1ull << 32, ST_INC = 2ull << 32;
-    static_assert(CHUNK % 256 == 0, "wave chunk must be whole rows");
 
     __shared__ __attribute__((aligned(16))) int32_t s_diffp[T + 4];
     __shared__ uint32_t s_bmap[NWORDS];
@@ -307,12 +302,12 @@ __global__ __launch_bounds__(NT) void gd_scan_kernel(Job job)
         B.carry = carry;
         // depth inside the tile <= prefix + sum of positive differences
         const bool wide = (long long)prefix + rise >= (1 << 22);
-        if (tlen == T && !wide) phase_b_rows<ROWS, true, false, 0>(B);
-        else                    phase_b_rows<ROWS, false, true, 0>(B);
+        if (tlen == T && !wide) phase_b_rows<true, false, 0>(B);
+        else                    phase_b_rows<false, true, 0>(B);
     }
     __syncthreads();
 
-    phase_c<T, NT>(job, tile, t0, lo, tid, lane, wv, s_bmap, s_clo, s_chi, s_wcnt, &s_hasb, &s_base);
+    phase_c(job, tile, t0, lo, tid, lane, wv, s_bmap, s_clo, s_chi, s_wcnt, &s_hasb, &s_base);
 }
 
 }  // namespace gd

@@ -1,10 +1,10 @@
 // gd_tile_common.hpp -- what the tile kernels of the per-base depth engine share: buffer descriptors,
-// wavefront primitives, the generic CIGAR walk, the generic (any tile shape, clipped tiles, any depth,
-// any window size) phase B and phase C.
+// wavefront primitives, the generic CIGAR walk, the generic (clipped tiles, any depth, any window size)
+// phase B and phase C.
 //
-// One workgroup (NT threads, NW = NT/64 waves) handles one tile of T reference positions.  Replaces, for
-// the reads of one tile, the per-read CIGAR walk and per-position counting that `samtools depth`
-// performs (/root/reference/depth/depth.go:45) and the per-line window / class reductions of the
+// One workgroup (shape::NT threads, shape::NW waves) handles one tile of shape::T reference positions.  Replaces,
+// for the reads of one tile, the per-read CIGAR walk and per-position counting that `samtools depth`
+// performs (the reference's depth/depth.go:45) and the per-line window / class reductions of the
 // callback (depth/depth.go:293-323).
 //
 //   * record fields come through raw buffer loads: the descriptors are bound to the tile's read range
@@ -153,9 +153,10 @@ struct PhaseB {
 //   FULL  every position of the tile is inside the contig (no masking)
 //   WIDE  depths may reach 2^22: 64-bit window accumulation everywhere
 //   ST    per-base stores: 0 plain, 1 non-temporal, 2 none (windows-only output)
-template <int ROWS, bool FULL, bool WIDE, int ST>
+template <bool FULL, bool WIDE, int ST>
 __device__ __forceinline__ void phase_b_rows(const PhaseB& B)
 {
+    using namespace shape;
     constexpr int BIG = 0x3fffffff;
     typedef typename std::conditional<WIDE, unsigned long long, uint32_t>::type acc_t;
     const int lane = B.lane, t0 = B.t0, tlen = B.tlen, chunk0 = B.chunk0;
@@ -343,14 +344,12 @@ __device__ __forceinline__ void phase_b_rows(const PhaseB& B)
 // chunk allocated with one global atomicAdd and add their count to the
 // per-SUPER-tiles group counter (ordering happens in gd_runs_order_kernel).
 // Must be called by every thread of the workgroup after a barrier.
-template <int T, int NT>
 __device__ __forceinline__ void phase_c(const Job& job, int tile, int32_t t0, int ctg, int tid, int lane,
                                         int wv, const uint32_t* s_bmap, const uint32_t* s_clo,
                                         const uint32_t* s_chi, uint32_t* s_wcnt, const uint32_t* s_hasb,
                                         uint32_t* s_base)
 {
-    constexpr int NW = NT / WAVE;
-    constexpr int NWORDS = T / 32;
+    using namespace shape;
     if (*s_hasb == 0) {
         if (tid == 0) { job.tile_cnt[tile] = 0; job.tile_off[tile] = 0; }
         return;

@@ -9,9 +9,8 @@
 // SALU wave-instructions per wave and tile, 5 workgroups per CU).  What is different here:
 //   * it reads the records AS THEY ARRIVED (pos, flag, MAPQ, CSR offsets, BAM-encoded ops in any form) -- nothing
 //     derived has to exist before the first gd_compute: a `goleft depth` run computes every input exactly once, so
-//     a pass that rewrites the records first costs more than it saves (rounds 2-4 kept such a pass, "canonical
-//     records", as an option; round 5 removed it).  A lane's four reads bring their CSR offsets (no prefix sum
-//     over op counts), flag and MAPQ come as one 8-byte and one 4-byte load per lane, reads of ONE OR TWO ops of
+//     a pass that rewrites the records first costs more than it saves.  A lane's four reads bring their CSR offsets (no
+//     prefix sum over op counts), flag and MAPQ come as one 8-byte and one 4-byte load per lane, reads of ONE OR TWO ops of
 //     any kind (150M, 20S130M, 100M50S, 5H145M ... 97 % of short reads) are one interval computed inline: no op
 //     decode loop, no zero-length / non-M special cases;
 //   * everything longer goes to ONE workgroup queue (an LDS counter, one atomic per wave that has any) and is
@@ -35,15 +34,10 @@
 namespace gd {
 namespace fast {
 
-constexpr int T = 4096;
-constexpr int NT = 256;
-constexpr int NW = NT / WAVE;          // 4 waves
-constexpr int CHUNK = T / NW;          // 1024 positions per wave
-constexpr int ROWS = CHUNK / 256;      // 4 rows of 256 positions per wave
-constexpr int CQ = 1280;               // staged ops (1024 would put 1-2 % of a 30x genome's tiles on the slow list)
+using namespace shape;
+constexpr int CQ = FAST_CQ;            // staged ops
 constexpr int U = 4;                   // reads per lane
 constexpr int QCAP = 120;              // queued multi-op reads per tile (more: walked in place); 23 004 bytes of LDS = seven workgroups per CU at any allocation granularity up to 512
-constexpr int NWORDS = T / 32;
 
 // ST: per-base stores 0 plain, 1 non-temporal, 2 none (windows-only output).
 template <int ST>
@@ -73,12 +67,12 @@ __global__ __launch_bounds__(NT) void gd_tile_fast_kernel(Job job)
     // indexed by the wave number below and end up in scratch memory
     const TileFast* __restrict__ const tp = job.ftiles + tile;
     struct {
-        const int32_t* pos; const uint32_t* rec; const uint32_t* cig; const uint16_t* flag; const uint8_t* mapq;
+        const int32_t* pos; const uint32_t* off; const uint32_t* cig; const uint16_t* flag; const uint8_t* mapq;
         int32_t* out; int64_t* wsum; int32_t* wmin; int32_t t0; uint32_t nrd, nst, clo; int32_t ctg;
     } tf;
     tf.nrd = tp->nrd;
     if ((int32_t)tf.nrd < 0) return;                   // on the slow list
-    tf.pos = tp->pos; tf.rec = tp->rec; tf.cig = tp->cig;
+    tf.pos = tp->pos; tf.off = tp->off; tf.cig = tp->cig;
     tf.flag = tp->flag; tf.mapq = tp->mapq; tf.clo = tp->clo;
     tf.out = tp->out; tf.wsum = tp->wsum; tf.wmin = tp->wmin;
     tf.t0 = tp->t0; tf.nst = tp->nst; tf.ctg = tp->ctg;
@@ -95,19 +89,19 @@ __global__ __launch_bounds__(NT) void gd_tile_fast_kernel(Job job)
     // i.e. no ops => dropped.
     const uint32_t nrd = tf.nrd;
     const rsrc_t r_pos = make_rsrc(tf.pos, nrd * 4u);
-    // tf.rec points at the CSR offsets of the tile's first read; entry nrd (the end of the last read) is read too
-    const rsrc_t r_rec = make_rsrc(tf.rec, (nrd != 0u ? nrd + 1u : nrd) * 4u);   // (no reads: no array either)
+    // tf.off points at the CSR offsets of the tile's first read; entry nrd (the end of the last read) is read too
+    const rsrc_t r_off = make_rsrc(tf.off, (nrd != 0u ? nrd + 1u : nrd) * 4u);   // (no reads: no array either)
     const rsrc_t r_cig = make_rsrc(tf.cig, tf.nst * 4u);
     const int tid4 = tid * 4;
     typedef unsigned int v4u __attribute__((ext_vector_type(4)));
     typedef unsigned int v2u __attribute__((ext_vector_type(2)));
     const v4u pv = __builtin_amdgcn_raw_buffer_load_b128(r_pos, tid * 16, 0, GD_LOAD_AUX);
-    const v4u rv = __builtin_amdgcn_raw_buffer_load_b128(r_rec, tid * 16, 0, GD_LOAD_AUX);
+    const v4u rv = __builtin_amdgcn_raw_buffer_load_b128(r_off, tid * 16, 0, GD_LOAD_AUX);
     // flag: four 16-bit values, MAPQ: four bytes per lane.  The ranges are rounded up to whole dwords (the range
     // check is per dword): at most 2 / 3 bytes past the tile's last read, inside the same aligned word.
     const rsrc_t r_flag = make_rsrc(tf.flag, ((nrd + 1u) & ~1u) * 2u);
     const rsrc_t r_mapq = make_rsrc(tf.mapq, (nrd + 3u) & ~3u);
-    const uint32_t o4 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r_rec, tid * 16 + 16, 0, GD_LOAD_AUX);
+    const uint32_t o4 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r_off, tid * 16 + 16, 0, GD_LOAD_AUX);
     const v2u fv = __builtin_amdgcn_raw_buffer_load_b64(r_flag, tid * 8, 0, GD_LOAD_AUX);
     const uint32_t mv = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r_mapq, tid4, 0, GD_LOAD_AUX);
     uint32_t cgv[CQN / NT];
@@ -124,14 +118,14 @@ __global__ __launch_bounds__(NT) void gd_tile_fast_kernel(Job job)
         if (tid == 0) { d4[T / 4] = z; s_qn = 0; s_hasb = 0; }
     }
     // ---- where each read's ops are: the CSR offsets say it
-    const uint32_t rec[U] = {rv.x, rv.y, rv.z, rv.w};
+    const uint32_t o0[U] = {rv.x, rv.y, rv.z, rv.w};
     uint32_t n[U], ex[U];                               // op count, staged index of the read's first op
     {
         const uint32_t oe[U] = {rv.y, rv.z, rv.w, o4};
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            n[u] = (uint32_t)(tid4 + u) < nrd ? oe[u] - rec[u] : 0u;
-            ex[u] = rec[u] - tf.clo;
+            n[u] = (uint32_t)(tid4 + u) < nrd ? oe[u] - o0[u] : 0u;
+            ex[u] = o0[u] - tf.clo;
         }
     }
     // stage the ops
@@ -451,7 +445,7 @@ __global__ __launch_bounds__(NT) void gd_tile_fast_kernel(Job job)
     __syncthreads();
 
     // ---- phase C: compact class boundaries of this tile -------------------------------------------
-    phase_c<T, NT>(job, tile, tf.t0, tf.ctg, tid, lane, wv, s_bmap, s_clo, s_chi, s_wcnt, &s_hasb, &s_base);
+    phase_c(job, tile, tf.t0, tf.ctg, tid, lane, wv, s_bmap, s_clo, s_chi, s_wcnt, &s_hasb, &s_base);
 }
 
 }  // namespace fast

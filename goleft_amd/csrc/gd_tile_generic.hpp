@@ -1,11 +1,10 @@
-// gd_tile_generic.hpp -- K1, the generic tile kernel (short-read path): any tile shape (T, NT), tiles
-// clipped at a contig end, tiles deeper than one batch of reads, CIGARs in any form,
-// any window size.  It runs every tile when the straight-line kernel is switched off
+// gd_tile_generic.hpp -- K1, the generic tile kernel (short-read path): tiles clipped at a contig end,
+// tiles deeper than one batch of reads, CIGARs in any form, any window size.  It runs every tile when the straight-line kernel is switched off
 // (GD_OPT_FAST_KERNEL = 0), the tiles gd_prep_kernel lists as `slow` otherwise, and -- as
 // gd_tile_sums_kernel -- the sums-only output.  Same algorithm and results as gd_tile_fast.hpp: phase A
 // marks +1/-1 per counted interval in an LDS difference array, phase B scans, stores and reduces,
 // phase C compacts class boundaries; it replaces the per-read CIGAR walk of `samtools depth`
-// (/root/reference/depth/depth.go:45) and the per-line window / class reductions of the callback
+// (the reference's depth/depth.go:45) and the per-line window / class reductions of the callback
 // (depth/depth.go:293-323).
 //
 //   * phase A is branch-free up to the LDS atomics: the record filter is mask arithmetic, the first
@@ -79,11 +78,12 @@ __device__ __forceinline__ uint32_t walk_cigar_sums(OpPtr ops, uint32_t n, int p
 
 // Phase A for one wave, U = 4 reads per lane and batch of NT*4.  SUMS: intervals go to a SumSink
 // (window accumulators) instead of +1/-1 marks.
-template <int NT, bool STAGED, bool SUMS = false>
+template <bool STAGED, bool SUMS = false>
 __device__ __forceinline__ uint32_t phase_a(const PhaseA& A, int32_t (&p)[4], uint32_t (&f)[4],
                                             uint32_t (&mq)[4], uint32_t (&o0)[4], uint32_t (&o1)[4],
                                             const SumSink* sink = nullptr)
 {
+    using namespace shape;
     constexpr int U = 4;
     const int tid = A.tid, lane = A.lane;
     const int tid4 = tid * 4, tid2 = tid * 2;
@@ -224,7 +224,7 @@ __device__ __forceinline__ uint32_t phase_a(const PhaseA& A, int32_t (&p)[4], ui
 
 // Phase B pass 2 for one wave on the fast configuration: every position of the
 // tile inside the contig, depths below 2^22 (32-bit window accumulation is
-// exact).  Other tiles take gd_tile_v6.hpp's generic phase_b_rows.
+// exact).  Other tiles take gd_tile_common.hpp's generic phase_b_rows.
 //   ST    per-base stores: 0 plain, 1 non-temporal, 2 none (windows-only output)
 // The rows of a wave's quarter after their scans: what phase_b_scan leaves in registers for phase_b_finish.
 struct PhaseBRows {
@@ -235,10 +235,9 @@ struct PhaseBRows {
 // First half: load the wave's four rows of 256 positions and run the four wave scans.  Returns the quarter's
 // total (wave uniform): a kernel without a separate totals pass publishes it, waits for the other waves and
 // passes the carry to phase_b_finish in B.carry.
-template <int ROWS>
 __device__ __forceinline__ int phase_b_scan(const PhaseB& B, PhaseBRows& R)
 {
-    static_assert(ROWS == 4, "scan4 interleaves exactly four rows");
+    using namespace shape;
 #pragma unroll
     for (int r = 0; r < ROWS; ++r)
         R.v[r] = *reinterpret_cast<const int4*>(&B.s_diff[B.chunk0 + r * 256 + B.lane * 4]);
@@ -254,23 +253,24 @@ __device__ __forceinline__ int phase_b_scan(const PhaseB& B, PhaseBRows& R)
     return tot;
 }
 
-template <int ROWS, int ST>
+template <int ST>
 __device__ __forceinline__ void phase_b_finish(const PhaseB& B, const PhaseBRows& R, uint32_t w_magic, uint32_t w_shift,
                                                uint32_t s_magic, uint32_t s_shift);
 
-template <int ROWS, int ST>
+template <int ST>
 __device__ __forceinline__ void phase_b_rows_full(const PhaseB& B, uint32_t w_magic, uint32_t w_shift,
                                              uint32_t s_magic, uint32_t s_shift)
 {
     PhaseBRows R;
-    (void)phase_b_scan<ROWS>(B, R);
-    phase_b_finish<ROWS, ST>(B, R, w_magic, w_shift, s_magic, s_shift);
+    (void)phase_b_scan(B, R);
+    phase_b_finish<ST>(B, R, w_magic, w_shift, s_magic, s_shift);
 }
 
-template <int ROWS, int ST>
+template <int ST>
 __device__ __forceinline__ void phase_b_finish(const PhaseB& B, const PhaseBRows& R, uint32_t w_magic, uint32_t w_shift,
                                                uint32_t s_magic, uint32_t s_shift)
 {
+    using namespace shape;
     constexpr int BIG = 0x3fffffff;
     constexpr int FAR = BIG - 65536;                     // anything at or past this is "never"
     const int lane = B.lane, t0 = B.t0, chunk0 = B.chunk0;
@@ -473,17 +473,13 @@ __device__ __forceinline__ void phase_b_finish(const PhaseB& B, const PhaseBRows
 
 // One tile.  OPT: per-base stores 0 plain, 1 non-temporal, 2 none (gd_set_outputs without GD_OUT_PERBASE).
 // Called by every thread of the workgroup.
-template <int T, int NT, int OPT>
+template <int OPT>
 __device__ __forceinline__ void tile_body(const Job& job, const TileInfo& ti, const int tile)
 {
-    constexpr int NW = NT / WAVE;          // waves per workgroup
-    constexpr int CHUNK = T / NW;          // positions per wave
-    constexpr int ROWS = CHUNK / 256;      // rows of 256 positions per wave
-    constexpr int NWORDS = T / 32;         // bitmap words
+    using namespace shape;
     constexpr int CQ = (T * 3) / 8;        // staged CIGAR ops (30x/150 bp needs ~T/4)
     constexpr int U = 4;                   // reads per lane in flight
     constexpr int CCH = (CQ + NT - 1) / NT;   // staged ops per thread
-    static_assert(CHUNK % 256 == 0, "wave chunk must be whole rows");
 
     __shared__ __attribute__((aligned(16))) int32_t s_diffp[T + 4];  // [3] = index -1
     __shared__ uint32_t s_bmap[NWORDS];    // boundary bit per position
@@ -557,8 +553,8 @@ __device__ __forceinline__ void tile_body(const Job& job, const TileInfo& ti, co
         A.gcig = ti.cigar; A.clo = ti.clo; A.nrd = nrd;
         A.neg4t0 = (int)(0u - ((uint32_t)t0 << 2));       // (p<<2) + neg4t0 = 4*(p - t0)
         A.T4 = T4; A.flag_mask = job.flag_mask; A.Q = job.Q; A.tid = tid; A.lane = lane;
-        const uint32_t smax = staged ? phase_a<NT, true>(A, p, f, mq, o0, o1)
-                                     : phase_a<NT, false>(A, p, f, mq, o0, o1);
+        const uint32_t smax = staged ? phase_a<true>(A, p, f, mq, o0, o1)
+                                     : phase_a<false>(A, p, f, mq, o0, o1);
         // publish the largest span seen
         publish_span(&job.counters->max_span, smax, seen0, lane);
     }
@@ -594,23 +590,18 @@ __device__ __forceinline__ void tile_body(const Job& job, const TileInfo& ti, co
         // depth <= reads examined for the tile: below 2^22 the 32-bit window
         // accumulation is exact (1024 positions x depth < 2^32)
         const bool wide = nrd >= (1u << 22);
-        if constexpr (ROWS == 4) {
-            if (tlen == T && !wide) phase_b_rows_full<ROWS, OPT>(B, job.w_magic, job.w_shift, job.s_magic, job.s_shift);
-            else                    phase_b_rows<ROWS, false, true, OPT>(B);   // clipped or very deep tiles
-        } else {
-            if (tlen == T && !wide) phase_b_rows<ROWS, true, false, OPT>(B);   // other tile shapes: row by row
-            else                    phase_b_rows<ROWS, false, true, OPT>(B);
-        }
+        if (tlen == T && !wide) phase_b_rows_full<OPT>(B, job.w_magic, job.w_shift, job.s_magic, job.s_shift);
+        else                    phase_b_rows<false, true, OPT>(B);   // clipped or very deep tiles
     }
     __syncthreads();
 
     // ---- phase C: compact class boundaries of this tile -------------------
-    phase_c<T, NT>(job, tile, t0, ti.ctg, tid, lane, wv, s_bmap, s_clo, s_chi, s_wcnt, &s_hasb, &s_base);
+    phase_c(job, tile, t0, ti.ctg, tid, lane, wv, s_bmap, s_clo, s_chi, s_wcnt, &s_hasb, &s_base);
 }
 
 // Every tile, one workgroup each (GD_OPT_FAST_KERNEL = 0, or contig arrays the straight-line kernel's vector loads cannot take).
-template <int T, int NT, int OPT>
-__global__ __launch_bounds__(NT) void gd_tile_kernel(Job job)
+template <int OPT>
+__global__ __launch_bounds__(shape::NT) void gd_tile_kernel(Job job)
 {
     // XCD-aware order: workgroup b runs on XCD b % 8; every XCD gets a contiguous
     // eighth of the genome so the look-back reads of neighbouring tiles hit the same L2.
@@ -618,18 +609,18 @@ __global__ __launch_bounds__(NT) void gd_tile_kernel(Job job)
     const int tile = (int)(blockIdx.x & 7u) * per + (int)(blockIdx.x >> 3);
     if (tile >= job.n_tiles) return;
     const TileInfo ti = job.tiles[tile];
-    tile_body<T, NT, OPT>(job, ti, tile);
+    tile_body<OPT>(job, ti, tile);
 }
 
 // The `slow` tiles of a fast run: gd_prep_kernel compacted their descriptors to the front of job.tiles
 // (tile id in TileInfo::tile) and counted them in Counters::n_slow[job.parity]; a fixed grid strides over the list.
-template <int T, int NT, int OPT>
-__global__ __launch_bounds__(NT) void gd_tile_slow_kernel(Job job)
+template <int OPT>
+__global__ __launch_bounds__(shape::NT) void gd_tile_slow_kernel(Job job)
 {
     const uint32_t n = __hip_atomic_load(&job.counters->n_slow[job.parity], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
         const TileInfo ti = job.tiles[i];
-        tile_body<T, NT, OPT>(job, ti, ti.tile);
+        tile_body<OPT>(job, ti, ti.tile);
         __syncthreads();                       // the next tile reuses the LDS arrays
     }
 }
@@ -637,10 +628,9 @@ __global__ __launch_bounds__(NT) void gd_tile_slow_kernel(Job job)
 
 // K1s: the tile kernel for GD_OUT_SUMS_ONLY.  Same read selection, filter, staging and look-back
 // verification as gd_tile_kernel; phase A feeds window accumulators, phases B and C do not exist.
-template <int T, int NT>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void gd_tile_sums_kernel(Job job)
+__global__ __launch_bounds__(shape::NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void gd_tile_sums_kernel(Job job)
 {
-    constexpr int NW = NT / WAVE;
+    using namespace shape;
     constexpr int CQ = (T * 3) / 8;
     constexpr int U = 4;
     constexpr int CCH = (CQ + NT - 1) / NT;
@@ -704,8 +694,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         A.gcig = ti.cigar; A.clo = ti.clo; A.nrd = nrd;
         A.neg4t0 = (int)(0u - ((uint32_t)t0 << 2));
         A.T4 = tlen * 4; A.flag_mask = job.flag_mask; A.Q = job.Q; A.tid = tid; A.lane = lane;
-        const uint32_t smax = staged ? phase_a<NT, true, true>(A, p, f, mq, o0, o1, &S)
-                                     : phase_a<NT, false, true>(A, p, f, mq, o0, o1, &S);
+        const uint32_t smax = staged ? phase_a<true, true>(A, p, f, mq, o0, o1, &S)
+                                     : phase_a<false, true>(A, p, f, mq, o0, o1, &S);
         publish_span(&job.counters->max_span, smax, seen0, lane);
     }
     __syncthreads();

@@ -64,6 +64,30 @@ def test_deletions_that_outnumber_their_slots():
     check(reads_of(reads, [100, 150, 200, 900, 1000, 1500, 5000]), 20_000)
 
 
+def test_slots_that_overflow_late_in_the_wave_walk():
+    """The wave walk takes a read's ops in batches of 256 and gives up at the first batch that would pass the read's slots:
+    here the first three batches (768 ops of M I pairs, which cross tile boundaries) succeed and have written list and
+    index entries when the run of single-base deletions behind them outgrows the slots.  The merging walk starts the
+    read again over what they wrote; the ordinary long reads directly before and after it own the neighbouring slots."""
+    ordinary = cg((M, 20), (D, 1), (M, 20), (I, 1)) * 100 + cg((M, 5))
+    late = cg((M, 20), (I, 1)) * 500 + cg((D, 1)) * 1300 + cg((M, 30))
+    reads = [ordinary, late, ordinary]
+    o0, n = len(ordinary), len(late)
+    cap = ((o0 + n) >> 1) - (o0 >> 1) + 1                                           # gd_dels_raw_kernel's slot formula
+    dn = np.cumsum([(x & 15) in (D, N) for x in late])
+    assert n > 24 and dn[767] <= cap < dn[-1], (n, cap, int(dn[767]), int(dn[-1]))
+    check(reads_of(reads, [100, 2000, 2500]), 20_000)
+
+
+def test_a_skip_too_long_for_the_wave_walk():
+    """An op above 2^22 bases ends both wave walks whatever the slots hold (their prefix sums stay below 2^30): a read
+    of more than 24 ops with one such skip, deletions on both sides of it, is walked by its own lane."""
+    ordinary = cg((M, 20), (D, 1), (M, 20), (I, 1)) * 100 + cg((M, 5))
+    skip = cg((M, 30), (D, 2)) * 20 + cg((N, (1 << 22) + 1)) + cg((M, 30), (D, 2)) * 20 + cg((M, 10))
+    assert len(skip) > 24
+    check(reads_of([ordinary, skip, ordinary], [100, 1000, 1200]), 4_300_000, W=1000)
+
+
 def test_tile_index_at_its_boundaries():
     """Entry k of a read's index = its deletions that start BEFORE boundary ((pos >> 12) + k) << 12.  Deletions that start
     exactly on a boundary, one base before and one after; a read that starts on a boundary, ends on one, ends one base

@@ -52,7 +52,7 @@ def test_tile_kernels_keep_seven_workgroups_per_cu(kernels):
 def test_streaming_and_ingest_kernels(kernels):
     for name, r in pick(kernels, "gd_sums_stream_kernel").items():
         assert r["scratch"] == 0 and r["lds"] * 6 <= LDS_PER_CU and r["vgpr"] <= 84, (name, r)     # six waves per SIMD
-    for name, r in {**pick(kernels, "gd_dels_raw_kernel"), **pick(kernels, "gd_prep_kernel<"), **pick(kernels, "gd_tile_slow_kernel<"),
+    for name, r in {**pick(kernels, "gd_dels_raw_kernel"), **pick(kernels, "gd_prep_kernel("), **pick(kernels, "gd_tile_slow_kernel<"),
                     **pick(kernels, "gd_h2d_kernel"), **pick(kernels, "gd_bam_walk_kernel<"),
                     **pick(kernels, "gd_index_records_kernel"), **pick(kernels, "gd_readback_kernel")}.items():
         assert r["scratch"] == 0, (name, r)
