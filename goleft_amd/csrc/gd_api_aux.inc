@@ -83,7 +83,7 @@ int gd_depthwed(gd_ctx* c, int n_samples, int n_ctg, const int32_t* tids, int64_
 int gd_depthwed_device(gd_ctx* c, int n_samples, int n_ctg, const int32_t* tids, int64_t size,
                        const int64_t** d_cells, size_t* n_rows)
 {
-    if (c && c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
+    if (int r = in_flight(c)) return r;
     if (!d_cells) return GD_E_INVALID;
     int64_t* p = nullptr;
     const int r = depthwed_on_device(c, n_samples, n_ctg, tids, size, nullptr, nullptr, nullptr, 0, false, n_rows, &p);
@@ -180,7 +180,7 @@ static int md_sample_ptrs(gd_ctx* c, int n_samples, const int32_t* tids, std::ve
 int gd_md_flags(gd_ctx* c, int n_samples, const int32_t* tids, int32_t min_cov, int32_t min_samples,
                 uint32_t* any_bits, uint32_t* suf_bits, size_t n_words)
 {
-    if (c && c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
+    if (int r = in_flight(c)) return r;
     if (!c || n_samples < 1 || !tids) return GD_E_INVALID;
     if (int r = set_device(c)) return r;
     std::vector<const int32_t*> ptrs;
@@ -236,7 +236,7 @@ int gd_md_begin(gd_ctx* c, int64_t len)
 
 int gd_md_accumulate(gd_ctx* c, int n_samples, const int32_t* tids, int32_t min_cov)
 {
-    if (c && c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
+    if (int r = in_flight(c)) return r;
     if (!c || n_samples < 1 || !tids) return GD_E_INVALID;
     if (int r = set_device(c)) return r;
     if (c->md_acc_len < 0) return fail(c, GD_E_STATE, "gd_md_begin has not been called");

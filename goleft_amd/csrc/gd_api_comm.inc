@@ -122,7 +122,7 @@ int gd_comm_unique_id(void* id, size_t bytes)
 int gd_comm_init(gd_ctx* c, int rank, int world, const void* id, size_t bytes)
 {
     if (!c || !id || bytes < GD_COMM_ID_BYTES || world < 1 || rank < 0 || rank >= world) return GD_E_INVALID;
-    if (c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
+    if (int r = in_flight(c)) return r;
     if (c->comm) return fail(c, GD_E_STATE, "this context already holds a communicator (gd_comm_destroy first)");
     if (int r = set_device(c)) return r;
     Rccl* R = rccl();

@@ -70,11 +70,12 @@ static void compute_build_table(gd_ctx* c, ComputeState& S)
     }
 }
 
-// The streaming sums kernel (GD_OUT_SUMS_ONLY, gd_sums_stream.hpp) reads the records as they arrived.
-static bool wants_sums_stream(const gd_ctx* c)
+// The contigs of a job: the selected ones, else all.
+static std::vector<int32_t> selected_or_all(const gd_ctx* c)
 {
-    return c->sums_only && c->fast_kernel && c->params.window_size >= 32 &&
-           (c->path == GD_PATH_TILE || c->path == GD_PATH_AUTO);
+    std::vector<int32_t> tids = c->selected;
+    if (tids.empty()) { tids.resize(c->contigs.size()); for (size_t i = 0; i < tids.size(); ++i) tids[i] = (int32_t)i; }
+    return tids;
 }
 
 // 0 = ready to enqueue, 1 = nothing to compute (no tiles), < 0 error
@@ -95,8 +96,7 @@ static int compute_prepare(gd_ctx* c, ComputeState& S)
     c->computed = false;                                 // until compute_publish: the result arrays are about to be overwritten
 
     // ---- contig table ------------------------------------------------------
-    S.tids = c->selected;
-    if (S.tids.empty()) { S.tids.resize(c->contigs.size()); for (size_t i = 0; i < S.tids.size(); ++i) S.tids[i] = (int32_t)i; }
+    S.tids = selected_or_all(c);
     for (auto& h : c->contigs) { h.base_off = h.win_off = -1; h.n_win = 0; h.run_beg = h.run_end = 0; }
     {
         const float ck_ms = c->kernel_ms[GD_K_CKPT];     // ingest-time work
@@ -107,14 +107,14 @@ static int compute_prepare(gd_ctx* c, ComputeState& S)
     for (int32_t tid : S.tids)
         if (c->contigs[tid].length > 0) { S.n_reads += c->contigs[tid].n_reads; S.n_ops += c->contigs[tid].n_ops; }
     compute_survey(c, S);
-    compute_build_table(c, S);
+    compute_build_table(c, S);                           // (for the layout totals; the enqueue builds the table it uploads)
     if (S.tile_beg > 0x7fffffffLL) return fail(c, GD_E_RANGE, "too many tiles");
     if (S.n_units > 0xfffffff0ull) return fail(c, GD_E_RANGE, "too many records");
     c->n_tiles = S.tile_beg;
     c->n_win_total = S.win_off;
     c->n_bases = S.bases;
     c->bounds.clear();
-    c->ran_sums_only = false;                            // (what THIS compute produces; set by the enqueue)
+    S.route = GD_TK_NONE;                                // (until an enqueue decides it)
     if (c->n_tiles == 0) return 1;
     if (c->export_buf && c->n_win_total > c->export_max_w)
         return fail(c, GD_E_CAPACITY, "gd_set_export: %lld windows, the export block holds %lld",
@@ -132,7 +132,7 @@ static int compute_prepare(gd_ctx* c, ComputeState& S)
         if (int r = ensure_dev(c, &c->d_super_cnt, &c4, (size_t)c->n_tiles / gd::SUPER + 1)) return r;
         c->cap_tiles = c1;
     }
-    if (c->fast_kernel && c->path != GD_PATH_SCATTER && c->path != GD_PATH_CHUNK)    // (allocations belong here, not in the enqueue)
+    if (straight_line_allowed(c))                        // (allocations belong here, not in the enqueue)
         if (int r = ensure_dev(c, &c->d_ftiles, &c->cap_ftiles, (size_t)c->n_tiles)) return r;
     if (c->keep_perbase) {
         if (int r = ensure_dev(c, &c->d_perbase, &c->cap_perbase, (size_t)S.base_off)) return r;
@@ -172,18 +172,35 @@ static int compute_prepare(gd_ctx* c, ComputeState& S)
 
     S.reruns = 0;
     S.used_lookback = c->lookback;
-    S.used_scatter = S.used_chunk = false;
+    return GD_OK;
+}
+
+// Profiling: the record that opens the stage `id` (a GD_K_* interval of gd_kernel_ms) and closes the one before it.
+static constexpr int kStagesEnd = -1;                    // the record behind the last launch opens nothing
+static int compute_stage(gd_ctx* c, ComputeState& S, int id)
+{
+    if (!c->profiling) return GD_OK;
+    HIPCHK(c, hipEventRecord(c->ev[S.n_stages], c->stream));
+    S.stage_id[S.n_stages++] = (int8_t)id;
     return GD_OK;
 }
 
 static int compute_enqueue(gd_ctx* c, ComputeState& S)
 {
     const gd_params& P = c->params;
+    // which device algorithm and kernel (include/goleft_depth.h GD_PATH_*, GD_TK_*)
+    const int route = compute_route(c, S);
+    if (route < 0)
+        return fail(c, route, "windows-only output (gd_set_outputs without GD_OUT_PERBASE) is not "
+                              "available on the scatter path");
+    S.route = route;
+    S.n_stages = 0;
     gd::Job job{};
     job.ctgs = c->d_ctgs;
     job.n_ctgs = (int32_t)c->h_ctgs.size();
     job.n_tiles = (int32_t)c->n_tiles;
     job.tiles = c->d_tiles;
+    if (route == GD_TK_FAST_RAW) { job.fast = 1; job.ftiles = c->d_ftiles; }   // (the sums-only tile kernel reads the generic tile table)
     job.perbase = c->d_perbase;
     job.win_sum = c->d_wsum;
     job.win_min = c->d_wmin;
@@ -213,31 +230,22 @@ static int compute_enqueue(gd_ctx* c, ComputeState& S)
                                  0, sizeof(uint32_t), c->stream));
     c->slow_counter_clean = false;
 
-    // which device algorithm (include/goleft_depth.h GD_PATH_*)
-    c->ran_sums_only = false;
-    const bool scatter = c->path == GD_PATH_SCATTER;
-    const bool chunk = c->path == GD_PATH_CHUNK ||
-                       (c->path == GD_PATH_AUTO && (c->span_forces_long || S.n_ops > 6 * S.n_reads));
-    S.chunk_span = 0;
-    if (chunk) {
+    if (route == GD_TK_LONG) {
         // deletion lists, read records and tile indexes of every contig that lacks them, as ONE batch, straight from the
         // records as they arrived -- also for short-read data forced onto this path, or after a span made AUTO leave
         // the tile path.
         if (int r = ck_tids(c, S.tids)) return r;
+        S.chunk_span = 0;
         for (int32_t tid : S.tids) {
             const ContigHost& h = c->contigs[tid];
             if (h.length > 0) S.chunk_span = std::max(S.chunk_span, h.max_span);
         }
-        compute_survey(c, S);
+        // the look-back IS the largest span (exact, known since the records arrived)
+        job.lookback = std::max(64, (int32_t)((S.chunk_span + 63) & ~63));
     }
-    // The straight-line tile kernel reads the records as they arrived (no pass over the records before the first --
-    // usually the only -- compute of an input); contig arrays its vector loads cannot take: the generic kernel.
-    job.fast = !scatter && !chunk && c->fast_kernel && S.raw_aligned;
+    // compute_prepare built the table for its totals; this is the one that is uploaded: the long-read pointers in it
+    // only exist after ck_tids, and under GD_PATH_AUTO a later attempt may be the first to need them
     compute_build_table(c, S);
-    if (job.fast) {
-        if (int r = ensure_dev(c, &c->d_ftiles, &c->cap_ftiles, (size_t)c->n_tiles)) return r;
-        job.ftiles = c->d_ftiles;
-    }
     // the table only changes when records, contigs or the path change: an identical one is not uploaded again
     // (a pageable-memory upload is a blocking staging copy, ~10 us of every step)
     if (c->d_ctgs != c->up_ctgs_dev || c->up_ctgs.size() != c->h_ctgs.size() ||
@@ -248,65 +256,10 @@ static int compute_enqueue(gd_ctx* c, ComputeState& S)
         c->up_ctgs_dev = c->d_ctgs;
     }
     job.n_units = (uint32_t)S.n_units;
-    const unsigned runs_grid = (unsigned)((c->n_tiles + gd::SUPER - 1) / gd::SUPER);
-    if (scatter && !c->keep_perbase)
-        return fail(c, GD_E_INVALID, "windows-only output (gd_set_outputs without GD_OUT_PERBASE) is not "
-                                     "available on the scatter path");
-    S.it_kernel = 0;
-    if (chunk) {
-        // the look-back IS the largest span (exact, known since the records arrived)
-        job.lookback = std::max(64, (int32_t)((S.chunk_span + 63) & ~63));
-        if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-        launch_prep(c, job);
-        c->slow_counter_clean = true;
-        if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-        launch_ltile(c, job);
-        if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-        hipLaunchKernelGGL(gd::gd_runs_order_kernel, dim3(runs_grid), dim3(gd::SUPER), 0,
-                           c->stream, c->d_chunks, job.run_cap, c->d_tile_cnt, c->d_tile_off,
-                           c->d_super_cnt, c->d_ordered, (int)c->n_tiles);
-        if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-        S.it_kernel = GD_TK_LONG;
-    } else if (!scatter) {
-        // sums-only: built for the default tile shape; W < 32 (more windows per tile than the
-        // LDS accumulators hold) keeps the regular windows-only kernel
-        c->ran_sums_only = c->sums_only && P.window_size >= 32;
-        // sums-only: one streaming pass over the records, no tiles (gd_sums_stream.hpp)
-        const bool stream = c->sums_only && c->fast_kernel && S.raw_aligned && S.n_groups <= 0xfffffff0ull &&
-                            P.window_size >= 32;      // (smaller windows: the regular windows-only kernels, as documented)
-        if (stream) {
-            c->ran_sums_only = true;
-            job.fast = 0;
-            job.n_groups = (uint32_t)S.n_groups;
-            if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-            HIPCHK(c, hipMemsetAsync(c->d_wsum, 0, (size_t)c->n_win_total * sizeof(int64_t), c->stream));
-            HIPCHK(c, hipMemsetAsync(c->d_counters, 0, sizeof(gd::Counters), c->stream));
-            if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-            if (S.n_groups) {
-                    hipLaunchKernelGGL(gd::sums::gd_sums_stream_kernel, dim3((unsigned)((S.n_groups + 3) / 4)), dim3(256), 0,
-                                       c->stream, job);
-            }
-            if (c->profiling) { HIPCHK(c, hipEventRecord(c->ev[2], c->stream)); HIPCHK(c, hipEventRecord(c->ev[3], c->stream)); }
-            S.it_kernel = GD_TK_SUMS_STREAM_RAW;
-        } else {
-            if (c->ran_sums_only) job.fast = 0;              // the sums-only kernel reads the generic tile table
-            if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-            launch_prep(c, job);
-            c->slow_counter_clean = true;
-            if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-            launch_tile(c, job);
-            if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-            if (!c->ran_sums_only)                           // no class runs in sums-only mode
-                hipLaunchKernelGGL(gd::gd_runs_order_kernel, dim3(runs_grid), dim3(gd::SUPER), 0,
-                                   c->stream, c->d_chunks, job.run_cap, c->d_tile_cnt, c->d_tile_off,
-                                   c->d_super_cnt, c->d_ordered, (int)c->n_tiles);
-            if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-            S.it_kernel = c->ran_sums_only ? GD_TK_TILE_SUMS : job.fast ? GD_TK_FAST_RAW : GD_TK_GENERIC;
-        }
-    } else {
+    if (route == GD_TK_SCATTER) {
         if (int r = ensure_dev(c, &c->d_status, &c->cap_status, (size_t)c->n_tiles)) return r;
         job.tile_status = c->d_status;
-        if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+        if (int r = compute_stage(c, S, GD_K_PREP)) return r;
         // the per-base array doubles as the difference array: zero it, padding included
         HIPCHK(c, hipMemsetAsync(c->d_perbase, 0, (size_t)S.base_off * sizeof(int32_t), c->stream));
         {
@@ -314,7 +267,7 @@ static int compute_enqueue(gd_ctx* c, ComputeState& S)
             hipLaunchKernelGGL(gd::gd_linit_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0,
                                c->stream, job);
         }
-        if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+        if (int r = compute_stage(c, S, GD_K_EXPAND)) return r;
         if (S.n_units > (1ull << 26) - 64)               // one wave per 64-read unit; a launch holds fewer than 2^32 work-items
             return fail(c, GD_E_RANGE, "the scatter path takes at most 2^32 records per compute");
         if (S.n_units) {
@@ -322,15 +275,28 @@ static int compute_enqueue(gd_ctx* c, ComputeState& S)
             const unsigned grid = (unsigned)(((groups + 7) / 8) * 8);
             hipLaunchKernelGGL(gd::gd_expand_scatter_kernel, dim3(grid), dim3(256), 0, c->stream, job);
         }
-        if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
+        if (int r = compute_stage(c, S, GD_K_SCAN)) return r;
         hipLaunchKernelGGL(gd::gd_scan_kernel, dim3((unsigned)c->n_tiles), dim3(gd::shape::NT), 0, c->stream, job);
-        if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-        hipLaunchKernelGGL(gd::gd_runs_order_kernel, dim3(runs_grid), dim3(gd::SUPER), 0,
-                           c->stream, c->d_chunks, job.run_cap, c->d_tile_cnt, c->d_tile_off,
-                           c->d_super_cnt, c->d_ordered, (int)c->n_tiles);
-        if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-        S.it_kernel = GD_TK_SCATTER;
+    } else if (route == GD_TK_SUMS_STREAM_RAW) {
+        job.n_groups = (uint32_t)S.n_groups;
+        if (int r = compute_stage(c, S, GD_K_PREP)) return r;
+        HIPCHK(c, hipMemsetAsync(c->d_wsum, 0, (size_t)c->n_win_total * sizeof(int64_t), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_counters, 0, sizeof(gd::Counters), c->stream));
+        if (int r = compute_stage(c, S, GD_K_TILE)) return r;
+        if (S.n_groups)
+            hipLaunchKernelGGL(gd::sums::gd_sums_stream_kernel, dim3((unsigned)((S.n_groups + 3) / 4)), dim3(256), 0,
+                               c->stream, job);
+    } else {
+        if (int r = compute_stage(c, S, GD_K_PREP)) return r;
+        launch_prep(c, job);
+        c->slow_counter_clean = true;
+        if (int r = compute_stage(c, S, GD_K_TILE)) return r;
+        if (route == GD_TK_LONG) launch_ltile(c, job);
+        else launch_tile(c, job, route);
     }
+    if (int r = compute_stage(c, S, GD_K_RUNS)) return r;
+    if (!route_sums_only(route)) launch_runs_order(c, job);   // (no class runs in sums-only mode: an empty stage)
+    if (int r = compute_stage(c, S, kStagesEnd)) return r;
     if (c->export_buf) {                                     // (its window capacity was checked before anything was launched)
         // the last gather may still be reading this very block (a host that does not alternate two export buffers):
         // the export waits for it -- with two buffers the pointers differ and nothing waits (ADVICE round 4)
@@ -348,22 +314,18 @@ static int compute_enqueue(gd_ctx* c, ComputeState& S)
     // link, so that one synchronisation serves both.  Two hipMemcpyAsync did the same through the runtime's copy path,
     // whose first use behind running kernels cost the first gd_compute of a process 1.3 - 13 ms inside the enqueue
     // (measured box to box), and every later one two copy commands.
-    const size_t spec = std::min(kSpecBounds, c->cap_runs);
-    hipLaunchKernelGGL(gd::gd_readback_kernel, dim3(1), dim3(256), 0, c->stream, c->d_counters, c->d_ordered, (uint32_t)spec,
+    S.spec = std::min(kSpecBounds, c->cap_runs);
+    hipLaunchKernelGGL(gd::gd_readback_kernel, dim3(1), dim3(256), 0, c->stream, c->d_counters, c->d_ordered, (uint32_t)S.spec,
                        c->h_counters, c->h_bounds);
     HIPCHK(c, hipGetLastError());
-    S.it_scatter = scatter; S.it_chunk = chunk; S.spec = spec;
     return GD_OK;
 }
 
 // 0 = done, 1 = enqueue again (look-back / path / capacity), < 0 error
 static int compute_complete(gd_ctx* c, ComputeState& S)
 {
-    const bool scatter = S.it_scatter, chunk = S.it_chunk;
-    const size_t spec = S.spec;
+    const bool scatter = S.route == GD_TK_SCATTER, chunk = S.route == GD_TK_LONG;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    S.used_scatter = scatter;
-    S.used_chunk = chunk;
 
     const gd::Counters k = *c->h_counters;
     if (chunk) {
@@ -409,7 +371,7 @@ static int compute_complete(gd_ctx* c, ComputeState& S)
     }
     // ---- ordered boundaries to the host (small) -------------------------
     c->bounds.resize(k.run_cursor);
-    if (k.run_cursor && (size_t)k.run_cursor <= spec)
+    if (k.run_cursor && (size_t)k.run_cursor <= S.spec)
         memcpy(c->bounds.data(), c->h_bounds, (size_t)k.run_cursor * sizeof(int2));
     else if (k.run_cursor)
         HIPCHK(c, hipMemcpy(c->bounds.data(), c->d_ordered, (size_t)k.run_cursor * sizeof(int2), hipMemcpyDeviceToHost));
@@ -418,26 +380,8 @@ static int compute_complete(gd_ctx* c, ComputeState& S)
 
 static int compute_publish(gd_ctx* c, ComputeState& S)
 {
-    if (c->profiling) {
-        auto ms = [&](int a, int b, float* out) -> int {
-            HIPCHK(c, hipEventElapsedTime(out, c->ev[a], c->ev[b]));
-            return GD_OK;
-        };
-        if (S.used_chunk) {
-            if (int r = ms(1, 2, &c->kernel_ms[GD_K_PREP])) return r;
-            if (int r = ms(2, 3, &c->kernel_ms[GD_K_TILE])) return r;
-            if (int r = ms(3, 4, &c->kernel_ms[GD_K_RUNS])) return r;
-        } else if (!S.used_scatter) {
-            if (int r = ms(0, 1, &c->kernel_ms[GD_K_PREP])) return r;
-            if (int r = ms(1, 2, &c->kernel_ms[GD_K_TILE])) return r;
-            if (int r = ms(2, 3, &c->kernel_ms[GD_K_RUNS])) return r;
-        } else {
-            if (int r = ms(0, 1, &c->kernel_ms[GD_K_PREP])) return r;
-            if (int r = ms(1, 2, &c->kernel_ms[GD_K_EXPAND])) return r;
-            if (int r = ms(2, 3, &c->kernel_ms[GD_K_SCAN])) return r;
-            if (int r = ms(3, 4, &c->kernel_ms[GD_K_RUNS])) return r;
-        }
-    }
+    for (int k = 0; k + 1 < S.n_stages; ++k)                // (the stages the enqueue opened; none without profiling)
+        HIPCHK(c, hipEventElapsedTime(&c->kernel_ms[S.stage_id[k]], c->ev[k], c->ev[k + 1]));
     // slice the boundary list per contig
     {
         size_t i = 0;
@@ -459,17 +403,17 @@ static int compute_publish(gd_ctx* c, ComputeState& S)
     c->stats.tile_positions = kTileT;
     c->stats.lookback = S.used_lookback;
     c->stats.reruns = S.reruns;
-    c->stats.path = S.used_chunk ? GD_PATH_CHUNK : S.used_scatter ? GD_PATH_SCATTER : GD_PATH_TILE;
+    c->stats.path = route_path(S.route);
     c->stats.n_slow_tiles = (int32_t)c->h_counters->n_slow[c->parity];
-    c->stats.tile_kernel = S.it_kernel;
+    c->stats.tile_kernel = S.route;
     // the slow list is normally one tile per contig: a small grid strides over it; data with many slow tiles
     // (deep pile-ups) gets a wider one from the next compute on
     if ((uint32_t)c->stats.n_slow_tiles > c->slow_grid * 4u) c->slow_grid = std::min<uint32_t>(2048u, (uint32_t)c->stats.n_slow_tiles);
     c->stats.n_canonical_ops = 0;
     c->stats.n_deletions = 0;
-    if (S.used_chunk)
+    if (S.route == GD_TK_LONG)
         for (int32_t tid : c->job_tids) c->stats.n_deletions += c->contigs[tid].n_dels;
-    if (S.used_scatter) c->stats.max_span_seen = 0;   // not measured on this path
+    if (S.route == GD_TK_SCATTER) c->stats.max_span_seen = 0;   // not measured on this path
     c->computed = true;
     return GD_OK;
 }
@@ -504,15 +448,21 @@ int gd_compute_finish(gd_ctx* c)
     if (!c) return GD_E_INVALID;
     if (!c->cs.pending) return fail(c, GD_E_STATE, "gd_compute_launch has not been called");
     c->cs.pending = false;
-    if (c->cs.nothing) { c->computed = true; return GD_OK; }
-    if (int r = set_device(c)) return r;
-    const double t0 = compute_now();
-    for (;;) {
-        const int r = compute_complete(c, c->cs);
-        if (r < 0) return r;
-        if (r == 0) break;
-        if (int e = compute_enqueue(c, c->cs)) return e;
+    double t0 = 0;
+    if (!c->cs.nothing) {
+        if (int r = set_device(c)) return r;
+        t0 = compute_now();
+        for (;;) {
+            const int r = compute_complete(c, c->cs);
+            if (r < 0) return r;
+            if (r == 0) break;
+            if (int e = compute_enqueue(c, c->cs)) return e;
+        }
     }
+    // what the results hold: the route of the LAST attempt (under GD_PATH_AUTO a re-run may have left a sums-only
+    // route for the long-read one); GD_TK_NONE for a job without tiles
+    c->ran_sums_only = route_sums_only(c->cs.route);
+    if (c->cs.nothing) { c->computed = true; return GD_OK; }
     const int rp = compute_publish(c, c->cs);
     c->timing[2] = compute_now() - t0;
     c->timing[3] += c->timing[2];
@@ -530,11 +480,10 @@ int gd_compute(gd_ctx* c)
 int gd_rebuild_derived(gd_ctx* c)
 {
     if (!c) return GD_E_INVALID;
-    if (c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
+    if (int r = in_flight(c)) return r;
     if (int r = set_device(c)) return r;
     if (c->contigs.empty()) return fail(c, GD_E_STATE, "gd_set_contigs has not been called");
-    std::vector<int32_t> tids = c->selected;
-    if (tids.empty()) { tids.resize(c->contigs.size()); for (size_t i = 0; i < tids.size(); ++i) tids[i] = (int32_t)i; }
+    const std::vector<int32_t> tids = selected_or_all(c);
     c->computed = false;
     std::vector<int32_t> raw;
     for (int32_t tid : tids) {
@@ -550,7 +499,7 @@ int gd_rebuild_derived(gd_ctx* c)
 int gd_drop_derived(gd_ctx* c)
 {
     if (!c) return GD_E_INVALID;
-    if (c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
+    if (int r = in_flight(c)) return r;
     if (int r = set_device(c)) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (auto& h : c->contigs) drop_ck(h);

@@ -140,7 +140,7 @@ int gd_ingest_release(gd_ctx* c)
 int gd_ingest_begin(gd_ctx* c, uint64_t n_bytes, uint64_t base_coffset, size_t n_members, const uint64_t* member_off,
                     const uint32_t* member_size, const uint16_t* header_size, const uint32_t* isize, const uint32_t* crc)
 {
-    if (c && c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
+    if (int r = in_flight(c)) return r;
     if (!c || n_members == 0 || !member_off || !member_size || !header_size || !isize || !crc) return GD_E_INVALID;
     // (a read in progress -- gd_ingest_feed_fd -- fills the newest range meanwhile: this call touches neither that
     // range nor the staging buffers; its error surfaces at the next gd_ingest_feed*)
@@ -257,19 +257,12 @@ static int ingest_fill(gd_ctx* c, int k, const uint8_t* bytes, int fd, uint64_t 
         for (size_t b = 0; b < piece; b += std::max<size_t>(slice, 4096)) {
             const size_t e = std::min(piece, b + std::max<size_t>(slice, 4096));
             items.push_back(FillPool::Item{c->ing_stage[k] + b, reinterpret_cast<const void*>((uintptr_t)(offset + b)), e - b,
-                                           (uint32_t)fd, 5, 0});
+                                           (uint32_t)fd, FillPool::PREAD, 0});
         }
-        if (pool) {
-            pool->bad.store(0);
-            pool->spin_limit.store(500, std::memory_order_relaxed);
-            pool->run(std::move(items));
-            pool->spin_limit.store(20000, std::memory_order_relaxed);
-            if (pool->bad.load()) return fail(c, GD_E_INVALID, "the file ended early or could not be read");
-        } else {
-            FillPool one;
-            for (const FillPool::Item& it : items) one.run_item(it);
-            if (one.bad.load()) return fail(c, GD_E_INVALID, "the file ended early or could not be read");
-        }
+        if (pool) pool->spin_limit.store(500, std::memory_order_relaxed);
+        const uint32_t bad = FillPool::run_items(pool, std::move(items));
+        if (pool) pool->spin_limit.store(20000, std::memory_order_relaxed);
+        if (bad) return fail(c, GD_E_INVALID, "the file ended early or could not be read");
     } else if (c->ing_copy_threads > 1 && piece >= (8u << 20)) {
         const int nt = c->ing_copy_threads;
         const size_t slice = ((piece / (size_t)nt) + 4095) & ~(size_t)4095;
@@ -369,7 +362,7 @@ static int ingest_feed(gd_ctx* c, IngestState* g, const uint8_t* bytes, int fd, 
 static int ingest_feed_target(gd_ctx* c, size_t n, IngestState** out)
 {
     if (int r = ingest_join(c)) { (void)gd_ingest_abort(c); return r; }
-    if (c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
+    if (int r = in_flight(c)) return r;
     IngestState* g = c->ing_n ? c->ing_q[c->ing_n - 1] : nullptr;
     if (!g) return fail(c, GD_E_STATE, "gd_ingest_begin has not been called");
     if (g->fed + n > g->n_bytes) return fail(c, GD_E_RANGE, "more bytes fed than announced");
@@ -404,7 +397,7 @@ struct IngestGuard { gd_ctx* c; bool on; ~IngestGuard() { if (on) (void)gd_inges
 // The oldest pending range, ready to decode (every member fed).  From the moment there is a range the guard is armed.
 static int ingest_oldest(gd_ctx* c, IngestGuard* guard, IngestState** out)
 {
-    if (c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
+    if (int r = in_flight(c)) return r;
     if (c->ing_n < 2)                                                 // (with two ranges pending a read in progress fills the newer one)
         if (int r = ingest_join(c)) { (void)gd_ingest_abort(c); return r; }
     if (int r = set_device(c)) return r;
@@ -581,7 +574,7 @@ static int ingest_decode(gd_ctx* c, int32_t tid, int32_t ref_id, const uint64_t*
             if (h.n_reads + want_r > h.cap_reads) want_r = std::max(want_r, h.cap_reads / 2);
             if (h.n_ops + want_o > h.cap_ops) want_o = std::max(want_o, h.cap_ops / 2);
         }
-        if (int r = reserve_records(c, h, want_r, want_o)) return r;
+        if (int r = reserve_records(c, h, want_r, want_o, Growth::EXACT)) return r;
         c->ing_secs[5] += ing_now() - td2;
         bj.rec_base = s_rbase; bj.op_base = s_obase;
         bj.pos = h.pos; bj.flag = h.flag; bj.mapq = h.mapq; bj.cigar_off = h.off; bj.cigar = h.cigar;
@@ -667,7 +660,7 @@ int gd_bgzf_members(const uint8_t* data, size_t n_bytes, size_t cap, uint64_t* m
 int gd_ingest_bgzf(gd_ctx* c, int32_t tid, int32_t ref_id, const uint8_t* data, size_t n_bytes, uint64_t base_coffset,
                    const uint64_t* anchors, size_t n_anchors, uint64_t* n_records)
 {
-    if (c && c->cs.pending) return fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first");
+    if (int r = in_flight(c)) return r;
     if (!c || !data || !anchors || n_anchors == 0) return GD_E_INVALID;
     (void)gd_ingest_abort(c);                              // one-shot form: nothing else may be pending
     size_t nm = 0;

@@ -257,3 +257,60 @@ int gd_regions(gd_ctx* c, size_t n_regions, const int32_t* tid, const int64_t* s
     if (nr > cap_runs || (nr && !runs)) return fail(c, GD_E_CAPACITY, "need room for %zu runs", nr);
     return GD_OK;
 }
+
+int gd_device_perbase(gd_ctx* c, int32_t tid, const int32_t** dptr, int64_t* len)
+{
+    if (!c || !dptr) return GD_E_INVALID;
+    if (int r = check_result_tid(c, tid)) return r;
+    const ContigHost& h = c->contigs[tid];
+    if (!c->d_perbase) return fail(c, GD_E_STATE, "the per-base vector was not kept (gd_set_outputs)");
+    *dptr = h.length > 0 ? c->d_perbase + h.base_off : nullptr;
+    if (len) *len = h.length;
+    return GD_OK;
+}
+
+int gd_device_windows(gd_ctx* c, const int64_t** d_sums, const int32_t** d_mins, size_t* n_total)
+{
+    if (!c) return GD_E_INVALID;
+    if (!c->computed) return fail(c, GD_E_STATE, "no results: call gd_compute first");
+    if (d_sums) *d_sums = c->d_wsum;
+    if (d_mins) *d_mins = c->d_wmin;
+    if (n_total) *n_total = (size_t)c->n_win_total;
+    return GD_OK;
+}
+
+int gd_window_offset(gd_ctx* c, int32_t tid, size_t* off, size_t* n)
+{
+    if (!c) return GD_E_INVALID;
+    if (int r = check_result_tid(c, tid)) return r;
+    const ContigHost& h = c->contigs[tid];
+    if (off) *off = h.win_off < 0 ? 0 : (size_t)h.win_off;
+    if (n) *n = (size_t)h.n_win;
+    return GD_OK;
+}
+
+int gd_device_runs(gd_ctx* c, const int32_t** d_bounds, size_t* n_bounds)
+{
+    if (!c) return GD_E_INVALID;
+    if (!c->computed) return fail(c, GD_E_STATE, "no results: call gd_compute first");
+    if (d_bounds) *d_bounds = reinterpret_cast<const int32_t*>(c->d_ordered);
+    if (n_bounds) *n_bounds = c->bounds.size();
+    return GD_OK;
+}
+
+int gd_set_export(gd_ctx* c, void* device_buf, int64_t max_windows, int64_t cap_bounds)
+{
+    if (!c || max_windows < 0 || cap_bounds < 0) return GD_E_INVALID;
+    c->export_buf = static_cast<int64_t*>(device_buf);
+    c->export_max_w = max_windows;
+    c->export_cap_b = cap_bounds;
+    return GD_OK;
+}
+
+int gd_wait_event(gd_ctx* c, void* ev)
+{
+    if (!c || !ev) return GD_E_INVALID;
+    if (int r = set_device(c)) return r;
+    HIPCHK(c, hipStreamWaitEvent(c->stream, static_cast<hipEvent_t>(ev), 0));
+    return GD_OK;
+}

@@ -1,7 +1,9 @@
 // gd_api_state.hpp -- what a gd_ctx holds and the helpers every part of the C ABI shares: per-contig
-// record streams, the pinned staging ring, the device job state, launch helpers of the tile kernels,
-// the long-read structures (gd_chunk.hpp) and the state of a device BAM read.  Included by gd_api.hip
-// only (one translation unit: the kernels of gd_kernels.hpp are not inline).
+// record streams, the pinned staging ring, the device job state, what a gd_compute carries from launch to finish
+// (ComputeState: the route and the profiling stages of the attempt in flight), the in-flight guard, the route rule
+// (compute_route) and the launch helpers of the tile kernels that take its answer, the long-read structures
+// (gd_chunk.hpp) and the state of a device BAM read.  Included by gd_api.hip only (one translation unit: the
+// kernels of gd_kernels.hpp are not inline).
 #pragma once
 
 #include <memory>
@@ -132,12 +134,14 @@ struct ComputeState {
     uint64_t n_reads = 0, n_ops = 0, n_units = 0, n_groups = 0;
     int64_t tile_beg = 0, base_off = 0, win_off = 0, bases = 0;
     bool raw_aligned = true;            // ... arrays aligned for the raw straight-line kernel's vector loads
-    int32_t it_kernel = 0;              // GD_TK_*: the kernel of the attempt in flight
+    int32_t route = GD_TK_NONE;         // compute_route's answer for the attempt in flight (GD_TK_NONE: a job without tiles)
+    // profiling: stage k is the interval ev[k] .. ev[k + 1] and belongs to kernel_ms[stage_id[k]]; the last record
+    // only closes the stage before it (scatter has the most: four stages, five records)
+    int8_t stage_id[6] = {};
+    int n_stages = 0;
     int reruns = 0, used_lookback = 0;
-    bool used_scatter = false, used_chunk = false;
     int32_t chunk_span = 0;
-    bool it_scatter = false, it_chunk = false;   // the attempt in flight
-    size_t spec = 0;                             // boundaries copied speculatively with the counters
+    size_t spec = 0;                    // boundaries copied speculatively with the counters
     bool pending = false;               // launched, not finished
     bool nothing = false;               // ... a job without tiles
 };
@@ -306,6 +310,13 @@ int fail(gd_ctx* c, int code, const char* fmt, ...)
     return code;
 }
 
+// Whatever changes what a launched compute reads (records, contigs, parameters, path, outputs, options) is refused
+// until gd_compute_finish.  A null context passes: the caller's own argument check answers that.
+int in_flight(gd_ctx* c)
+{
+    return c && c->cs.pending ? fail(c, GD_E_STATE, "a compute is in flight: gd_compute_finish first") : GD_OK;
+}
+
 #define HIPCHK(ctx, call)                                                              \
     do {                                                                               \
         hipError_t e_ = (call);                                                        \
@@ -394,6 +405,22 @@ int set_device(gd_ctx* c)
     return GD_OK;
 }
 
+// The records are gone (gd_set_contigs, gd_reset): so are the blocks handed out before, the verdicts pending on committed
+// ones, and what the context learnt from the records -- the look-back, the spans the index pass measured.
+int forget_records_state(gd_ctx* c)
+{
+    for (auto& s : c->ring) s.held = false;
+    c->commit_checks_pending = false;                      // (d_ingest is cleared below)
+    c->computed = false;
+    c->lookback = c->params.max_span_hint > 0 ? c->params.max_span_hint : kDefaultLookback;
+    c->span_forces_long = false;
+    HIPCHK(c, hipMemsetAsync(c->d_ingest, 0, 4 * sizeof(uint32_t), c->stream));   // spans of records that are gone
+    HIPCHK(c, hipStreamSynchronize(c->stream));            // (the next block's index pass runs on the copy stream: not before this)
+    c->ingest_span = 0;
+    c->ingest_span_dirty = false;
+    return GD_OK;
+}
+
 void launch_prep(gd_ctx* c, const gd::Job& job)
 {
     // one thread per tile; the same threads grid-stride over the window arrays (a thread per window made a 30x
@@ -414,23 +441,23 @@ void with_store_mode(const gd_ctx* c, F&& f)
     else f(std::integral_constant<int, 0>{});
 }
 
-void launch_tile(gd_ctx* c, const gd::Job& job)
+void launch_tile(gd_ctx* c, const gd::Job& job, int route)
 {
     // 8 XCDs: the grid is 8 equal slices of the tile list (see the kernel)
     const unsigned grid = (unsigned)(((job.n_tiles + 7) / 8) * 8);
     const dim3 block(gd::shape::NT);
-    if (c->ran_sums_only) {                                 // decided by gd_compute for this run
+    if (route == GD_TK_TILE_SUMS) {
         hipLaunchKernelGGL(gd::gd_tile_sums_kernel, dim3(grid), block, 0, c->stream, job);
         return;
     }
     with_store_mode(c, [&](auto m) {
         constexpr int M = decltype(m)::value;
-        if (!job.fast) {
+        if (route == GD_TK_GENERIC) {
             hipLaunchKernelGGL(gd::gd_tile_kernel<M>, dim3(grid), block, 0, c->stream, job);
             return;
         }
-        // ordinary tiles: the straight-line kernel; the tiles gd_prep_kernel listed as `slow` (clipped at a
-        // contig end, deeper than one batch of reads, more ops than the staging area): the generic one
+        // GD_TK_FAST_RAW.  Ordinary tiles: the straight-line kernel; the tiles gd_prep_kernel listed as `slow` (clipped
+        // at a contig end, deeper than one batch of reads, more ops than the staging area): the generic one
         // The slow list (a few dozen workgroups of a large, cold kernel) goes FIRST: launched after the
         // straight-line kernel it took ~0.1 ms -- as long as all of chr20's ordinary tiles -- behind the
         // write-back of that kernel's per-base stores; in front of it, it costs a few microseconds
@@ -448,6 +475,14 @@ void launch_ltile(gd_ctx* c, const gd::Job& job)
         constexpr int M = decltype(m)::value == 1 ? 0 : decltype(m)::value;   // (built with plain stores and with none)
         hipLaunchKernelGGL(gd::gd_ltile2_kernel<M>, dim3(grid), dim3(gd::shape::NT), 0, c->stream, job);
     });
+}
+
+// The class runs of every tile, in genome order (every route but the sums-only ones ends with it).
+void launch_runs_order(gd_ctx* c, const gd::Job& job)
+{
+    hipLaunchKernelGGL(gd::gd_runs_order_kernel, dim3((unsigned)((c->n_tiles + gd::SUPER - 1) / gd::SUPER)), dim3(gd::SUPER), 0,
+                       c->stream, c->d_chunks, job.run_cap, c->d_tile_cnt, c->d_tile_off, c->d_super_cnt, c->d_ordered,
+                       (int)c->n_tiles);
 }
 
 // In-place exclusive scan of v[0..n) on the compute stream, v[n] = total (v has n + 1 elements).
@@ -634,10 +669,39 @@ int ck_batch(gd_ctx* c, const std::vector<ContigHost*>& hs)
     return GD_OK;
 }
 
-// What GD_PATH_AUTO sends to the long-read path (contig-wise).
-bool long_shaped(const gd_ctx* c, const ContigHost& h)
+// ---- the route of a gd_compute ------------------------------------------------------------------------------
+// Which device algorithm and which tile kernel a job runs: the GD_TK_* value gd_stats.tile_kernel reports, or
+// GD_E_INVALID.  This is the one statement of the rule; everything else -- long-read or scatter
+// launch sequence, sums-only, Job::fast, gd_stats.path, the kernel launch_tile launches -- is read off its answer.
+// Under GD_PATH_AUTO the answer can change between two attempts of one compute (span_forces_long).
+
+// May the straight-line tile kernel and the streaming sums kernel run at all?  (They still need aligned arrays;
+// compute_prepare allocates the straight-line kernel's tile table on this.)
+bool straight_line_allowed(const gd_ctx* c)
 {
-    return c->path == GD_PATH_CHUNK || (c->path == GD_PATH_AUTO && (c->span_forces_long || h.n_ops > 6 * h.n_reads));
+    return c->fast_kernel && (c->path == GD_PATH_TILE || c->path == GD_PATH_AUTO);
+}
+
+int compute_route(const gd_ctx* c, const ComputeState& S)
+{
+    if (c->path == GD_PATH_SCATTER) return c->keep_perbase ? GD_TK_SCATTER : GD_E_INVALID;
+    if (c->path == GD_PATH_CHUNK || (c->path == GD_PATH_AUTO && (c->span_forces_long || S.n_ops > 6 * S.n_reads)))
+        return GD_TK_LONG;                                   // (sums-only is ignored: minima and runs are produced)
+    // The straight-line kernels read the records as they arrived (no pass over the records before the first -- usually
+    // the only -- compute of an input); contig arrays their vector loads cannot take: the generic kernels.
+    const bool straight = straight_line_allowed(c) && S.raw_aligned;
+    // sums-only: built for the default tile shape; W < 32 (more windows per tile than the LDS accumulators hold) keeps
+    // the regular windows-only kernels, as documented
+    if (c->sums_only && c->params.window_size >= 32)         // one streaming pass over the records, no tiles, where it can
+        return straight && S.n_groups <= 0xfffffff0ull ? GD_TK_SUMS_STREAM_RAW : GD_TK_TILE_SUMS;
+    return straight ? GD_TK_FAST_RAW : GD_TK_GENERIC;
+}
+
+bool route_sums_only(int route) { return route == GD_TK_TILE_SUMS || route == GD_TK_SUMS_STREAM_RAW; }
+
+int route_path(int route)
+{
+    return route == GD_TK_LONG ? GD_PATH_CHUNK : route == GD_TK_SCATTER ? GD_PATH_SCATTER : GD_PATH_TILE;
 }
 
 // The long-read structures of the listed contigs that lack them, straight from the records as they arrived.
