@@ -351,6 +351,7 @@ __global__ __launch_bounds__(NT) void gd_tile_fast_kernel(Job job)
                 if (k <= 0) qm = e0 < qm ? e0 : qm;
                 if (k <= 1) qm = e1 < qm ? e1 : qm;
                 if (k <= 2) qm = e2 < qm ? e2 : qm;
+                // (the depth reaches 1024 in case a-depth-1024 of tests/tile_shapes.py)
                 const uint32_t tot = (uint32_t)wave_total((int)a_old) + ps;   // < 2^32 (depth <= 1024 reads)
                 int m = wave_min_dpp(m_old);
                 m = pm < m ? pm : m;

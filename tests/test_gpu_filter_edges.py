@@ -148,24 +148,7 @@ def some_regions(seed):
     return tids, starts, ends
 
 
-def device_arrays(r, misaligned=()):
-    """The records as device tensors; the arrays named in `misaligned` are contiguous slices at element offset 1 of
-    larger tensors (what a host that slices one device arena per contig hands over)."""
-    import torch
-    dev = torch.device("cuda", 0)
-    out = []
-    for name, a, dt in (("pos", r.pos, np.int32), ("flag", r.flag, np.int16), ("mapq", r.mapq, np.uint8),
-                        ("off", r.cigar_off, np.int32), ("cigar", r.cigar, np.int32)):
-        a = np.ascontiguousarray(a).view(dt)
-        if name in misaligned:
-            big = torch.zeros(a.shape[0] + 9, dtype=torch.from_numpy(a[:0]).dtype, device=dev)
-            t = big[1:1 + a.shape[0]]
-            t.copy_(torch.from_numpy(a))
-            assert t.is_contiguous() and t.data_ptr() % {"pos": 16, "flag": 8, "mapq": 4, "off": 16, "cigar": 4}[name]
-        else:
-            t = torch.from_numpy(a).to(dev)
-        out.append(t)
-    return out
+device_arrays = H.device_arrays        # (shared with tests/test_gpu_tile_shapes.py)
 
 
 ALL4 = ("pos", "flag", "mapq", "off")
