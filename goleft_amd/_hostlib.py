@@ -33,6 +33,8 @@ SYMBOLS = {
     "gdh_indexsplit_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_indexsplit_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p]),
     "gdh_samplename_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
+    "gdh_crai_read": (C.c_int, [C.c_char_p, C.c_size_t, C.c_size_t, _P, _P, _P, _P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]),
     "gdh_round3g": (None, [_P, C.c_size_t, _P]),
     "gdh_fmt3g": (C.c_int, [C.c_uint32, C.c_char_p, C.c_size_t]),
     "gdh_indexcov_pcs": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),

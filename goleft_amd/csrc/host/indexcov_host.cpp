@@ -1,9 +1,9 @@
 // indexcov_host.cpp -- host twin of `goleft indexcov` (goleft's indexcov/indexcov.go, types.go).
 //
-//   goleft-depth indexcov -d DIR [-X X,Y] [-p REGEX] [-e] [-n] [-f ref.fai] a.bam b.bam ... | a.bai ...
+//   goleft-depth indexcov -d DIR [-X X,Y] [-p REGEX] [-e] [-n] [-f ref.fai] a.bam b.bam ... | a.bai ... | a.crai ...
 //
-// Coverage of a cohort from the .bai linear indexes alone: DIR/<DIR>-indexcov.bed.gz (one row per 16 384-base tile, one
-// %.3g column per sample), .roc (coverage ROC per reference) and .ped (inferred sex, copy number of the sex references,
+// Coverage of a cohort from the .bai linear indexes -- or the .crai slices, tiled on the device (gd_crai_sizes; DESIGN.md
+// section 3.9) -- alone: DIR/<DIR>-indexcov.bed.gz (one row per 16 384-base tile, one %.3g column per sample), .roc (coverage ROC per reference) and .ped (inferred sex, copy number of the sex references,
 // bin counts, slopes, five principal components).  The host reads the indexes (eight reader threads), runs the
 // reference's sequential -n pass, solves the N x N eigenproblem and writes text and BGZF; medians, depths, cells, slots,
 // counters, copy numbers, the pca8 bytes and their exact Gram matrix come from the device (gd_indexcov_*).
@@ -53,9 +53,10 @@ void usage(FILE* f)
           "  -e  accepted (it selects plotted chromosomes; GL* references then also weigh into the slope)\n"
           "  -p  regular expression of chromosome names to exclude (ECMAScript syntax; the reference uses RE2)\n"
           "  -X  comma delimited names of the sex chromosome(s), '' if there are none (default X,Y)\n"
-          "  -f  fasta index file, required when the first input is a bare .bai\n"
+          "  -f  fasta index file, required when the first input is a bare .bai or a .crai\n"
           "  -n  normalize across samples and smooth within a sample\n"
-          "  inputs: .bam files (index x.bam.bai, else x.bai) or .bai files; .crai / .cram and -c/--chrom are refused.\n"
+          "  inputs: .bam files (index x.bam.bai, else x.bai), .bai files or .crai files, in any mix; for a .cram pass its\n"
+          "          .crai; -c/--chrom is refused.\n"
           "  No HTML, PNG or chart output is written (index.html, *-roc-*.html, *.png of the reference are out of scope).\n", f);
 }
 
@@ -136,7 +137,7 @@ void read_sample(Sample* s)
     const std::string& b = s->path;
     std::string err;
     if (!gdh::read_index_sizes(b, s, &s->err)) return;
-    if (ends_with(b, ".bai")) {
+    if (ends_with(b, ".bai") || ends_with(b, ".crai")) {
         gdh::short_name(b, "", &s->name);
     } else {
         gdh::BamReader br;
@@ -268,11 +269,17 @@ int run(const IArgs& a)
     const bool timing = getenv("GOLEFT_INDEXCOV_TIMING") != nullptr;
     double t_read = 0, t_norm = 0, t_eig = 0, t_text = 0, t_bgzf = 0, t_back = 0;
     const double t_start = now_s();
-    for (const std::string& b : a.inputs)
-        if (ends_with(b, ".crai") || ends_with(b, ".cram")) {
-            fprintf(stderr, "indexcov: %s: CRAM indexes are not supported (only .bam / .bai inputs)\n", b.c_str());
+    for (const std::string& b : a.inputs) {
+        if (ends_with(b, ".cram")) {
+            fprintf(stderr, "indexcov: %s: CRAM alignment files are not read: pass the .crai index instead\n", b.c_str());
             return 1;
         }
+        // (expandGlobs below drops what matches nothing; a .crai that is not there is named instead)
+        if (ends_with(b, ".crai") && b.find_first_of("*?[") == std::string::npos && access(b.c_str(), F_OK) != 0) {
+            fprintf(stderr, "indexcov: %s: no such .crai index\n", b.c_str());
+            return 1;
+        }
+    }
     std::vector<std::string> sex;
     if (!a.sex.empty()) {                                                      // strings.Split(strings.TrimSpace(Sex), ",")
         std::string t = a.sex;
@@ -332,6 +339,31 @@ int run(const IArgs& a)
     for (const Sample& s : smp)
         if (!s.err.empty()) { fprintf(stderr, "indexcov: %s\n", s.err.c_str()); return 1; }
     t_read = now_s() - t_start;
+    gd_ctx* ctx = nullptr;
+    auto open_device = [&]() -> bool {
+        if (ctx) return true;
+        int device = 0;
+        if (const char* e = getenv("GOLEFT_DEVICE")) device = atoi(e);
+        const int rc = gd_create(device, &ctx);
+        if (rc != GD_OK) fprintf(stderr, "indexcov: no usable MI355X device (%s); this build has no CPU path\n", gd_strerror(rc));
+        return rc == GD_OK;
+    };
+    double t_crai_read = 0, t_crai_tile = 0;
+    {
+        // the slices of the .crai indexes become tile sizes: one device call for all of them
+        std::vector<gdh::IndexSizes*> all(N);
+        bool any = false;
+        for (size_t s = 0; s < N; ++s) { all[s] = &smp[s]; any = any || smp[s].is_crai; t_crai_read += smp[s].crai_read_s; }
+        if (any) {
+            if (!open_device()) return 1;
+            std::string err;
+            if (!gdh::tile_crai_indexes(ctx, all, paths, &err, &t_crai_tile)) {
+                fprintf(stderr, "indexcov: %s\n", err.c_str());
+                gd_destroy(ctx);
+                return 1;
+            }
+        }
+    }
     fprintf(stderr, "indexcov: running on %zu indexes\n", N);
     // the references that are reported
     std::vector<size_t> kept;
@@ -339,7 +371,7 @@ int run(const IArgs& a)
         if (has_exclude && std::regex_search(refs[r].name, exclude)) continue;
         kept.push_back(r);
     }
-    if (kept.empty()) { fprintf(stderr, "(FATAL) indexcov: every reference is excluded by %s\n", a.exclude.c_str()); return 1; }
+    if (kept.empty()) { fprintf(stderr, "(FATAL) indexcov: every reference is excluded by %s\n", a.exclude.c_str()); gd_destroy(ctx); return 1; }
     const size_t R = kept.size();
     std::vector<uint8_t> is_sex(R);
     for (size_t k = 0; k < R; ++k) is_sex[k] = same_chrom(sex, refs[kept[k]].name) ? 1 : 0;
@@ -358,16 +390,7 @@ int run(const IArgs& a)
         std::vector<int64_t>().swap(smp[s].sizes);
         std::vector<std::vector<uint64_t>>().swap(smp[s].raw);
     }
-    int device = 0;
-    if (const char* e = getenv("GOLEFT_DEVICE")) device = atoi(e);
-    gd_ctx* ctx = nullptr;
-    {
-        const int rc = gd_create(device, &ctx);
-        if (rc != GD_OK) {
-            fprintf(stderr, "indexcov: no usable MI355X device (%s); this build has no CPU path\n", gd_strerror(rc));
-            return 1;
-        }
-    }
+    if (!open_device()) return 1;
     IC_CHECK(gd_indexcov_upload(ctx, (int32_t)N, (int32_t)R, sample_off.data(), sizes.data(), tile_off.data(), tile_cnt.data(), is_sex.data()));
     std::vector<int64_t>().swap(sizes);
     gd_indexcov_dims dims{};
@@ -548,9 +571,9 @@ int run(const IArgs& a)
     t_text += now_s() - t0;
     if (timing)
         fprintf(stderr, "{\"samples\": %zu, \"tiles\": %" PRId64 ", \"m\": %" PRId64 ", \"total_s\": %.4f, \"index_read_s\": %.4f, "
-                        "\"upload_s\": %.4f, \"median_depth_s\": %.4f, \"pass_s\": %.4f, \"cn_s\": %.4f, \"gram_s\": %.4f, "
+                        "\"crai_read_s\": %.4f, \"crai_tile_s\": %.4f, \"upload_s\": %.4f, \"median_depth_s\": %.4f, \"pass_s\": %.4f, \"cn_s\": %.4f, \"gram_s\": %.4f, "
                         "\"readback_s\": %.4f, \"normalize_s\": %.4f, \"eigen_s\": %.4f, \"text_s\": %.4f, \"bgzf_s\": %.4f}\n",
-                N, dims.n_tiles, dims.m, now_s() - t_start, t_read, lib[0], lib[1], lib[2], lib[3], lib[4], t_back, t_norm, t_eig,
+                N, dims.n_tiles, dims.m, now_s() - t_start, t_read, t_crai_read, t_crai_tile, lib[0], lib[1], lib[2], lib[3], lib[4], t_back, t_norm, t_eig,
                 t_text, t_bgzf);
     fprintf(stderr, "indexcov finished: see %s.ped for overview of output\n", base.c_str());
     return 0;
@@ -730,6 +753,28 @@ extern "C" int gdh_fmt3g(uint32_t cell, char* out, size_t cap)
     memcpy(out, buf, (size_t)n);
     out[n] = 0;
     return n;
+}
+
+extern "C" int gdh_crai_read(const char* path, size_t cap_refs, size_t cap_slices, int64_t* ref_off, int64_t* aln_start, int64_t* aln_span,
+                             int32_t* slice_len, size_t* n_refs, size_t* n_slices, int64_t* line, char* msg, size_t cap_msg)
+{
+    if (!path || !n_refs || !n_slices || !line) return -1;
+    gdh::CraiSlices c;
+    std::string why;
+    *n_refs = *n_slices = 0;
+    if (!gdh::read_crai(path, &c, line, &why)) {
+        if (msg && cap_msg) snprintf(msg, cap_msg, "%s", why.c_str());
+        return -2;
+    }
+    *n_refs = c.ref_off.size() - 1;
+    *n_slices = c.start.size();
+    if (!ref_off || cap_refs < *n_refs || cap_slices < *n_slices) return -3;
+    if (*n_slices && (!aln_start || !aln_span || !slice_len)) return -1;
+    std::copy(c.ref_off.begin(), c.ref_off.end(), ref_off);
+    std::copy(c.start.begin(), c.start.end(), aln_start);
+    std::copy(c.span.begin(), c.span.end(), aln_span);
+    std::copy(c.len.begin(), c.len.end(), slice_len);
+    return 0;
 }
 
 extern "C" int gdh_indexcov_run(int argc, const char* const* argv)

@@ -1,9 +1,10 @@
 // indexsplit_host.cpp -- host twin of `goleft indexsplit` (goleft's indexsplit/indexsplit.go).
 //
-//   goleft-depth indexsplit -n N [--fai ref.fai] [-p problematic.bed] a.bam b.bam ... | a.bai ...
+//   goleft-depth indexsplit -n N [--fai ref.fai] [-p problematic.bed] a.bam b.bam ... | a.bai ... | a.crai ...
 //
-// N regions that hold about the same amount of data across a cohort, from the .bai linear indexes alone: the tile
-// sizes of every index are summed cell by cell on the device (gd_indexsplit_*, float64, the samples in argument
+// N regions that hold about the same amount of data across a cohort, from the .bai linear indexes -- or the .crai slices,
+// tiled on the device (gd_crai_sizes) -- alone: the tile sizes of every index are summed cell by
+// cell on the device (gd_indexsplit_*, float64, the samples in argument
 // order); chop, getPercents and the walk over the tiles carry state from cell to cell and run here, in plain
 // sequential float64 (this library is built without fused multiply-adds).  Rows: chrom, start, end, %.2f sum, splits.
 #include <algorithm>
@@ -42,9 +43,10 @@ void usage(FILE* f)
 {
     fputs("usage: indexsplit --n N [--fai FAI] [--problematic PROBLEMATIC] INDEXES [INDEXES ...]\n"
           "  -n  number of regions to split to (at least 1)\n"
-          "  --fai  fasta index file, required when the first input is a bare .bai\n"
+          "  --fai  fasta index file, required when the first input is a bare .bai or a .crai\n"
           "  -p  BED file of regions to split small (one path; it is not split at '|')\n"
-          "  inputs: .bam files (index x.bam.bai, else x.bai) or .bai files; .crai / .cram are refused.\n", f);
+          "  inputs: .bam files (index x.bam.bai, else x.bai), .bai files or .crai files, in any mix; for a .cram pass its\n"
+          "          .crai.\n", f);
 }
 
 int parse_args(int argc, const char* const* argv, SArgs* a)
@@ -130,8 +132,8 @@ int run(const SArgs& a, FILE* out)
     const bool timing = getenv("GOLEFT_INDEXSPLIT_TIMING") != nullptr;
     const double t_start = now_s();
     for (const std::string& b : a.inputs)
-        if (ends_with(b, ".crai") || ends_with(b, ".cram")) {
-            fprintf(stderr, "indexsplit: %s: CRAM indexes are not supported (only .bam / .bai inputs)\n", b.c_str());
+        if (ends_with(b, ".cram")) {
+            fprintf(stderr, "indexsplit: %s: CRAM alignment files are not read: pass the .crai index instead\n", b.c_str());
             return 1;
         }
     gdh_intervals* probs = nullptr;
@@ -170,14 +172,6 @@ int run(const SArgs& a, FILE* out)
     for (const Sample& s : smp)
         if (!s.err.empty()) { fprintf(stderr, "indexsplit: %s\n", s.err.c_str()); return 1; }
     const double t_read = now_s() - t_start;
-    // Split (:92-114): reference i of the list is reference i of every index; an index with fewer has nothing there
-    auto count = [&](const Sample& s, size_t r) -> int64_t { return r + 1 < s.ref_off.size() ? s.ref_off[r + 1] - s.ref_off[r] : 0; };
-    std::vector<int32_t> longest(R, 0);
-    std::vector<int64_t> cell_off(R + 1, 0);
-    for (size_t r = 0; r < R; ++r) {
-        for (const Sample& s : smp) longest[r] = (int32_t)std::max<int64_t>(longest[r], count(s, r));
-        cell_off[r + 1] = cell_off[r] + longest[r];
-    }
     int device = 0;
     if (const char* e = getenv("GOLEFT_DEVICE")) device = atoi(e);
     gd_ctx* ctx = nullptr;
@@ -187,6 +181,26 @@ int run(const SArgs& a, FILE* out)
             fprintf(stderr, "indexsplit: no usable MI355X device (%s); this build has no CPU path\n", gd_strerror(rc));
             return 1;
         }
+    }
+    double t_crai_read = 0, t_crai_tile = 0;
+    {
+        // the slices of the .crai indexes become tile sizes: one device call for all of them
+        std::vector<gdh::IndexSizes*> all(N);
+        for (size_t s = 0; s < N; ++s) { all[s] = &smp[s]; t_crai_read += smp[s].crai_read_s; }
+        std::string err;
+        if (!gdh::tile_crai_indexes(ctx, all, a.inputs, &err, &t_crai_tile)) {
+            fprintf(stderr, "indexsplit: %s\n", err.c_str());
+            gd_destroy(ctx);
+            return 1;
+        }
+    }
+    // Split (:92-114): reference i of the list is reference i of every index; an index with fewer has nothing there
+    auto count = [&](const Sample& s, size_t r) -> int64_t { return r + 1 < s.ref_off.size() ? s.ref_off[r + 1] - s.ref_off[r] : 0; };
+    std::vector<int32_t> longest(R, 0);
+    std::vector<int64_t> cell_off(R + 1, 0);
+    for (size_t r = 0; r < R; ++r) {
+        for (const Sample& s : smp) longest[r] = (int32_t)std::max<int64_t>(longest[r], count(s, r));
+        cell_off[r + 1] = cell_off[r] + longest[r];
     }
     IS_CHECK(gd_indexsplit_begin(ctx, (int32_t)R, longest.data()));
     for (size_t s0 = 0; s0 < N; s0 += kBatch) {
@@ -281,8 +295,8 @@ int run(const SArgs& a, FILE* out)
     if (fwrite(o.data(), 1, o.size(), out) != o.size() || fflush(out) != 0) { fprintf(stderr, "indexsplit: error writing the regions\n"); return 1; }
     if (timing)
         fprintf(stderr, "{\"samples\": %zu, \"references\": %zu, \"cells\": %" PRId64 ", \"total_s\": %.4f, \"index_read_s\": %.4f, "
-                        "\"upload_s\": %.4f, \"kernel_s\": %.4f, \"readback_s\": %.4f, \"scan_s\": %.4f}\n",
-                N, R, cell_off[R], now_s() - t_start, t_read, lib[0], lib[1], lib[2], t_scan);
+                        "\"crai_read_s\": %.4f, \"crai_tile_s\": %.4f, \"upload_s\": %.4f, \"kernel_s\": %.4f, \"readback_s\": %.4f, \"scan_s\": %.4f}\n",
+                N, R, cell_off[R], now_s() - t_start, t_read, t_crai_read, t_crai_tile, lib[0], lib[1], lib[2], t_scan);
     return 0;
 }
 

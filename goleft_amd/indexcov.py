@@ -9,7 +9,8 @@ from . import _hostlib
 
 
 def Main(argv) -> int:
-    """argv: the arguments after the program name, e.g. ["-d", "out", "a.bam", "b.bam"].
+    """argv: the arguments after the program name, e.g. ["-d", "out", "a.bam", "b.bam"]; the inputs are .bam, .bai
+    or .crai files in any mix (a .bai or .crai first needs "-f", "ref.fai"; for a .cram pass its .crai).
     Writes out/out-indexcov.bed.gz, .roc and .ped; returns the exit code."""
     lib = _hostlib.load()
     args = [b"indexcov"] + [str(a).encode() for a in argv]

@@ -9,7 +9,8 @@ from . import _hostlib
 
 
 def Main(argv, out_path=None) -> int:
-    """argv: the arguments after the program name, e.g. ["-n", "1000", "a.bam", "b.bam"].
+    """argv: the arguments after the program name, e.g. ["-n", "1000", "a.bam", "b.bam"]; the inputs are .bam, .bai
+    or .crai files in any mix (a .bai or .crai first needs "--fai", "ref.fai"; for a .cram pass its .crai).
     The rows go to out_path (stdout when None); returns the exit code."""
     lib = _hostlib.load()
     args = [b"indexsplit"] + [str(a).encode() for a in argv]

@@ -38,11 +38,11 @@ extern "C" {
 #endif
 
 /* GD_ABI_VERSION changes when an existing entry point or structure changes; GD_ABI_REVISION counts the releases that only
- * ADDED entry points since then (revision 1: gd_indexcov_*; 2: gd_indexsplit_*).  A caller built against (15, r) runs on any (15, r' >= r).
+ * ADDED entry points since then (revision 1: gd_indexcov_*; 2: gd_indexsplit_*; 3: gd_crai_sizes).  A caller built against (15, r) runs on any (15, r' >= r).
  * Why indexcov did not become version 16: nothing that existed changed, so callers of ABI 15 need not be turned away, and
  * tests/test_host_cpu.py holds gd_abi_version() to 15 until something does change. */
 #define GD_ABI_VERSION 15
-#define GD_ABI_REVISION 2
+#define GD_ABI_REVISION 3
 
 typedef enum {
     GD_OK = 0,
@@ -628,6 +628,23 @@ int gd_indexsplit_add(gd_ctx* ctx, int32_t n_samples, const int64_t* sample_off,
 int gd_indexsplit_sums(gd_ctx* ctx, double* out, size_t cap);
 /* Seconds since gd_indexsplit_begin (measurement only): upload, kernel, read-back.  Fills min(n, 3) values. */
 int gd_indexsplit_timing(gd_ctx* ctx, double* out, size_t n);
+/* ---- the tile sizes of .crai slices (indexcov/crai/crai.go:56-127 makeSizes): what a .crai gives `indexcov` and
+ * `indexsplit` in place of a .bai's linear index ----
+ * A sequence is one reference of one index: the slices [seq_off[s], seq_off[s + 1]) of the three arrays, in file order
+ * (alnStart, alnSpan and sliceLen of the index's lines).  One wavefront walks a sequence; the call takes as many
+ * sequences as the caller has -- a whole cohort -- and the result of a sequence does not depend on what else is in the
+ * call.  tile_off[s + 1] - tile_off[s] is the number of 16 384-base tiles of sequence s (tile_off[0] = 0) and status[s]
+ * is 0, or 1 / 2 where the reference panics ("tilewidth logic error" / "logic error"; no input is known to get there;
+ * the tiles of such a sequence are the ones emitted up to that point).  Both are always filled.  sizes == NULL: that
+ * is all (count only).  Otherwise the tiles of sequence s are written to sizes[tile_off[s] .. tile_off[s + 1]), or,
+ * when cap < tile_off[n_seq], nothing is and the call returns GD_E_CAPACITY with tile_off in place.  GD_E_INVALID: a
+ * seq_off that does not start at 0 or decreases; GD_E_RANGE: an alnStart outside +-(2^31 - 1) or an alnSpan outside
+ * 0 .. 2^31 - 1 -- both found before anything is launched.  n_seq == 0 is GD_OK.  Nothing is kept between calls. */
+int gd_crai_sizes(gd_ctx* ctx, int32_t n_seq, const int64_t* seq_off,    /* [n_seq + 1] into the three arrays */
+                  const int64_t* aln_start, const int64_t* aln_span, const int32_t* slice_len,
+                  int64_t* tile_off,                                      /* out [n_seq + 1] */
+                  int32_t* status,                                        /* out [n_seq]: 0, or which panic */
+                  int64_t* sizes, size_t cap);                            /* NULL: count only */
 int gd_ingest_abort(gd_ctx* ctx);
 /* Page-locked host memory for the byte range handed to gd_ingest_bgzf (read the file
  * straight into it: the H2D copy then runs at PCIe speed instead of through a bounce

@@ -162,10 +162,12 @@ int gdh_covstats_finish(const int64_t* counts, const gdh_covstats_values* sizes,
  * with ".bam" replaced by ".bai".  0, or -1 without a usable index. */
 int gdh_bai_mapped(const char* bam_path, int64_t* mapped, size_t cap, size_t* n_ref);
 
-/* ---- `indexcov` (indexcov/indexcov.go, types.go): coverage of a cohort from the .bai linear indexes alone.
- * argv: -d DIR [-X X,Y] [-p REGEX] [-e] [-n] [-f ref.fai] a.bam|a.bai ...   Writes DIR/<DIR>-indexcov.bed.gz
- * (BGZF), .roc and .ped; no HTML, PNG or chart output.  .crai / .cram inputs and -c/--chrom are refused.  Returns the
- * exit code (1 on an error, 255 on a usage error); no .ped is left behind by a failed run. ------------------------- */
+/* ---- `indexcov` (indexcov/indexcov.go, types.go): coverage of a cohort from the .bai linear indexes or the .crai
+ * indexes alone.  argv: -d DIR [-X X,Y] [-p REGEX] [-e] [-n] [-f ref.fai] a.bam|a.bai|a.crai ...   Writes
+ * DIR/<DIR>-indexcov.bed.gz (BGZF), .roc and .ped; no HTML, PNG or chart output.  A cohort may mix the three kinds of
+ * input; the slices of the .crai indexes are tiled on the device (gd_crai_sizes) and then go where a .bai's tile sizes
+ * go.  A .crai first needs -f.  .cram inputs (pass the .crai) and -c/--chrom are refused.  Returns the exit code (1 on
+ * an error, 255 on a usage error); no .ped is left behind by a failed run. ----------------------------------------- */
 int gdh_indexcov_main(int argc, const char* const* argv);
 int gdh_indexcov_run(int argc, const char* const* argv);
 /* What `%.3g` prints for a float32 (goleft_amd/csrc/gd_round3g.hpp, the host instance of the code the device cell
@@ -180,13 +182,27 @@ int gdh_fmt3g(uint32_t cell, char* out, size_t cap);
 int gdh_indexcov_pcs(const int64_t* G, int n, int k, double* out, double* sigma);
 
 /* ---- `indexsplit` (indexsplit/indexsplit.go): N regions that hold about the same amount of data across a cohort,
- * from the .bai linear indexes alone.  argv: -n N [--fai FAI] [-p BED] a.bam|a.bai ...   The references are those of
- * the first input's header when it is a .bam, else the .fai's.  Rows `chrom \t start \t end \t %.2f sum \t splits`.
- * .crai / .cram inputs are refused.  Returns the exit code (1 on an error -- an index that cannot be read, a cohort
+ * from the .bai linear indexes or the .crai indexes alone.  argv: -n N [--fai FAI] [-p BED] a.bam|a.bai|a.crai ...   The
+ * references are those of the first input's header when it is a .bam, else the .fai's.  Rows
+ * `chrom \t start \t end \t %.2f sum \t splits`.  .crai inputs are tiled on the device as for indexcov; .cram inputs are
+ * refused (pass the .crai).  Returns the exit code (1 on an error -- an index that cannot be read, a cohort
  * without data -- with no row written; 255 on a usage error). ---------------------------------------------------- */
 int gdh_indexsplit_main(int argc, const char* const* argv);
 /* Same, writing to out_path (NULL = stdout). */
 int gdh_indexsplit_run(int argc, const char* const* argv, const char* out_path);
+
+/* ---- the slices of a .crai (indexcov/crai/crai.go:129-192 ReadIndex), pure CPU: what `indexcov` and `indexsplit` read
+ * from a CRAM index before the device tiles it.  The file is gzip (any number of members) of lines of six tab-separated
+ * integers; per reference (seqID 0 .. *n_refs - 1) the alnStart, alnSpan and sliceLen of its slices in file order:
+ * reference r owns [ref_off[r], ref_off[r + 1]) of the three arrays (ref_off has room for cap_refs + 1 entries).  As the
+ * reference reads it: lines are trimmed, seqID -1 is skipped, a negative alnSpan ends the reading, a last line without
+ * its newline is not seen.  Returns 0; -3 when cap_refs or cap_slices is too small (*n_refs and *n_slices say what is
+ * needed; call with 0, 0 and ref_off NULL to ask); -2 when the file is refused: *line is the 1-based line (0: it cannot be opened or is
+ * not gzip) and msg says why -- a field count other than 6, an unparsable number, a seqID below -1 or above 2^20 - 1,
+ * |alnStart| or alnSpan above 2^31 - 1, a sliceLen outside int32; -1 on bad arguments. --------------------------------- */
+int gdh_crai_read(const char* path, size_t cap_refs, size_t cap_slices, int64_t* ref_off, int64_t* aln_start,
+                  int64_t* aln_span, int32_t* slice_len, size_t* n_refs, size_t* n_slices, int64_t* line, char* msg,
+                  size_t cap_msg);
 
 /* ---- `samplename` (samplename/samplename.go): the SM values of a BAM header's @RG lines, one per line in order of
  * first appearance (an empty line when there is none).  argv: [-e] x.bam; -e: exit 2 with the reference's message
