@@ -242,6 +242,7 @@ static int compute_enqueue(gd_ctx* c, ComputeState& S)
         }
         // the look-back IS the largest span (exact, known since the records arrived)
         job.lookback = std::max(64, (int32_t)((S.chunk_span + 63) & ~63));
+        S.used_lookback = job.lookback;                  // (gd_stats.lookback: what the tile table was built with)
     }
     // compute_prepare built the table for its totals; this is the one that is uploaded: the long-read pointers in it
     // only exist after ck_tids, and under GD_PATH_AUTO a later attempt may be the first to need them
@@ -330,7 +331,6 @@ static int compute_complete(gd_ctx* c, ComputeState& S)
     const gd::Counters k = *c->h_counters;
     if (chunk) {
         c->stats.max_span_seen = S.chunk_span;           // over all records with ops (the filter is applied per tile)
-        S.used_lookback = S.chunk_span;
     } else if (scatter) {
         if (k.pad1 != 0) return fail(c, GD_E_HIP, "scan look-back timed out (internal error)");
     } else {

@@ -7,10 +7,12 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle as po
+from tests import helpers as H
+from tests import long_shapes as LS
 
 pytestmark = pytest.mark.gpu
 
-M, I, D, N, S, H, P, EQ, X = 0, 1, 2, 3, 4, 5, 6, 7, 8
+M, I, D, N, S, HC, P, EQ, X = 0, 1, 2, 3, 4, 5, 6, 7, 8
 
 
 def cg(*ops):
@@ -43,9 +45,19 @@ def check(r, L, W=100, **params):
         pad = np.zeros(nw * W, np.int64)
         pad[:L] = want
         assert np.array_equal(sums, pad.reshape(nw, W).sum(1))
+        owin = H.oracle_windows(want, W)
+        oruns = H.oracle_runs(want, params.get("min_cov", 4), params.get("max_mean_depth", 0), po.step_for(W))
+        assert np.array_equal(sums, owin[0]) and np.array_equal(mins, owin[1])
+        assert np.array_equal(eng.callable_runs(0), oruns)
+        # the deletion-list pass against the routing model of tests/long_shapes.py
+        st, model = eng.stats(), LS.stats_of_reads(r)
+        assert (st.n_deletions, st.max_span_seen) == (model["n_deletions"], model["max_span_seen"])
         eng.rebuild_derived()                              # the same structures again, into the block they occupy
         eng.compute()
         assert np.array_equal(eng.perbase(0), want)
+        assert np.array_equal(eng.windows(0)[1], owin[1]) and np.array_equal(eng.callable_runs(0), oruns)
+        st = eng.stats()
+        assert (st.n_deletions, st.max_span_seen) == (model["n_deletions"], model["max_span_seen"])
     return want
 
 

@@ -4,7 +4,8 @@ paths, the one-ballot any_noisy shortcut, the generic kernel's batches and per-w
 tiles, the read-back's 4096 boundaries and the boundary list's growth.  The shapes come from tests/tile_shapes.py;
 tests/test_tile_shapes.py shows on the CPU that each one reaches its edge.
 
-Every case runs through the C ABI on every tile route and is compared with the C oracle, exactly: the whole per-base
+Every case runs through the C ABI on every tile route -- the window, class and phase C shapes also on the long-read tile
+kernel, which instantiates the same phase B / C code with its own LDS layout and carry -- and is compared with the C oracle, exactly: the whole per-base
 vector where the route keeps one, window sums and minima, the class runs of every contig, and for one case per family
 --bed regions around the crafted positions.  gd_stats says which kernel ran; n_slow_tiles, n_tiles, n_runs, reruns,
 lookback and max_span_seen are held against the routing model.  Every case is computed twice on its context (the
@@ -24,7 +25,17 @@ ROUTES = {
     "generic": ("push", True, False, {"OPT_FAST_KERNEL": 0}, "TK_GENERIC"),  # gd_tile_kernel for every tile
     "generic-misaligned": (("pos",), True, False, {}, "TK_GENERIC"),         # `pos` at element offset 1 of its tensor
     "tile-sums": (("pos",), False, True, {}, "TK_TILE_SUMS"),                # gd_tile_sums_kernel (window cases, W >= 32)
+    "long": ("push", True, False, {"path": "PATH_CHUNK"}, "TK_LONG"),        # gd_ltile2_kernel<1>: the same phase B / C code
+    "long-windows": ("push", False, False, {"path": "PATH_CHUNK"}, "TK_LONG"),   # gd_ltile2_kernel<2>: no per-base stores
 }
+LONG_FAMILIES = ("windows", "classes", "phase-c", "phase-c-large")
+
+
+def long_stats(c):
+    """(lookback, max_span_seen) of a case on the long-read path: the largest span of ALL reads with ops (the filter is
+    applied per tile), rounded up to 64 and at least 64; the hint does not matter."""
+    span = max([int(H.ref_span(c.get(t)).max()) for t in range(len(c.lengths)) if c.lengths[t] > 0 and c.get(t).n] + [0])
+    return max(64, (span + 63) & ~63), span
 
 
 def first_diff(got, want):
@@ -64,7 +75,7 @@ def regions_of(c):
 def configure(eng, c, route):
     from goleft_amd import engine as E
     how, perbase, sums_only, opts, _ = ROUTES[route]
-    eng.set_path(E.PATH_TILE)
+    eng.set_path(getattr(E, opts.get("path", "PATH_TILE")))
     eng.set_outputs(perbase=perbase, sums_only=sums_only)
     eng.set_option(E.OPT_FAST_KERNEL, opts.get("OPT_FAST_KERNEL", 1))
     eng.set_option(E.OPT_INGEST_INDEX, int(c.index))
@@ -117,6 +128,8 @@ def check(eng, c, route, attempt, with_regions):
             bad.append(same(rr[k], H.oracle_runs(d, c.min_cov, c.max_mean_depth, 1 << 62, a), ctx, "region runs", run_start))
     # the routing model
     lookback, lb_reruns, span = TS.lookback_of(c, attempt)
+    if route.startswith("long"):
+        (lookback, span), lb_reruns = long_stats(c), 0
     want = dict(n_tiles=c.n_tiles, lookback=lookback, max_span_seen=span)
     if not sums_only:
         want["n_runs"] = TS.boundaries(c)[0]
@@ -138,7 +151,9 @@ def cases_for(family, route):
 
 
 # (the sums-only tile kernel runs the window cases only)
-PAIRS = [(f, r) for f in TS.FAMILIES for r in ROUTES if r != "tile-sums" or f == "windows"]
+# ... and the long-read tile kernel the families that are about phase B and phase C
+PAIRS = [(f, r) for f in TS.FAMILIES for r in ROUTES
+         if (f == "windows" if r == "tile-sums" else f in LONG_FAMILIES if r.startswith("long") else True)]
 
 
 @pytest.mark.parametrize("family,route", PAIRS)
