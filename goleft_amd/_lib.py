@@ -120,6 +120,9 @@ SYMBOLS = {
     "gd_indexsplit_sums": (C.c_int, [_P, _P, C.c_size_t]),
     "gd_indexsplit_timing": (C.c_int, [_P, _P, C.c_size_t]),
     "gd_crai_sizes": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_size_t]),
+    "gd_emdepth": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P, _P, _P]),
+    "gd_emdepth_cells": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P, _P, _P, _P]),
+    "gd_emdepth_timing": (C.c_int, [_P, _P, C.c_size_t]),
     "gd_ingest_finish": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_uint64)]),
     "gd_ingest_decode": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_uint64)]),
     "gd_ingest_decode_part": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_size_t, C.c_uint64, C.c_uint, C.c_double,

@@ -261,6 +261,7 @@ struct gd_ctx {
     CovState* cov = nullptr;                                   // gd_covstats_*: the sampling state and its buffers (gd_api_covstats.inc)
     IcState* ic = nullptr;                                     // gd_indexcov_*: the cohort's tile sizes and results (gd_api_indexcov.inc)
     IsState* isp = nullptr;                                    // gd_indexsplit_*: the cohort's cell sums (gd_api_indexsplit.inc)
+    double em_secs[3] = {0, 0, 0};                             // gd_emdepth*: upload, kernel, read-back of the last call (gd_api_emdepth.inc)
     uint8_t* h_walk = nullptr; size_t cap_walk = 0;            // gd_ingest_decode, gd_covstats_decode: per-segment tables of the record walk (page-locked host memory
                                                                // the walk kernels read and write over the link: no copy command)
     uint32_t* h_ingest = nullptr;                              // page-locked: d_ingest's words as the host reads them (gd_copy_words_kernel)

@@ -297,6 +297,40 @@ class DepthEngine:
                                                C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    def _emdepth_outputs(self, rows: int, n: int):
+        return (np.empty((rows, 9), np.float64), np.empty(rows, np.uint8), np.empty((rows, n), np.uint8),
+                np.empty((rows, n), np.float32))
+
+    def emdepth(self, depths):
+        """emdepth.EMDepth per row of a [rows][samples] float32 matrix (finite, >= 0; 1 or 3 .. 4096 samples):
+        (lambda float64 [rows, 9], iters uint8 [rows], cn uint8 [rows, samples], log2fc float32 [rows, samples])."""
+        d = np.ascontiguousarray(depths, np.float32)
+        assert d.ndim == 2
+        rows, n = d.shape
+        lam, it, cn, fc = self._emdepth_outputs(rows, n)
+        self._chk(self._lib.gd_emdepth(self._ctx, d.ctypes.data if d.size else None, rows, n, lam.ctypes.data,
+                                       it.ctypes.data, cn.ctypes.data, fc.ctypes.data))
+        return lam, it, cn, fc
+
+    def emdepth_cells(self, dptr: int, rows: int, n_samples: int, scale=None):
+        """The same for int64 cells in HBM (depthwed_device's pointer): the depth of a cell is float32(cell), times
+        scale[sample] in float32 when a scale is given.  Returns what emdepth returns."""
+        lam, it, cn, fc = self._emdepth_outputs(rows, n_samples)
+        s = None
+        if scale is not None:
+            s = np.ascontiguousarray(scale, np.float32)
+            assert s.shape == (n_samples,)
+        self._chk(self._lib.gd_emdepth_cells(self._ctx, C.c_void_p(dptr), rows, n_samples,
+                                             s.ctypes.data if s is not None else None, lam.ctypes.data, it.ctypes.data,
+                                             cn.ctypes.data, fc.ctypes.data))
+        return lam, it, cn, fc
+
+    def emdepth_timing(self):
+        """Seconds of the last emdepth call: (upload, kernel, read-back)."""
+        t = (C.c_double * 3)()
+        self._chk(self._lib.gd_emdepth_timing(self._ctx, t, 3))
+        return tuple(t)
+
     def seq_load(self, seq) -> None:
         """One contig's reference bases (bytes / uint8 array, FASTA line breaks removed) into HBM."""
         a = np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else np.ascontiguousarray(seq, np.uint8)

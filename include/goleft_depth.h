@@ -39,6 +39,7 @@ extern "C" {
 
 /* GD_ABI_VERSION changes when an existing entry point or structure changes; GD_ABI_REVISION counts the releases that only
  * ADDED entry points since then (revision 1: gd_indexcov_*; 2: gd_indexsplit_*; 3: gd_crai_sizes).  A caller built against (15, r) runs on any (15, r' >= r).
+ * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing were added without a revision; look them up by symbol.
  * Why indexcov did not become version 16: nothing that existed changed, so callers of ABI 15 need not be turned away, and
  * tests/test_host_cpu.py holds gd_abi_version() to 15 until something does change. */
 #define GD_ABI_VERSION 15
@@ -645,6 +646,27 @@ int gd_crai_sizes(gd_ctx* ctx, int32_t n_seq, const int64_t* seq_off,    /* [n_s
                   int64_t* tile_off,                                      /* out [n_seq + 1] */
                   int32_t* status,                                        /* out [n_seq]: 0, or which panic */
                   int64_t* sizes, size_t cap);                            /* NULL: count only */
+/* ---- emdepth.EMDepth (emdepth/emdepth.go:117-206, :250-304) per row of a sites x samples depth matrix ----
+ * For every row: the copy-number centres lambda[0..8] fitted by the reference's EM (median start, at most ten
+ * classify-and-average passes), the number of passes run (1 .. 10), every cell's copy number (Type with adjustCN:
+ * 0 .. 8, and 9 for a depth above lambda[8], as the reference's code -- not its unit test -- has it) and every cell's
+ * log2(depth / lambda[2]) as float32 (-inf for a depth of 0).  Quirk for quirk: the median of an even row is
+ * (b[N/2] + b[N/2 + 1]) / 2, and the centres are searched with the reference's binary search although they are not always
+ * ascending.  n_samples is 1 or 3 .. 4096 (the reference panics on 0 and 2), GD_E_RANGE otherwise.  Any output may be
+ * NULL.  n_rows == 0 is GD_OK.  Nothing is kept between calls; everything is checked before anything runs.
+ *   gd_emdepth        depths: host float32 [n_rows][n_samples], each finite and >= 0 (GD_E_INVALID otherwise)
+ *   gd_emdepth_cells  d_cells: DEVICE int64 [n_rows][n_samples] as gd_depthwed_device leaves them (non-negative); the
+ *                     depth of a cell is (float)cell, and with scale (host [n_samples], finite and >= 0, or NULL)
+ *                     (float)cell * scale[s] in float32: one rounding each.  The matrix does not leave HBM.
+ * Rows whose depths are integers (times one power of two) give lambda bit for bit as the reference's float64 loop does;
+ * otherwise the bin sums are taken in another order and lambda agrees to about n_samples * 2^-53 relative.
+ * gd_emdepth_timing: seconds of the last call (measurement only): upload, kernel, read-back.  Fills min(n, 3) values. */
+int gd_emdepth(gd_ctx* ctx, const float* depths, size_t n_rows, int n_samples,
+               double* lambda /* [n_rows][9] */, uint8_t* iters /* [n_rows] */, uint8_t* cn /* [n_rows][n_samples] */,
+               float* log2fc /* [n_rows][n_samples] */);
+int gd_emdepth_cells(gd_ctx* ctx, const int64_t* d_cells, size_t n_rows, int n_samples, const float* scale,
+                     double* lambda, uint8_t* iters, uint8_t* cn, float* log2fc);
+int gd_emdepth_timing(gd_ctx* ctx, double* out, size_t n);
 int gd_ingest_abort(gd_ctx* ctx);
 /* Page-locked host memory for the byte range handed to gd_ingest_bgzf (read the file
  * straight into it: the H2D copy then runs at PCIe speed instead of through a bounce
