@@ -4,7 +4,7 @@
 // gd_create / gd_destroy, the setters (stream, parameters, path, outputs, contigs, selection), options, statistics and
 // timing.  The rest of the ABI is in the gd_api_*.inc files included at the end, in this order: records (pinned
 // staging ring + copy stream, records host -> HBM, HBM-resident per-contig record streams), compute (route, launch
-// sequencing, look-back), results (read-back), aux, ingest, covstats, indexcov, indexsplit, crai, emdepth, comm.
+// sequencing, look-back), results (read-back), aux, ingest, covstats, indexcov, indexsplit, crai, emdepth, emcnv, comm.
 // Replaces gargs' process.Runner + the samtools child + the callback's parse loop of `goleft depth`
 // (depth/depth.go:392-394, :45, :282-325).
 #include "../../include/goleft_depth.h"
@@ -130,7 +130,7 @@ int gd_create(int device_id, gd_ctx** out)
     return GD_OK;
 }
 
-namespace { static void drop_pool(gd_ctx* c); static void cov_drop(gd_ctx* c); static void ic_drop(gd_ctx* c); static void is_drop(gd_ctx* c); }
+namespace { static void drop_pool(gd_ctx* c); static void cov_drop(gd_ctx* c); static void ic_drop(gd_ctx* c); static void is_drop(gd_ctx* c); static void ec_drop(gd_ctx* c); }
 
 void gd_destroy(gd_ctx* c)
 {
@@ -142,6 +142,7 @@ void gd_destroy(gd_ctx* c)
     cov_drop(c);
     ic_drop(c);
     is_drop(c);
+    ec_drop(c);
     (void)gd_comm_destroy(c);
     for (hipEvent_t e : c->comm_ev) if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < 2; ++k) {
@@ -408,6 +409,7 @@ int gd_kernel_ms(gd_ctx* c, int id, float* ms)
 #include "gd_api_indexsplit.inc"
 #include "gd_api_crai.inc"
 #include "gd_api_emdepth.inc"
+#include "gd_api_emcnv.inc"
 #include "gd_api_comm.inc"
 
 }  // extern "C"

@@ -1,0 +1,384 @@
+// gd_api_emcnv.inc -- emdepth.Cache on the device (part of gd_api.hip, inside extern "C"; after gd_api_emdepth.inc, whose
+// checks and launch it uses): gd_emcnv_begin / add / add_cells / finish / read / end / timing.  The kernels are
+// gd_emcnv.hpp's.  Between the blocks the context keeps, on the device: the positions, one member bit per cell, the
+// members' values (depth, cn, log2fc: the arena), each row's offset into it, and the states of the last row.  Everything
+// that joins members into CNVs runs in gd_emcnv_finish over those, so the result cannot depend on the blocks.
+
+namespace {
+
+struct EcState {
+    int n = 0, words = 0;
+    size_t R = 0;                                // rows so far
+    uint64_t members = 0;                        // ... and their members
+    int cur = 0;                                 // carry[cur]: the states of row R - 1
+    bool finished = false;
+    uint64_t n_cnvs = 0, n_members = 0;
+    double secs[4] = {0, 0, 0, 0};               // upload, EM kernel, CNV kernels, read-back
+    // kept for the whole run (grow-only)
+    uint8_t* carry[2] = {nullptr, nullptr};
+    uint32_t* start = nullptr; size_t cap_start = 0;
+    uint32_t* end = nullptr; size_t cap_end = 0;
+    uint64_t* mbits = nullptr; size_t cap_mbits = 0;
+    uint64_t* rowoff = nullptr; size_t cap_rowoff = 0;
+    float* m_depth = nullptr; size_t cap_m_depth = 0;
+    uint8_t* m_cn = nullptr; size_t cap_m_cn = 0;
+    float* m_fc = nullptr; size_t cap_m_fc = 0;
+    // a block's temporaries (grow-only, nothing kept in them)
+    float* in = nullptr; size_t cap_in = 0;
+    float* scale = nullptr;
+    double* lambda = nullptr; size_t cap_lambda = 0;
+    uint8_t* cn = nullptr; size_t cap_cn = 0;
+    float* fc = nullptr; size_t cap_fc = 0;
+    uint32_t* rowcnt = nullptr; size_t cap_rowcnt = 0;
+    uint64_t* tiles = nullptr; size_t cap_tiles = 0;
+    uint64_t* total = nullptr;                   // one word: a scan's total
+    // the result (gd_emcnv_finish)
+    uint32_t *c_sample = nullptr, *c_psize = nullptr, *c_emit = nullptr, *c_count = nullptr, *c_last = nullptr;
+    uint64_t* member_off = nullptr;
+    uint32_t* o_row = nullptr; float* o_depth = nullptr; uint8_t* o_cn = nullptr; float* o_fc = nullptr;
+    ~EcState()
+    {
+        for (void* p : {(void*)carry[0], (void*)carry[1], (void*)start, (void*)end, (void*)mbits, (void*)rowoff, (void*)m_depth,
+                        (void*)m_cn, (void*)m_fc, (void*)in, (void*)scale, (void*)lambda, (void*)cn, (void*)fc, (void*)rowcnt,
+                        (void*)tiles, (void*)total, (void*)c_sample, (void*)c_psize, (void*)c_emit, (void*)c_count, (void*)c_last,
+                        (void*)member_off, (void*)o_row, (void*)o_depth, (void*)o_cn, (void*)o_fc})
+            if (p) (void)hipFree(p);
+    }
+};
+
+static void ec_drop(gd_ctx* c)
+{
+    if (!c->ec) return;
+    (void)hipStreamSynchronize(c->stream);
+    delete c->ec;
+    c->ec = nullptr;
+}
+
+extern "C++" {
+// room for `need` elements, the first `used` kept (all on the context's stream)
+template <typename Tp>
+static int ec_grow(gd_ctx* c, Tp** p, size_t* cap, size_t need, size_t used)
+{
+    if (need <= *cap && *p) return GD_OK;
+    size_t ncap = std::max(need, *cap + *cap / 2);
+    if (ncap == 0) ncap = 1;
+    Tp* np = nullptr;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&np), ncap * sizeof(Tp)));
+    if (*p) {
+        hipError_t e = hipSuccess;
+        if (used) e = hipMemcpyAsync(np, *p, used * sizeof(Tp), hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(np);
+            HIPCHK(c, e);
+        }
+        HIPCHK(c, hipFree(*p));
+    }
+    *p = np;
+    *cap = ncap;
+    return GD_OK;
+}
+}  // extern "C++"
+
+// buffers of gd_emcnv_finish that do not outlive it
+struct EcTemps {
+    std::vector<void*> v;
+    ~EcTemps() { for (void* p : v) (void)hipFree(p); }
+};
+
+extern "C++" {
+template <typename Tp>
+static int ec_alloc(gd_ctx* c, Tp** p, size_t count, EcTemps* owner = nullptr, bool zero = false)
+{
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(Tp)));
+    if (owner) owner->v.push_back(*p);
+    if (zero) HIPCHK(c, hipMemsetAsync(*p, 0, (count ? count : 1) * sizeof(Tp), c->stream));
+    return GD_OK;
+}
+}  // extern "C++"
+
+// workgroups of the two per-block kernels, which stride over the rows
+static unsigned ec_grid(uint64_t items, uint64_t per_wg)
+{
+    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + per_wg - 1) / per_wg, (uint64_t)gd::EMCNV_MAX_GRID));
+}
+
+// workgroups that cover `items`, `per_wg` each (the callers' bounds keep it below 2^31)
+static unsigned ec_cover(uint64_t items, uint64_t per_wg) { return (unsigned)std::max<uint64_t>(1, (items + per_wg - 1) / per_wg); }
+
+// out[i] = base + in[0] + .. + in[i - 1] for i < n; d_total[0] = base + all (both on the device); n >= 1
+static int ec_scan(gd_ctx* c, EcState& s, const uint32_t* in, uint64_t n, uint64_t base, uint64_t* out, uint64_t* d_total)
+{
+    const uint64_t tiles = (n + gd::EMCNV_SCAN_TILE - 1) / gd::EMCNV_SCAN_TILE;
+    if (int r = ec_grow(c, &s.tiles, &s.cap_tiles, (size_t)tiles, 0)) return r;
+    hipLaunchKernelGGL(gd::gd_emcnv_scan_tile_kernel, dim3((unsigned)tiles), dim3(gd::EMCNV_WG), 0, c->stream, in, n, s.tiles);
+    hipLaunchKernelGGL(gd::gd_emcnv_scan_top_kernel, dim3(1), dim3(gd::EMCNV_WG), 0, c->stream, s.tiles, tiles, base, d_total);
+    hipLaunchKernelGGL(gd::gd_emcnv_scan_apply_kernel, dim3((unsigned)tiles), dim3(gd::EMCNV_WG), 0, c->stream, in, n,
+                       (const uint64_t*)s.tiles, out);
+    HIPCHK(c, hipGetLastError());
+    return GD_OK;
+}
+
+static int ec_fetch(gd_ctx* c, const uint64_t* d_word, uint64_t* out)
+{
+    HIPCHK(c, hipMemcpyAsync(out, d_word, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return GD_OK;
+}
+
+// One block whose rows are on the device.  The state moves on only when everything has run.
+static int ec_add(gd_ctx* c, EcState& s, bool cells, const void* d_in, const float* d_scale, size_t B, const uint32_t* starts,
+                  const uint32_t* ends, uint8_t* cn_out)
+{
+    const size_t N = (size_t)s.n, W = (size_t)s.words, R = s.R;
+    double t0 = ing_now();
+    if (int r = ec_grow(c, &s.start, &s.cap_start, R + B, R)) return r;
+    if (int r = ec_grow(c, &s.end, &s.cap_end, R + B, R)) return r;
+    if (int r = ec_grow(c, &s.mbits, &s.cap_mbits, (R + B) * W, R * W)) return r;
+    if (int r = ec_grow(c, &s.rowoff, &s.cap_rowoff, R + B, R)) return r;
+    if (int r = ec_grow(c, &s.lambda, &s.cap_lambda, B * gd::EM_CENTRES, 0)) return r;
+    if (int r = ec_grow(c, &s.cn, &s.cap_cn, B * N, 0)) return r;
+    if (int r = ec_grow(c, &s.fc, &s.cap_fc, B * N, 0)) return r;
+    if (int r = ec_grow(c, &s.rowcnt, &s.cap_rowcnt, B, 0)) return r;
+    HIPCHK(c, hipMemcpyAsync(s.start + R, starts, B * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(s.end + R, ends, B * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    s.secs[0] += ing_now() - t0;
+
+    double em_s = 0;
+    if (int r = em_launch(c, cells, d_in, d_scale, B, s.n, s.lambda, nullptr, s.cn, s.fc, &em_s)) return r;
+    s.secs[1] += em_s;
+
+    t0 = ing_now();
+    gd::EmcnvBlock j{};
+    j.cells = d_in; j.scale = d_scale; j.lambda = s.lambda; j.cn = s.cn; j.log2fc = s.fc;
+    j.n_rows = (int64_t)B; j.row0 = (int64_t)R; j.n = s.n; j.words = s.words;
+    j.carry_in = s.carry[s.cur]; j.carry_out = s.carry[s.cur ^ 1];
+    j.mbits = s.mbits; j.rowcnt = s.rowcnt; j.rowoff = s.rowoff;
+    const dim3 grid(ec_grid(B, gd::EMCNV_WAVES)), wg(gd::EMCNV_WG);
+    if (cells) hipLaunchKernelGGL(gd::gd_emcnv_member_kernel<int64_t>, grid, wg, 0, c->stream, j);
+    else hipLaunchKernelGGL(gd::gd_emcnv_member_kernel<float>, grid, wg, 0, c->stream, j);
+    HIPCHK(c, hipGetLastError());
+    if (int r = ec_scan(c, s, s.rowcnt, B, s.members, s.rowoff + R, s.total)) return r;
+    uint64_t total = 0;
+    if (int r = ec_fetch(c, s.total, &total)) return r;
+    if (total > s.members) {
+        if (int r = ec_grow(c, &s.m_depth, &s.cap_m_depth, (size_t)total, (size_t)s.members)) return r;
+        if (int r = ec_grow(c, &s.m_cn, &s.cap_m_cn, (size_t)total, (size_t)s.members)) return r;
+        if (int r = ec_grow(c, &s.m_fc, &s.cap_m_fc, (size_t)total, (size_t)s.members)) return r;
+        j.m_depth = s.m_depth; j.m_cn = s.m_cn; j.m_fc = s.m_fc;
+        if (cells) hipLaunchKernelGGL(gd::gd_emcnv_gather_kernel<int64_t>, grid, wg, 0, c->stream, j);
+        else hipLaunchKernelGGL(gd::gd_emcnv_gather_kernel<float>, grid, wg, 0, c->stream, j);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    s.secs[2] += ing_now() - t0;
+    if (cn_out) {
+        t0 = ing_now();
+        HIPCHK(c, hipMemcpyAsync(cn_out, s.cn, B * N, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        s.secs[3] += ing_now() - t0;
+    }
+    s.R = R + B;
+    s.members = total;
+    s.cur ^= 1;
+    return GD_OK;
+}
+
+#define EC_STATE(c)                                                                                       \
+    if (!(c)) return GD_E_INVALID;                                                                        \
+    if (!(c)->ec) return fail((c), GD_E_STATE, "gd_emcnv_begin has not been called");                     \
+    if (int r_ = set_device(c)) return r_;                                                                \
+    EcState& s = *(c)->ec
+
+static int ec_check_add(gd_ctx* c, EcState& s, size_t n_rows, const void* rows, const uint32_t* starts, const uint32_t* ends)
+{
+    if (s.finished) return fail(c, GD_E_STATE, "emcnv: gd_emcnv_finish has run: gd_emcnv_begin starts another");
+    if (n_rows == 0) return GD_OK;
+    if (!rows || !starts || !ends) return GD_E_INVALID;
+    // (F holds R + 1 in 32 bits)
+    if (n_rows > 0xfffffffdull - s.R) return fail(c, GD_E_RANGE, "emcnv: more than 2^32 - 3 rows");
+    if (n_rows > (SIZE_MAX / sizeof(double)) / ((size_t)s.n > gd::EM_CENTRES ? (size_t)s.n : gd::EM_CENTRES))
+        return fail(c, GD_E_RANGE, "emcnv: %zu rows of %d samples do not fit an allocation", n_rows, s.n);
+    return GD_OK;
+}
+
+}  // namespace
+
+int gd_emcnv_begin(gd_ctx* c, int n_samples)
+{
+    if (!c) return GD_E_INVALID;
+    if (int r = em_check_n(c, n_samples)) return r;      // (a refused begin leaves an earlier state alone)
+    if (int r = set_device(c)) return r;
+    ec_drop(c);
+    c->ec = new (std::nothrow) EcState();
+    if (!c->ec) return GD_E_NOMEM;
+    EcState& s = *c->ec;
+    auto body = [&]() -> int {
+        s.n = n_samples;
+        s.words = (n_samples + 63) / 64;
+        for (auto& p : s.carry) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&p), (size_t)s.words * 64));
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s.scale), (size_t)n_samples * sizeof(float)));
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s.total), sizeof(uint64_t)));
+        return GD_OK;
+    };
+    const int rc = body();
+    if (rc != GD_OK) ec_drop(c);
+    return rc;
+}
+
+int gd_emcnv_add(gd_ctx* c, const float* depths, size_t n_rows, const uint32_t* starts, const uint32_t* ends, uint8_t* cn_out)
+{
+    EC_STATE(c);
+    if (int r = ec_check_add(c, s, n_rows, depths, starts, ends)) return r;
+    if (n_rows == 0) return GD_OK;
+    const size_t N = (size_t)s.n;
+    for (size_t i = 0; i < n_rows * N; ++i)
+        if (!(depths[i] >= 0.0f) || !std::isfinite(depths[i]))
+            return fail(c, GD_E_INVALID, "emcnv: the depth of row %zu, sample %zu is not a finite number >= 0", i / N, i % N);
+    const double t0 = ing_now();
+    if (int r = ec_grow(c, &s.in, &s.cap_in, n_rows * N, 0)) return r;
+    HIPCHK(c, hipMemcpyAsync(s.in, depths, n_rows * N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    s.secs[0] += ing_now() - t0;
+    return ec_add(c, s, false, s.in, nullptr, n_rows, starts, ends, cn_out);
+}
+
+int gd_emcnv_add_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, const float* scale, const uint32_t* starts,
+                       const uint32_t* ends, uint8_t* cn_out)
+{
+    EC_STATE(c);
+    const size_t N = (size_t)s.n;
+    if (scale)
+        for (size_t k = 0; k < N; ++k)
+            if (!(scale[k] >= 0.0f) || !std::isfinite(scale[k]))
+                return fail(c, GD_E_INVALID, "emcnv: the scale of sample %zu is not a finite number >= 0", k);
+    if (int r = ec_check_add(c, s, n_rows, d_cells, starts, ends)) return r;
+    if (n_rows == 0) return GD_OK;
+    if (scale) {
+        const double t0 = ing_now();
+        HIPCHK(c, hipMemcpyAsync(s.scale, scale, N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        s.secs[0] += ing_now() - t0;
+    }
+    return ec_add(c, s, true, d_cells, scale ? s.scale : nullptr, n_rows, starts, ends, cn_out);
+}
+
+int gd_emcnv_finish(gd_ctx* c, uint64_t* n_cnvs, uint64_t* n_members)
+{
+    EC_STATE(c);
+    if (!s.finished && s.R > 0) {
+        const double t0 = ing_now();
+        const size_t R = s.R, W = (size_t)s.words, pad = W * 64;
+        const size_t n_chunks = (R + gd::EMCNV_CHUNK - 1) / gd::EMCNV_CHUNK;
+        EcTemps tmp;
+        gd::EmcnvJob j{};
+        j.R = (uint32_t)R; j.n = s.n; j.words = s.words; j.n_chunks = (uint32_t)n_chunks;
+        j.start = s.start; j.end = s.end; j.mbits = s.mbits; j.rowoff = s.rowoff;
+        j.m_depth = s.m_depth; j.m_cn = s.m_cn; j.m_fc = s.m_fc;
+        uint32_t* ecnt = nullptr;
+        uint64_t* eoff = nullptr;
+        const size_t n1 = (R + 63) / 64, n2 = (n1 + 63) / 64;
+        if (int r = ec_alloc(c, &j.F, R, &tmp)) return r;
+        if (int r = ec_alloc(c, &j.span1, n1 * 4, &tmp)) return r;
+        if (int r = ec_alloc(c, &j.span2, n2 * 4, &tmp)) return r;
+        if (int r = ec_alloc(c, &j.first, n_chunks * pad, &tmp)) return r;
+        if (int r = ec_alloc(c, &j.last, n_chunks * pad, &tmp)) return r;
+        if (int r = ec_alloc(c, &j.lastF, n_chunks * pad, &tmp)) return r;
+        if (int r = ec_alloc(c, &j.tail, n_chunks * pad, &tmp)) return r;
+        if (int r = ec_alloc(c, &j.psize, R + 1, &tmp, true)) return r;
+        if (int r = ec_alloc(c, &ecnt, R + 1, &tmp, true)) return r;
+        if (int r = ec_alloc(c, &j.ebits, (R + 1) * W, &tmp, true)) return r;
+        if (int r = ec_alloc(c, &eoff, R + 1, &tmp)) return r;
+        j.ecnt = ecnt; j.eoff = eoff;
+        const dim3 wg(gd::EMCNV_WG), walk(ec_cover(n_chunks * W, gd::EMCNV_WAVES));
+        hipLaunchKernelGGL(gd::gd_emcnv_span_kernel<1>, dim3(ec_cover(n1, gd::EMCNV_WAVES)), wg, 0, c->stream, j);
+        hipLaunchKernelGGL(gd::gd_emcnv_span_kernel<2>, dim3(ec_cover(n2, gd::EMCNV_WAVES)), wg, 0, c->stream, j);
+        hipLaunchKernelGGL(gd::gd_emcnv_gap_kernel, dim3(ec_cover(R, gd::EMCNV_WG)), wg, 0, c->stream, j);
+        hipLaunchKernelGGL(gd::gd_emcnv_chunk_kernel, walk, wg, 0, c->stream, j);
+        hipLaunchKernelGGL(gd::gd_emcnv_carry_kernel, dim3((unsigned)((pad + gd::EMCNV_WG - 1) / gd::EMCNV_WG)), wg, 0, c->stream, j);
+        hipLaunchKernelGGL(gd::gd_emcnv_emit_kernel<0>, walk, wg, 0, c->stream, j);
+        HIPCHK(c, hipGetLastError());
+        if (int r = ec_scan(c, s, ecnt, R + 1, 0, eoff, s.total)) return r;
+        uint64_t n_c = 0, n_m = 0;
+        if (int r = ec_fetch(c, s.total, &n_c)) return r;
+        if (n_c > 0x7fffffffull * gd::EMCNV_WAVES) return fail(c, GD_E_RANGE, "emcnv: more than 2^33 - 4 CNVs");
+        // the result is the state's only once it is whole
+        EcTemps res;
+        uint32_t *c_sample, *c_psize, *c_emit, *c_count, *c_last, *o_row = nullptr;
+        uint64_t* member_off;
+        float *o_depth = nullptr, *o_fc = nullptr;
+        uint8_t* o_cn = nullptr;
+        if (int r = ec_alloc(c, &c_sample, n_c, &res)) return r;
+        if (int r = ec_alloc(c, &c_psize, n_c, &res)) return r;
+        if (int r = ec_alloc(c, &c_emit, n_c, &res)) return r;
+        if (int r = ec_alloc(c, &c_count, n_c, &res)) return r;
+        if (int r = ec_alloc(c, &c_last, n_c, &res)) return r;
+        if (int r = ec_alloc(c, &member_off, n_c + 1, &res, true)) return r;
+        if (n_c > 0) {
+            j.c_sample = c_sample; j.c_psize = c_psize; j.c_emit = c_emit; j.c_count = c_count; j.c_last = c_last;
+            j.n_cnvs = n_c;
+            hipLaunchKernelGGL(gd::gd_emcnv_emit_kernel<1>, walk, wg, 0, c->stream, j);
+            HIPCHK(c, hipGetLastError());
+            if (int r = ec_scan(c, s, c_count, n_c, 0, member_off, member_off + n_c)) return r;
+            if (int r = ec_fetch(c, member_off + n_c, &n_m)) return r;
+            if (int r = ec_alloc(c, &o_row, n_m, &res)) return r;
+            if (int r = ec_alloc(c, &o_depth, n_m, &res)) return r;
+            if (int r = ec_alloc(c, &o_cn, n_m, &res)) return r;
+            if (int r = ec_alloc(c, &o_fc, n_m, &res)) return r;
+            j.member_off = member_off;
+            j.o_row = o_row; j.o_depth = o_depth; j.o_cn = o_cn; j.o_fc = o_fc;
+            hipLaunchKernelGGL(gd::gd_emcnv_members_kernel, dim3(ec_cover(n_c, gd::EMCNV_WAVES)), wg, 0, c->stream, j);
+            HIPCHK(c, hipGetLastError());
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        res.v.clear();
+        s.c_sample = c_sample; s.c_psize = c_psize; s.c_emit = c_emit; s.c_count = c_count; s.c_last = c_last;
+        s.member_off = member_off; s.o_row = o_row; s.o_depth = o_depth; s.o_cn = o_cn; s.o_fc = o_fc;
+        s.n_cnvs = n_c; s.n_members = n_m;
+        s.secs[2] += ing_now() - t0;
+    }
+    s.finished = true;
+    if (n_cnvs) *n_cnvs = s.n_cnvs;
+    if (n_members) *n_members = s.n_members;
+    return GD_OK;
+}
+
+int gd_emcnv_read(gd_ctx* c, uint32_t* sample, uint32_t* psize, uint32_t* emit_row, uint64_t* member_off, uint32_t* member_row,
+                  float* depth, uint8_t* cn, float* log2fc)
+{
+    EC_STATE(c);
+    if (!s.finished) return fail(c, GD_E_STATE, "emcnv: gd_emcnv_finish has not been called");
+    const double t0 = ing_now();
+    const size_t nc = (size_t)s.n_cnvs, nm = (size_t)s.n_members;
+    if (member_off && !s.member_off) member_off[0] = 0;      // (no rows at all)
+    if (s.member_off) {
+        if (sample && nc) HIPCHK(c, hipMemcpyAsync(sample, s.c_sample, nc * 4, hipMemcpyDeviceToHost, c->stream));
+        if (psize && nc) HIPCHK(c, hipMemcpyAsync(psize, s.c_psize, nc * 4, hipMemcpyDeviceToHost, c->stream));
+        if (emit_row && nc) HIPCHK(c, hipMemcpyAsync(emit_row, s.c_emit, nc * 4, hipMemcpyDeviceToHost, c->stream));
+        if (member_off) HIPCHK(c, hipMemcpyAsync(member_off, s.member_off, (nc + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        if (member_row && nm) HIPCHK(c, hipMemcpyAsync(member_row, s.o_row, nm * 4, hipMemcpyDeviceToHost, c->stream));
+        if (depth && nm) HIPCHK(c, hipMemcpyAsync(depth, s.o_depth, nm * 4, hipMemcpyDeviceToHost, c->stream));
+        if (cn && nm) HIPCHK(c, hipMemcpyAsync(cn, s.o_cn, nm, hipMemcpyDeviceToHost, c->stream));
+        if (log2fc && nm) HIPCHK(c, hipMemcpyAsync(log2fc, s.o_fc, nm * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    s.secs[3] += ing_now() - t0;
+    return GD_OK;
+}
+
+int gd_emcnv_end(gd_ctx* c)
+{
+    if (!c) return GD_E_INVALID;
+    if (int r = set_device(c)) return r;
+    ec_drop(c);
+    return GD_OK;
+}
+
+int gd_emcnv_timing(gd_ctx* c, double* out, size_t n)
+{
+    EC_STATE(c);
+    if (!out) return GD_E_INVALID;
+    for (size_t i = 0; i < n && i < 4; ++i) out[i] = s.secs[i];
+    return GD_OK;
+}

@@ -28,20 +28,16 @@ static int em_check_n(gd_ctx* c, int n_samples)
     return GD_OK;
 }
 
-// d_in: the rows on the device (float32 when !cells, int64 otherwise); d_scale: device or nullptr
-static int em_run(gd_ctx* c, bool cells, const void* d_in, const float* d_scale, size_t n_rows, int n_samples,
-                  double* lambda, uint8_t* iters, uint8_t* cn, float* log2fc, EmBufs& b)
+// the kernel on rows already on the device (float32 when !cells, int64 otherwise); every output is a device pointer or
+// nullptr.  Returns once the stream has run it; *secs is its wall time.
+static int em_launch(gd_ctx* c, bool cells, const void* d_in, const float* d_scale, size_t n_rows, int n_samples,
+                     double* d_lambda, uint8_t* d_iters, uint8_t* d_cn, float* d_log2fc, double* secs)
 {
-    const size_t N = (size_t)n_samples, cellsN = n_rows * N;
-    if (lambda) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.lambda), n_rows * gd::EM_CENTRES * sizeof(double)));
-    if (iters) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.iters), n_rows));
-    if (cn) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.cn), cellsN));
-    if (log2fc) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.log2fc), cellsN * sizeof(float)));
     gd::EmJob j{};
     j.cells = d_in; j.scale = d_scale; j.n_rows = (int64_t)n_rows; j.n = n_samples;
     // the initial centres' factors (:136), from the host's libm as the oracle's are
     for (int i = 0; i < gd::EM_CENTRES; ++i) j.pw[i] = std::pow((double)i / 2.0, 1.1);
-    j.lambda = b.lambda; j.iters = b.iters; j.cn = b.cn; j.log2fc = b.log2fc;
+    j.lambda = d_lambda; j.iters = d_iters; j.cn = d_cn; j.log2fc = d_log2fc;
     const unsigned grid = (unsigned)std::min<size_t>((n_rows + gd::EM_WAVES - 1) / gd::EM_WAVES, (size_t)gd::EM_MAX_GRID);
     const dim3 wg(gd::EM_WAVES * 64);
     const bool regs = n_samples <= gd::EM_REG_MAX;
@@ -55,8 +51,21 @@ static int em_run(gd_ctx* c, bool cells, const void* d_in, const float* d_scale,
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    *secs = ing_now() - t0;
+    return GD_OK;
+}
+
+// d_in: the rows on the device (float32 when !cells, int64 otherwise); d_scale: device or nullptr
+static int em_run(gd_ctx* c, bool cells, const void* d_in, const float* d_scale, size_t n_rows, int n_samples,
+                  double* lambda, uint8_t* iters, uint8_t* cn, float* log2fc, EmBufs& b)
+{
+    const size_t N = (size_t)n_samples, cellsN = n_rows * N;
+    if (lambda) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.lambda), n_rows * gd::EM_CENTRES * sizeof(double)));
+    if (iters) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.iters), n_rows));
+    if (cn) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.cn), cellsN));
+    if (log2fc) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.log2fc), cellsN * sizeof(float)));
+    if (int r = em_launch(c, cells, d_in, d_scale, n_rows, n_samples, b.lambda, b.iters, b.cn, b.log2fc, &c->em_secs[1])) return r;
     const double t1 = ing_now();
-    c->em_secs[1] = t1 - t0;
     if (lambda) HIPCHK(c, hipMemcpyAsync(lambda, b.lambda, n_rows * gd::EM_CENTRES * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (iters) HIPCHK(c, hipMemcpyAsync(iters, b.iters, n_rows, hipMemcpyDeviceToHost, c->stream));
     if (cn) HIPCHK(c, hipMemcpyAsync(cn, b.cn, cellsN, hipMemcpyDeviceToHost, c->stream));

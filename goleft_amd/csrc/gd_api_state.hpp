@@ -76,7 +76,7 @@ struct RingSlot {
 
 // State of a device BAM read between gd_ingest_begin and gd_ingest_finish.
 struct IngestState;
-namespace { struct FillPool; struct CovState; struct IcState; struct IsState; }
+namespace { struct FillPool; struct CovState; struct IcState; struct IsState; struct EcState; }
 
 // Device buffers of one pending range (compressed bytes, inflated bytes, member tables): grow-only and
 // kept by the context between ranges -- allocating and freeing gigabytes per range cost 0.1-0.2 s.
@@ -261,6 +261,7 @@ struct gd_ctx {
     CovState* cov = nullptr;                                   // gd_covstats_*: the sampling state and its buffers (gd_api_covstats.inc)
     IcState* ic = nullptr;                                     // gd_indexcov_*: the cohort's tile sizes and results (gd_api_indexcov.inc)
     IsState* isp = nullptr;                                    // gd_indexsplit_*: the cohort's cell sums (gd_api_indexsplit.inc)
+    EcState* ec = nullptr;                                     // gd_emcnv_*: the positions, member bits and member values of the rows so far (gd_api_emcnv.inc)
     double em_secs[3] = {0, 0, 0};                             // gd_emdepth*: upload, kernel, read-back of the last call (gd_api_emdepth.inc)
     uint8_t* h_walk = nullptr; size_t cap_walk = 0;            // gd_ingest_decode, gd_covstats_decode: per-segment tables of the record walk (page-locked host memory
                                                                // the walk kernels read and write over the link: no copy command)

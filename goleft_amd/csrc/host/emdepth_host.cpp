@@ -1,7 +1,7 @@
 // emdepth_host.cpp -- copy numbers per site of a depthwed matrix: goleft's emdepth.EMDepth (emdepth/emdepth.go; DESIGN.md
 // section 3.10) run on the device, row by row.
 //
-//   goleft-depth emdepth [--scales FILE] matrix.bed[.gz]
+//   goleft-depth emdepth [--scales FILE] [--cnvs FILE] matrix.bed[.gz]
 //
 // The matrix is what `depthwed` writes and dcnv reads (dcnv/dcnv.go:153-186): a `#chrom start end samples...` header and
 // rows of chrom, start, end and one depth per sample.  Cells are parsed with strtod and narrowed to float32; with
@@ -9,6 +9,11 @@
 // normalised: the reference package "does no normalization and expects incoming data to be normalized".  The whole file is
 // read and checked first, then the rows go through gd_emdepth in blocks (GOLEFT_EMDEPTH_ROWS, default 65536; the output
 // does not depend on it).  Output: the header, and per row chrom, start, end and one copy number per sample.
+//
+// With --cnvs the rows go through gd_emcnv_add instead (the same kernel, the same copy numbers, the same blocks), which
+// also joins every sample's aberrant sites into CNV calls as emdepth.Cache does; FILE gets one
+// line per call.  Cache knows positions, not chromosomes, so start and end must be decimal uint32 values, and a call may
+// run across a chromosome boundary when the arithmetic says so: every site is written with its chromosome.
 #include <zlib.h>
 
 #include <algorithm>
@@ -26,14 +31,15 @@
 namespace {
 
 struct EArgs {
-    std::string scales, input;
+    std::string scales, cnvs, input;
 };
 
 void usage(FILE* f)
 {
-    fputs("usage: emdepth [--scales FILE] MATRIX\n"
+    fputs("usage: emdepth [--scales FILE] [--cnvs FILE] MATRIX\n"
           "  MATRIX  a depthwed matrix (#chrom start end samples... and its rows), plain or gzipped, already normalised\n"
-          "  --scales  a file of one factor per line, in column order: every depth is multiplied by its sample's factor\n", f);
+          "  --scales  a file of one factor per line, in column order: every depth is multiplied by its sample's factor\n"
+          "  --cnvs  write the CNV calls of every sample (emdepth.Cache) to FILE: sample, index, psize, sites, positions, cn, depth, log2fc\n", f);
 }
 
 int parse_args(int argc, const char* const* argv, EArgs* a)
@@ -48,12 +54,13 @@ int parse_args(int argc, const char* const* argv, EArgs* a)
             bool has_val = false;
             const size_t eq = arg.find('=');
             if (eq != std::string::npos) { key = arg.substr(0, eq); val = arg.substr(eq + 1); has_val = true; }
-            if (key != "--scales") { fprintf(stderr, "error: unknown argument %s\n", arg.c_str()); usage(stderr); return -1; }
+            if (key != "--scales" && key != "--cnvs") { fprintf(stderr, "error: unknown argument %s\n", arg.c_str()); usage(stderr); return -1; }
             if (!has_val) {
                 if (i + 1 >= argc) { fprintf(stderr, "error: missing value for %s\n", key.c_str()); usage(stderr); return -1; }
                 val = argv[++i];
             }
-            a->scales = val;
+            if (val.empty()) { fprintf(stderr, "error: empty value for %s\n", key.c_str()); usage(stderr); return -1; }
+            (key == "--scales" ? a->scales : a->cnvs) = val;
             continue;
         }
         pos.push_back(arg);
@@ -99,6 +106,7 @@ struct Matrix {
     std::string header;
     size_t n = 0;                                // samples
     std::vector<std::string> where;              // chrom \t start \t end of each row, as read
+    std::vector<long long> lineno;               // ... and the line it was read from
     std::vector<float> depths;                   // [rows][n]
 };
 
@@ -156,6 +164,7 @@ int read_matrix(const std::string& path, Matrix* m)
             return 1;
         }
         m->where.emplace_back(line.c_str(), (size_t)(cells_at - 1 - line.c_str()));
+        m->lineno.push_back(lineno);
     }
     if (!have_header) { fprintf(stderr, "emdepth: %s is empty\n", path.c_str()); return 1; }
     return 0;
@@ -188,6 +197,106 @@ int read_scales(const std::string& path, size_t n, std::vector<float>* out)
     return 0;
 }
 
+// all of [s, e) as a decimal uint32
+bool parse_u32(const char* s, const char* e, uint32_t* out)
+{
+    if (s == e) return false;
+    uint64_t v = 0;
+    for (; s < e; ++s) {
+        if (*s < '0' || *s > '9') return false;
+        v = v * 10 + (uint64_t)(*s - '0');
+        if (v > 0xffffffffull) return false;
+    }
+    *out = (uint32_t)v;
+    return true;
+}
+
+// start and end of every row (emdepth.Position holds uint32 values)
+int parse_positions(const std::string& path, const Matrix& m, std::vector<uint32_t>* starts, std::vector<uint32_t>* ends)
+{
+    const size_t rows = m.where.size();
+    starts->resize(rows);
+    ends->resize(rows);
+    for (size_t r = 0; r < rows; ++r) {
+        const std::string& w = m.where[r];
+        const size_t t1 = w.find('\t'), t2 = t1 == std::string::npos ? t1 : w.find('\t', t1 + 1);
+        if (t2 == std::string::npos || !parse_u32(w.c_str() + t1 + 1, w.c_str() + t2, &(*starts)[r]) ||
+            !parse_u32(w.c_str() + t2 + 1, w.c_str() + w.size(), &(*ends)[r])) {
+            fprintf(stderr, "emdepth: %s: line %lld: --cnvs needs start and end as decimal numbers below 2^32\n", path.c_str(),
+                    m.lineno[r]);
+            return 1;
+        }
+    }
+    return 0;
+}
+
+// %.2f as Go prints it: the infinities are +Inf and -Inf
+void append_fc(std::string* o, float v)
+{
+    if (std::isinf(v)) { *o += v > 0 ? "+Inf" : "-Inf"; return; }
+    char buf[64];
+    snprintf(buf, sizeof buf, "%.2f", (double)v);
+    *o += buf;
+}
+
+// the calls gd_emcnv_finish left as the text of the --cnvs file, one line each, in (emit row, sample) order
+int format_cnvs(gd_ctx* ctx, const Matrix& m, uint64_t n_cnvs, uint64_t n_members, std::string* text)
+{
+    std::vector<uint32_t> sample(n_cnvs), psize(n_cnvs), row(n_members);
+    std::vector<uint64_t> off(n_cnvs + 1);
+    std::vector<float> depth(n_members), fc(n_members);
+    std::vector<uint8_t> cn(n_members);
+    const int rc = gd_emcnv_read(ctx, sample.data(), psize.data(), nullptr, off.data(), row.data(), depth.data(), cn.data(), fc.data());
+    if (rc != GD_OK) { fprintf(stderr, "emdepth: gd_emcnv_read: %s (%s)\n", gd_strerror(rc), gd_last_error(ctx)); return 1; }
+    std::vector<std::string> names;
+    {
+        size_t at = 0;
+        for (int k = 0; k < 3; ++k) at = m.header.find('\t', at) + 1;
+        for (;;) {
+            const size_t q = m.header.find('\t', at);
+            names.push_back(m.header.substr(at, q == std::string::npos ? q : q - at));
+            if (q == std::string::npos) break;
+            at = q + 1;
+        }
+    }
+    std::string& o = *text;
+    o = "#sample\tindex\tpsize\tsites\tpositions\tcn\tdepth\tlog2fc\n";
+    char buf[64];
+    for (uint64_t k = 0; k < n_cnvs; ++k) {
+        const uint64_t a = off[k], b = off[k + 1];
+        o += names[sample[k]];
+        snprintf(buf, sizeof buf, "\t%u\t%u\t%llu\t", sample[k], psize[k], (unsigned long long)(b - a));
+        o += buf;
+        for (uint64_t i = a; i < b; ++i) {
+            const std::string& w = m.where[row[i]];
+            const size_t t1 = w.find('\t'), t2 = w.find('\t', t1 + 1);
+            if (i > a) o += ',';
+            o.append(w, 0, t1);
+            o += ':';
+            o.append(w, t1 + 1, t2 - t1 - 1);
+            o += '-';
+            o.append(w, t2 + 1, std::string::npos);
+        }
+        o += '\t';
+        for (uint64_t i = a; i < b; ++i) { if (i > a) o += ','; o += (char)('0' + cn[i]); }
+        o += '\t';
+        for (uint64_t i = a; i < b; ++i) { if (i > a) o += ','; snprintf(buf, sizeof buf, "%.9g", (double)depth[i]); o += buf; }
+        o += '\t';
+        for (uint64_t i = a; i < b; ++i) { if (i > a) o += ','; append_fc(&o, fc[i]); }
+        o += '\n';
+    }
+    return 0;
+}
+
+int write_text(const std::string& path, const std::string& o)
+{
+    FILE* f = fopen(path.c_str(), "w");
+    if (!f) { fprintf(stderr, "emdepth: cannot create %s\n", path.c_str()); return 1; }
+    const bool ok = fwrite(o.data(), 1, o.size(), f) == o.size();
+    if (fclose(f) != 0 || !ok) { fprintf(stderr, "emdepth: error writing %s\n", path.c_str()); return 1; }
+    return 0;
+}
+
 int run(const EArgs& a, FILE* out)
 {
     const bool timing = getenv("GOLEFT_EMDEPTH_TIMING") != nullptr;
@@ -208,6 +317,10 @@ int run(const EArgs& a, FILE* out)
                 m.depths[r * N + s] = d;
             }
     }
+    const bool cnvs = !a.cnvs.empty();
+    std::vector<uint32_t> starts, ends;
+    if (cnvs)
+        if (int rc = parse_positions(a.input, m, &starts, &ends)) return rc;
     const double t_read = now_s() - t_start;
     size_t block = 65536;
     if (const char* e = getenv("GOLEFT_EMDEPTH_ROWS")) {
@@ -227,7 +340,25 @@ int run(const EArgs& a, FILE* out)
     }
     std::vector<uint8_t> cn(rows * N);
     double lib[3] = {0, 0, 0};
-    for (size_t r0 = 0; r0 < rows; r0 += block) {
+    double cnv_lib[4] = {0, 0, 0, 0}, t_cnv_write = 0;
+    std::string cnv_text;
+    uint64_t n_cnvs = 0, n_members = 0;
+    if (cnvs) {
+        int rc = gd_emcnv_begin(ctx, (int)N);
+        for (size_t r0 = 0; rc == GD_OK && r0 < rows; r0 += block) {
+            const size_t nb = std::min(block, rows - r0);
+            rc = gd_emcnv_add(ctx, m.depths.data() + r0 * N, nb, starts.data() + r0, ends.data() + r0, cn.data() + r0 * N);
+        }
+        if (rc == GD_OK) rc = gd_emcnv_finish(ctx, &n_cnvs, &n_members);
+        if (rc != GD_OK) {
+            fprintf(stderr, "emdepth: gd_emcnv: %s (%s)\n", gd_strerror(rc), gd_last_error(ctx));
+            gd_destroy(ctx);
+            return 1;
+        }
+        if (format_cnvs(ctx, m, n_cnvs, n_members, &cnv_text) != 0) { gd_destroy(ctx); return 1; }
+        (void)gd_emcnv_timing(ctx, cnv_lib, 4);
+    }
+    for (size_t r0 = 0; !cnvs && r0 < rows; r0 += block) {
         const size_t nb = std::min(block, rows - r0);
         const int rc = gd_emdepth(ctx, m.depths.data() + r0 * N, nb, (int)N, nullptr, nullptr, cn.data() + r0 * N, nullptr);
         if (rc != GD_OK) {
@@ -249,7 +380,18 @@ int run(const EArgs& a, FILE* out)
         o += '\n';
     }
     if (fwrite(o.data(), 1, o.size(), out) != o.size() || fflush(out) != 0) { fprintf(stderr, "emdepth: error writing the rows\n"); return 1; }
-    if (timing)
+    if (cnvs) {                                  // after the rows: a run that fails leaves no calls file behind
+        const double t0 = now_s();
+        if (int rc = write_text(a.cnvs, cnv_text)) return rc;
+        t_cnv_write = now_s() - t0;
+    }
+    if (timing && cnvs)
+        fprintf(stderr, "{\"rows\": %zu, \"samples\": %zu, \"block_rows\": %zu, \"total_s\": %.4f, \"read_s\": %.4f, \"upload_s\": %.4f, "
+                        "\"kernel_s\": %.4f, \"cnv_kernels_s\": %.4f, \"readback_s\": %.4f, \"write_s\": %.4f, \"cnvs\": %llu, "
+                        "\"members\": %llu, \"cnvs_write_s\": %.4f}\n",
+                rows, N, block, now_s() - t_start, t_read, cnv_lib[0], cnv_lib[1], cnv_lib[2], cnv_lib[3], now_s() - t_write0,
+                (unsigned long long)n_cnvs, (unsigned long long)n_members, t_cnv_write);
+    else if (timing)
         fprintf(stderr, "{\"rows\": %zu, \"samples\": %zu, \"block_rows\": %zu, \"total_s\": %.4f, \"read_s\": %.4f, \"upload_s\": %.4f, "
                         "\"kernel_s\": %.4f, \"readback_s\": %.4f, \"write_s\": %.4f}\n",
                 rows, N, block, now_s() - t_start, t_read, lib[0], lib[1], lib[2], now_s() - t_write0);

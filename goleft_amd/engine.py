@@ -331,6 +331,69 @@ class DepthEngine:
         self._chk(self._lib.gd_emdepth_timing(self._ctx, t, 3))
         return tuple(t)
 
+    def _emcnv_positions(self, starts, ends, rows: int):
+        st, en = np.ascontiguousarray(starts, np.uint32), np.ascontiguousarray(ends, np.uint32)
+        assert st.shape == (rows,) and en.shape == (rows,)
+        return st, en
+
+    def _emcnv_result(self, cn):
+        nc, nm = C.c_uint64(), C.c_uint64()
+        self._chk(self._lib.gd_emcnv_finish(self._ctx, C.byref(nc), C.byref(nm)))
+        nc, nm = nc.value, nm.value
+        out = dict(sample=np.empty(nc, np.uint32), psize=np.empty(nc, np.uint32), emit_row=np.empty(nc, np.uint32),
+                   member_off=np.empty(nc + 1, np.uint64), member_row=np.empty(nm, np.uint32),
+                   depth=np.empty(nm, np.float32), cn=np.empty(nm, np.uint8), log2fc=np.empty(nm, np.float32))
+        self._chk(self._lib.gd_emcnv_read(self._ctx, *[out[k].ctypes.data for k in (
+            "sample", "psize", "emit_row", "member_off", "member_row", "depth", "cn", "log2fc")]))
+        out["site_cn"] = cn
+        out["timing"] = self.emcnv_timing()
+        self._chk(self._lib.gd_emcnv_end(self._ctx))
+        return out
+
+    def emdepth_cnvs(self, depths, starts, ends, block_rows=None):
+        """emdepth.Cache over a [rows][samples] float32 matrix whose rows span start[r] .. end[r] (uint32), in input
+        order: the CNV calls in (emit_row, sample) order.  A dict of sample, psize, emit_row (uint32 [cnvs]), member_off
+        (uint64 [cnvs + 1]), member_row (uint32), depth (float32), cn (uint8), log2fc (float32) per member, site_cn
+        (uint8 [rows, samples]: what emdepth gives) and timing.  block_rows: rows per device call (None: all at
+        once); the result does not depend on it."""
+        d = np.ascontiguousarray(depths, np.float32)
+        assert d.ndim == 2
+        rows, n = d.shape
+        st, en = self._emcnv_positions(starts, ends, rows)
+        cn = np.empty((rows, n), np.uint8)
+        self._chk(self._lib.gd_emcnv_begin(self._ctx, n))
+        step = rows if not block_rows else int(block_rows)
+        for r0 in range(0, rows, max(step, 1)):
+            r1 = min(rows, r0 + step)
+            self._chk(self._lib.gd_emcnv_add(self._ctx, d[r0:r1].ctypes.data, r1 - r0, st[r0:r1].ctypes.data,
+                                             en[r0:r1].ctypes.data, cn[r0:r1].ctypes.data))
+        return self._emcnv_result(cn)
+
+    def emdepth_cnvs_cells(self, dptr: int, rows: int, n_samples: int, starts, ends, scale=None, block_rows=None,
+                           site_cn=False):
+        """The same for int64 cells in HBM (depthwed_device's pointer), scaled as emdepth_cells does.  The per-site copy
+        numbers are read back only when site_cn is set (they are the one output of rows x samples bytes)."""
+        st, en = self._emcnv_positions(starts, ends, rows)
+        s = None
+        if scale is not None:
+            s = np.ascontiguousarray(scale, np.float32)
+            assert s.shape == (n_samples,)
+        cn = np.empty((rows, n_samples), np.uint8) if site_cn else None
+        self._chk(self._lib.gd_emcnv_begin(self._ctx, n_samples))
+        step = rows if not block_rows else int(block_rows)
+        for r0 in range(0, rows, max(step, 1)):
+            r1 = min(rows, r0 + step)
+            self._chk(self._lib.gd_emcnv_add_cells(self._ctx, C.c_void_p(dptr + r0 * n_samples * 8), r1 - r0,
+                                                   s.ctypes.data if s is not None else None, st[r0:r1].ctypes.data,
+                                                   en[r0:r1].ctypes.data, cn[r0:r1].ctypes.data if site_cn else None))
+        return self._emcnv_result(cn)
+
+    def emcnv_timing(self):
+        """Seconds since the last gd_emcnv_begin: (upload, emdepth kernel, CNV kernels, read-back)."""
+        t = (C.c_double * 4)()
+        self._chk(self._lib.gd_emcnv_timing(self._ctx, t, 4))
+        return tuple(t)
+
     def seq_load(self, seq) -> None:
         """One contig's reference bases (bytes / uint8 array, FASTA line breaks removed) into HBM."""
         a = np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else np.ascontiguousarray(seq, np.uint8)

@@ -39,7 +39,7 @@ extern "C" {
 
 /* GD_ABI_VERSION changes when an existing entry point or structure changes; GD_ABI_REVISION counts the releases that only
  * ADDED entry points since then (revision 1: gd_indexcov_*; 2: gd_indexsplit_*; 3: gd_crai_sizes).  A caller built against (15, r) runs on any (15, r' >= r).
- * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing were added without a revision; look them up by symbol.
+ * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, were added without a revision; look them up by symbol.
  * Why indexcov did not become version 16: nothing that existed changed, so callers of ABI 15 need not be turned away, and
  * tests/test_host_cpu.py holds gd_abi_version() to 15 until something does change. */
 #define GD_ABI_VERSION 15
@@ -667,6 +667,37 @@ int gd_emdepth(gd_ctx* ctx, const float* depths, size_t n_rows, int n_samples,
 int gd_emdepth_cells(gd_ctx* ctx, const int64_t* d_cells, size_t n_rows, int n_samples, const float* scale,
                      double* lambda, uint8_t* iters, uint8_t* cn, float* log2fc);
 int gd_emdepth_timing(gd_ctx* ctx, double* out, size_t n);
+/* ---- emdepth.Cache (emdepth/emdepth.go:216-398): a sample's aberrant sites joined into CNV calls, on the device ----
+ * The rows go in in input order, in blocks of any size (the result does not depend on the cut); every block runs the
+ * emdepth kernel and keeps its outputs in HBM.  A cell is U when log2(depth / lambda[2]) (float64) >= 0.40, D when it is
+ * <= -0.80; a cell is a member when it is U or D and the same sample's cell one row up has the same state (row 0 is
+ * compared with itself).  A row r is a gap for a member of row a when (start[r] - end[a]) mod 2^32 >= 30000 -- a start
+ * below that end wraps and counts.  A sample's consecutive members form one CNV until a gap row comes before the next
+ * member; the CNV is emitted at the first gap row after its last member, or by gd_emcnv_finish (emit row = the row
+ * count) when (start[last row] + 100000 - end[a]) mod 2^32 >= 30000, and never otherwise.  As in the reference, sample 0
+ * loses its list in every Clear that finds any list: it yields single-site CNVs only, when the next row is a gap.
+ * PSize is the number of samples holding a list when the CNV is emitted.  CNVs are ordered by (emit row, sample) --
+ * the reference's order within one Clear is Go's map order -- and a CNV's members by row.
+ *   gd_emcnv_begin      n_samples as gd_emdepth; drops an earlier state (a refused call does not)
+ *   gd_emcnv_add        depths: host float32 [n_rows][n_samples], finite and >= 0; starts, ends: host [n_rows];
+ *                       cn_out: NULL or host [n_rows][n_samples], the copy numbers gd_emdepth gives
+ *   gd_emcnv_add_cells  d_cells: DEVICE int64 [n_rows][n_samples], scale: host [n_samples] or NULL, as gd_emdepth_cells
+ *   gd_emcnv_finish     Clear(nil); the counts.  No rows at all: 0 and 0.  gd_emcnv_add* is GD_E_STATE afterwards.
+ *   gd_emcnv_read       after gd_emcnv_finish (GD_E_STATE before); any output may be NULL.  member_off[k] .. [k + 1] are
+ *                       CNV k's members in member_row (input row), depth, cn and log2fc (float32 of the float64 value).
+ *   gd_emcnv_end        frees the state (gd_destroy does too)
+ *   gd_emcnv_timing     seconds since gd_emcnv_begin: upload, emdepth kernel, CNV kernels, read-back; min(n, 4) values
+ * A refused call leaves the state as it was.  Apart from cn_out, what is copied back is O(CNVs + members). */
+int gd_emcnv_begin(gd_ctx* ctx, int n_samples);
+int gd_emcnv_add(gd_ctx* ctx, const float* depths, size_t n_rows, const uint32_t* starts, const uint32_t* ends, uint8_t* cn_out);
+int gd_emcnv_add_cells(gd_ctx* ctx, const int64_t* d_cells, size_t n_rows, const float* scale, const uint32_t* starts,
+                       const uint32_t* ends, uint8_t* cn_out);
+int gd_emcnv_finish(gd_ctx* ctx, uint64_t* n_cnvs, uint64_t* n_members);
+int gd_emcnv_read(gd_ctx* ctx, uint32_t* sample /* [n_cnvs] */, uint32_t* psize, uint32_t* emit_row,
+                  uint64_t* member_off /* [n_cnvs + 1] */, uint32_t* member_row /* [n_members] */, float* depth, uint8_t* cn,
+                  float* log2fc);
+int gd_emcnv_end(gd_ctx* ctx);
+int gd_emcnv_timing(gd_ctx* ctx, double* out, size_t n);
 int gd_ingest_abort(gd_ctx* ctx);
 /* Page-locked host memory for the byte range handed to gd_ingest_bgzf (read the file
  * straight into it: the H2D copy then runs at PCIe speed instead of through a bounce

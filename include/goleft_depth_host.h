@@ -192,11 +192,13 @@ int gdh_indexsplit_main(int argc, const char* const* argv);
 int gdh_indexsplit_run(int argc, const char* const* argv, const char* out_path);
 
 /* ---- `emdepth` (emdepth/emdepth.go EMDepth, CN): copy numbers per site of a depthwed matrix, fitted on the device
- * (gd_emdepth).  argv: [--scales FILE] matrix.bed[.gz] -- the `#chrom start end samples...` header and its rows as
+ * (gd_emdepth).  argv: [--scales FILE] [--cnvs FILE] matrix.bed[.gz] -- the `#chrom start end samples...` header and its rows as
  * dcnv/dcnv.go:153-186 reads them, 1 or 3 .. 4096 samples, cells parsed with strtod and narrowed to float32; --scales:
  * one factor per line in column order, multiplied in float32.  Nothing else is normalised.  Output: the header, and per
  * row chrom, start, end and one copy number (0 .. 9) per sample.  The file is checked before anything runs: a row whose
  * column count differs from the header's, or a cell that is not a finite number >= 0, is reported with its line number.
+ * --cnvs: also join every sample's aberrant sites into CNV calls as emdepth.Cache does (gd_emcnv_*) and write them to
+ * FILE, one line per call; start and end must then be decimal numbers below 2^32 (reported with the line number).
  * Returns the exit code (1 on an error, with no row written; 255 on a usage error). ---------------------------------- */
 int gdh_emdepth_main(int argc, const char* const* argv);
 /* Same, writing to out_path (NULL = stdout). */
