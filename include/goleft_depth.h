@@ -451,7 +451,10 @@ int gd_md_sums(gd_ctx* ctx, size_t n_blocks, const int64_t* start, const int64_t
 int gd_md_begin(gd_ctx* ctx, int64_t len);
 int gd_md_accumulate(gd_ctx* ctx, int n_samples, const int32_t* tids, int32_t min_cov);
 int gd_md_finish(gd_ctx* ctx, int32_t min_samples, uint32_t* any_bits, uint32_t* suf_bits, size_t n_words);
-/* Bitmaps made elsewhere become the current ones (tests; a host with its own depth source). */
+/* Bitmaps made elsewhere become the current ones (tests; a host with its own depth source).  Precondition: suf is a
+ * subset of any -- the reference only ever sees printed sites, so what gd_md_blocks answers for a sufficient but
+ * unprinted site is not defined by it (gd_md_flags and gd_md_finish may produce such sites, with min_cov <= 0 or
+ * min_samples < 0; the blocks over them are the device's own). */
 int gd_md_load_flags(gd_ctx* ctx, const uint32_t* any_bits, const uint32_t* suf_bits, int64_t len);
 /* The block state machine on the device (aggregate + splitBlocks, multidepth.go:188-268, for every chunk of
  * `chunk` positions, in chunk order -- what `multidepth -p 1` prints): blocks [start, end) over the current
