@@ -34,6 +34,8 @@ SYMBOLS = {
     "gdh_indexsplit_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p]),
     "gdh_emdepth_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_emdepth_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p]),
+    "gdh_scales_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
+    "gdh_scales_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p]),
     "gdh_samplename_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_crai_read": (C.c_int, [C.c_char_p, C.c_size_t, C.c_size_t, _P, _P, _P, _P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                 C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]),

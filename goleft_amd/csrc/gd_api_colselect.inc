@@ -1,0 +1,141 @@
+// gd_api_colselect.inc -- dcnv's SampleMedians per column of a depth matrix (part of gd_api.hip, inside extern "C"): the
+// host float32 form, the device int64 form (the cells gd_depthwed_device leaves) and the seconds of the last call.  The
+// kernels are gd_colselect.hpp's.  Nothing is kept between calls but the three timings.
+
+namespace {
+
+// the device buffers of one call, freed when it returns
+struct CsBufs {
+    void* in = nullptr;
+    uint32_t* counts = nullptr;
+    uint32_t* zeros = nullptr;
+    uint64_t* prefix = nullptr;
+    int32_t* rem = nullptr;
+    uint32_t* rank = nullptr;
+    uint64_t* nonzero = nullptr;
+    uint32_t* flags = nullptr;
+    ~CsBufs()
+    {
+        for (void* p : {in, (void*)counts, (void*)zeros, (void*)prefix, (void*)rem, (void*)rank, (void*)nonzero, (void*)flags})
+            if (p) (void)hipFree(p);
+    }
+};
+
+static int cs_check(gd_ctx* c, size_t n_rows, int n_samples)
+{
+    if (n_samples < 1 || n_samples > gd::CS_MAX_N)
+        return fail(c, GD_E_RANGE, "sample medians: 1 .. %d samples, not %d", gd::CS_MAX_N, n_samples);
+    if (n_rows < 1 || n_rows > 0x7fffffffull)
+        return fail(c, GD_E_RANGE, "sample medians: 1 .. 2^31 - 1 rows, not %zu", n_rows);
+    return GD_OK;
+}
+
+// d_in: the matrix on the device (float32 when !cells, int64 otherwise).  prefix_out: host [n_samples], the answers as
+// keys (a float's bits or the cell); nonzero_out: host [n_samples] or nullptr.
+static int cs_run(gd_ctx* c, bool cells, const void* d_in, size_t n_rows, int n_samples, uint64_t* prefix_out,
+                  uint64_t* nonzero_out, CsBufs& b)
+{
+    const size_t N = (size_t)n_samples;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.counts), N * gd::CS_BINS * sizeof(uint32_t)));
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.zeros), N * sizeof(uint32_t)));
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.prefix), N * sizeof(uint64_t)));
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.rem), N * sizeof(int32_t)));
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.rank), N * sizeof(uint32_t)));
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.nonzero), N * sizeof(uint64_t)));
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.flags), 2 * sizeof(uint32_t)));
+    const double t0 = ing_now();
+    HIPCHK(c, hipMemsetAsync(b.counts, 0, N * gd::CS_BINS * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(b.zeros, 0, N * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(b.flags, 0, 2 * sizeof(uint32_t), c->stream));
+    gd::CsJob j{};
+    j.cells = d_in; j.n_rows = (int64_t)n_rows; j.n = n_samples;
+    j.counts = b.counts; j.zeros = b.zeros; j.prefix = b.prefix; j.rem = b.rem; j.rank = b.rank; j.nonzero = b.nonzero;
+    j.flags = b.flags;
+    // the column tiles share CS_MAX_GRID workgroups; each strides over the slabs of rows
+    const unsigned tiles = (unsigned)((N + gd::CS_COLS - 1) / gd::CS_COLS);
+    const size_t slabs = (n_rows + gd::CS_SLAB - 1) / gd::CS_SLAB;
+    const unsigned gx = (unsigned)std::min<size_t>(slabs, std::max<unsigned>(1u, (unsigned)gd::CS_MAX_GRID / tiles));
+    const dim3 grid(gx, tiles), wg(gd::CS_WG);
+    const dim3 pgrid((unsigned)((N + gd::CS_PICK_WAVES - 1) / gd::CS_PICK_WAVES)), pwg(gd::CS_PICK_WAVES * 64);
+    int passes = 3;                              // float: the digits after the first
+    if (cells) {
+        hipLaunchKernelGGL((gd::gd_colselect_hist_kernel<int64_t, true>), grid, wg, 0, c->stream, j);
+        hipLaunchKernelGGL((gd::gd_colselect_pick_kernel<gd::CS_PICK_LENGTH>), pgrid, pwg, 0, c->stream, j);
+        HIPCHK(c, hipGetLastError());
+        uint32_t flags[2] = {0, 0};
+        HIPCHK(c, hipMemcpyAsync(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (flags[1]) return fail(c, GD_E_INVALID, "sample medians: a cell of the device matrix is negative");
+        passes = (int)flags[0];                  // the longest answer, in bytes
+    } else {
+        hipLaunchKernelGGL((gd::gd_colselect_hist_kernel<float, true>), grid, wg, 0, c->stream, j);
+        hipLaunchKernelGGL((gd::gd_colselect_pick_kernel<gd::CS_PICK_FLOAT_FIRST>), pgrid, pwg, 0, c->stream, j);
+    }
+    for (int p = 0; p < passes; ++p) {
+        if (cells) hipLaunchKernelGGL((gd::gd_colselect_hist_kernel<int64_t, false>), grid, wg, 0, c->stream, j);
+        else hipLaunchKernelGGL((gd::gd_colselect_hist_kernel<float, false>), grid, wg, 0, c->stream, j);
+        hipLaunchKernelGGL((gd::gd_colselect_pick_kernel<gd::CS_PICK_DIGIT>), pgrid, pwg, 0, c->stream, j);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->sm_secs[1] = ing_now() - t0;
+    c->sm_passes = 1 + passes;
+    const double t1 = ing_now();
+    HIPCHK(c, hipMemcpyAsync(prefix_out, b.prefix, N * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (nonzero_out) HIPCHK(c, hipMemcpyAsync(nonzero_out, b.nonzero, N * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->sm_secs[2] = ing_now() - t1;
+    return GD_OK;
+}
+
+}  // namespace
+
+int gd_sample_medians(gd_ctx* c, const float* depths, size_t n_rows, int n_samples, float* med, uint64_t* n_nonzero)
+{
+    if (!c) return GD_E_INVALID;
+    if (int r = cs_check(c, n_rows, n_samples)) return r;
+    if (!depths || !med) return GD_E_INVALID;
+    const size_t N = (size_t)n_samples;
+    for (size_t i = 0; i < n_rows * N; ++i)
+        if (!(depths[i] >= 0.0f) || !std::isfinite(depths[i]))
+            return fail(c, GD_E_INVALID, "sample medians: the depth of row %zu, sample %zu is not a finite number >= 0", i / N, i % N);
+    if (int r = set_device(c)) return r;
+    c->sm_secs[0] = c->sm_secs[1] = c->sm_secs[2] = 0;
+    c->sm_passes = 0;
+    CsBufs b;
+    const double t0 = ing_now();
+    HIPCHK(c, hipMalloc(&b.in, n_rows * N * sizeof(float)));
+    HIPCHK(c, hipMemcpyAsync(b.in, depths, n_rows * N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->sm_secs[0] = ing_now() - t0;
+    std::vector<uint64_t> keys(N);
+    if (int r = cs_run(c, false, b.in, n_rows, n_samples, keys.data(), n_nonzero, b)) return r;
+    for (size_t s = 0; s < N; ++s) {
+        const uint32_t bits = (uint32_t)keys[s];
+        memcpy(&med[s], &bits, sizeof bits);
+    }
+    return GD_OK;
+}
+
+int gd_sample_medians_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, int n_samples, int64_t* med, uint64_t* n_nonzero)
+{
+    if (!c) return GD_E_INVALID;
+    if (int r = cs_check(c, n_rows, n_samples)) return r;
+    if (!d_cells || !med) return GD_E_INVALID;
+    if (int r = set_device(c)) return r;
+    c->sm_secs[0] = c->sm_secs[1] = c->sm_secs[2] = 0;
+    c->sm_passes = 0;
+    CsBufs b;
+    std::vector<uint64_t> keys((size_t)n_samples);
+    if (int r = cs_run(c, true, d_cells, n_rows, n_samples, keys.data(), n_nonzero, b)) return r;
+    for (size_t s = 0; s < keys.size(); ++s) med[s] = (int64_t)keys[s];
+    return GD_OK;
+}
+
+int gd_sample_medians_timing(gd_ctx* c, double* out, size_t n)
+{
+    if (!c || !out) return GD_E_INVALID;
+    for (size_t i = 0; i < n && i < 3; ++i) out[i] = c->sm_secs[i];
+    if (n > 3) out[3] = (double)c->sm_passes;
+    return GD_OK;
+}

@@ -1,7 +1,8 @@
 // emdepth_host.cpp -- copy numbers per site of a depthwed matrix: goleft's emdepth.EMDepth (emdepth/emdepth.go; DESIGN.md
 // section 3.10) run on the device, row by row.
 //
-//   goleft-depth emdepth [--scales FILE] [--cnvs FILE] matrix.bed[.gz]
+//   goleft-depth emdepth [--scales FILE | --normalize [--level L]] [--cnvs FILE] matrix.bed[.gz]
+//   goleft-depth scales [--level L] matrix.bed[.gz]
 //
 // The matrix is what `depthwed` writes and dcnv reads (dcnv/dcnv.go:153-186): a `#chrom start end samples...` header and
 // rows of chrom, start, end and one depth per sample.  Cells are parsed with strtod and narrowed to float32; with
@@ -14,6 +15,12 @@
 // also joins every sample's aberrant sites into CNV calls as emdepth.Cache does; FILE gets one
 // line per call.  Cache knows positions, not chromosomes, so start and end must be decimal uint32 values, and a call may
 // run across a chromosome boundary when the arithmetic says so: every site is written with its chromosome.
+//
+// `scales` reads the same matrix with the same reader and writes the factors `--scales` takes, one per line in column order:
+// every sample's 0.65 quantile of its non-zero depths (dcnv's SampleMedians, dcnv/dcnv.go:108-125; gd_sample_medians on
+// the device) carried to one level, scale[s] = (float)(T / med[s]) with T = sorted(med)[N / 2] or
+// --level.  `emdepth --normalize` computes the same factors in-process and goes on as with --scales: the matrix is
+// uploaded once for the medians and again, scaled, in its blocks.
 #include <zlib.h>
 
 #include <algorithm>
@@ -32,38 +39,79 @@ namespace {
 
 struct EArgs {
     std::string scales, cnvs, input;
+    bool normalize = false, has_level = false;
+    double level = 0;
 };
+
+void usage_scales(FILE* f)
+{
+    fputs("usage: scales [--level L] MATRIX\n"
+          "  MATRIX  a depthwed matrix (#chrom start end samples... and its rows), plain or gzipped\n"
+          "  writes one factor per sample and line, in column order, for emdepth --scales: T / q[s], where q[s] is the 0.65\n"
+          "  quantile of the sample's non-zero depths and T the middle one of them (sorted q, index N / 2)\n"
+          "  --level  a finite number > 0 that replaces T (1: the factors 1 / q[s])\n", f);
+}
 
 void usage(FILE* f)
 {
-    fputs("usage: emdepth [--scales FILE] [--cnvs FILE] MATRIX\n"
+    fputs("usage: emdepth [--scales FILE | --normalize [--level L]] [--cnvs FILE] MATRIX\n"
           "  MATRIX  a depthwed matrix (#chrom start end samples... and its rows), plain or gzipped, already normalised\n"
           "  --scales  a file of one factor per line, in column order: every depth is multiplied by its sample's factor\n"
+          "  --normalize  compute those factors here, as `scales` does: each sample's 0.65 quantile of its non-zero depths\n"
+          "               carried to the middle one of them (--level L: to L)\n"
           "  --cnvs  write the CNV calls of every sample (emdepth.Cache) to FILE: sample, index, psize, sites, positions, cn, depth, log2fc\n", f);
 }
 
-int parse_args(int argc, const char* const* argv, EArgs* a)
+// scales_cmd: the `scales` entry, which takes --level alone
+int parse_args(int argc, const char* const* argv, EArgs* a, bool scales_cmd)
 {
+    const auto usage = [scales_cmd](FILE* f) { scales_cmd ? usage_scales(f) : ::usage(f); };
     std::vector<std::string> pos;
     for (int i = 1; i < argc; ++i) {
         std::string arg = argv[i];
         if (arg == "-h" || arg == "--help") { usage(stdout); return 1; }
         if (arg == "--") { for (++i; i < argc; ++i) pos.push_back(argv[i]); break; }
+        if (arg == "--normalize" && !scales_cmd) { a->normalize = true; continue; }
         if (arg.size() > 1 && arg[0] == '-') {
             std::string key = arg, val;
             bool has_val = false;
             const size_t eq = arg.find('=');
             if (eq != std::string::npos) { key = arg.substr(0, eq); val = arg.substr(eq + 1); has_val = true; }
-            if (key != "--scales" && key != "--cnvs") { fprintf(stderr, "error: unknown argument %s\n", arg.c_str()); usage(stderr); return -1; }
+            if (key != "--level" && (scales_cmd || (key != "--scales" && key != "--cnvs"))) {
+                fprintf(stderr, "error: unknown argument %s\n", arg.c_str());
+                usage(stderr);
+                return -1;
+            }
             if (!has_val) {
                 if (i + 1 >= argc) { fprintf(stderr, "error: missing value for %s\n", key.c_str()); usage(stderr); return -1; }
                 val = argv[++i];
             }
             if (val.empty()) { fprintf(stderr, "error: empty value for %s\n", key.c_str()); usage(stderr); return -1; }
+            if (key == "--level") {
+                char* end = nullptr;
+                a->level = strtod(val.c_str(), &end);
+                if (end != val.c_str() + val.size() || !std::isfinite(a->level) || !(a->level > 0)) {
+                    fprintf(stderr, "error: --level must be a finite number > 0, not '%s'\n", val.c_str());
+                    usage(stderr);
+                    return -1;
+                }
+                a->has_level = true;
+                continue;
+            }
             (key == "--scales" ? a->scales : a->cnvs) = val;
             continue;
         }
         pos.push_back(arg);
+    }
+    if (a->normalize && !a->scales.empty()) {
+        fprintf(stderr, "error: --normalize computes the factors that --scales reads: give one of them\n");
+        usage(stderr);
+        return -1;
+    }
+    if (a->has_level && !a->normalize && !scales_cmd) {
+        fprintf(stderr, "error: --level sets the level --normalize carries the samples to: it needs --normalize\n");
+        usage(stderr);
+        return -1;
     }
     if (pos.size() != 1) { fprintf(stderr, "error: one matrix is required\n"); usage(stderr); return -1; }
     a->input = pos[0];
@@ -230,6 +278,21 @@ int parse_positions(const std::string& path, const Matrix& m, std::vector<uint32
     return 0;
 }
 
+// the header's fields from the fourth on
+std::vector<std::string> sample_names(const Matrix& m)
+{
+    std::vector<std::string> names;
+    size_t at = 0;
+    for (int k = 0; k < 3; ++k) at = m.header.find('\t', at) + 1;
+    for (;;) {
+        const size_t q = m.header.find('\t', at);
+        names.push_back(m.header.substr(at, q == std::string::npos ? q : q - at));
+        if (q == std::string::npos) break;
+        at = q + 1;
+    }
+    return names;
+}
+
 // %.2f as Go prints it: the infinities are +Inf and -Inf
 void append_fc(std::string* o, float v)
 {
@@ -248,17 +311,7 @@ int format_cnvs(gd_ctx* ctx, const Matrix& m, uint64_t n_cnvs, uint64_t n_member
     std::vector<uint8_t> cn(n_members);
     const int rc = gd_emcnv_read(ctx, sample.data(), psize.data(), nullptr, off.data(), row.data(), depth.data(), cn.data(), fc.data());
     if (rc != GD_OK) { fprintf(stderr, "emdepth: gd_emcnv_read: %s (%s)\n", gd_strerror(rc), gd_last_error(ctx)); return 1; }
-    std::vector<std::string> names;
-    {
-        size_t at = 0;
-        for (int k = 0; k < 3; ++k) at = m.header.find('\t', at) + 1;
-        for (;;) {
-            const size_t q = m.header.find('\t', at);
-            names.push_back(m.header.substr(at, q == std::string::npos ? q : q - at));
-            if (q == std::string::npos) break;
-            at = q + 1;
-        }
-    }
+    const std::vector<std::string> names = sample_names(m);
     std::string& o = *text;
     o = "#sample\tindex\tpsize\tsites\tpositions\tcn\tdepth\tlog2fc\n";
     char buf[64];
@@ -297,6 +350,102 @@ int write_text(const std::string& path, const std::string& o)
     return 0;
 }
 
+int open_device(const char* prog, gd_ctx** ctx)
+{
+    int device = 0;
+    if (const char* e = getenv("GOLEFT_DEVICE")) device = atoi(e);
+    const int rc = gd_create(device, ctx);
+    if (rc != GD_OK) {
+        fprintf(stderr, "%s: no usable MI355X device (%s); this build has no CPU path\n", prog, gd_strerror(rc));
+        return 1;
+    }
+    return 0;
+}
+
+// Every sample's factor: gd_sample_medians over the whole matrix, then N values of host work in float64.  The level T is
+// the middle median, sorted(med)[N / 2] -- the centre the reference's own scalers use (gmean, dcnv/scalers/scalers.go:
+// 126-130) -- or --level.  med and nonzero are left for the caller; secs: upload, kernels, read-back, passes.
+int sample_scales(const char* prog, gd_ctx* ctx, const EArgs& a, const Matrix& m, std::vector<float>* scale,
+                  std::vector<float>* med, std::vector<uint64_t>* nonzero, double* secs)
+{
+    const size_t N = m.n, rows = m.where.size();
+    if (rows == 0) { fprintf(stderr, "%s: %s has no rows\n", prog, a.input.c_str()); return 1; }
+    med->assign(N, 0.0f);
+    nonzero->assign(N, 0);
+    const int rc = gd_sample_medians(ctx, m.depths.data(), rows, (int)N, med->data(), nonzero->data());
+    if (rc != GD_OK) {
+        fprintf(stderr, "%s: gd_sample_medians: %s (%s)\n", prog, gd_strerror(rc), gd_last_error(ctx));
+        return 1;
+    }
+    (void)gd_sample_medians_timing(ctx, secs, 4);
+    const std::vector<std::string> names = sample_names(m);
+    for (size_t s = 0; s < N; ++s)
+        if ((*nonzero)[s] == 0) {
+            fprintf(stderr, "%s: sample %s (column %zu) has no depth above 0: it has no factor\n", prog, names[s].c_str(), s + 4);
+            return 1;
+        }
+    double T = a.level;
+    if (!a.has_level) {
+        std::vector<float> sorted(*med);
+        std::sort(sorted.begin(), sorted.end());
+        T = (double)sorted[N / 2];
+    }
+    scale->resize(N);
+    for (size_t s = 0; s < N; ++s) {
+        const float f = (float)(T / (double)(*med)[s]);
+        if (!std::isfinite(f)) {
+            fprintf(stderr, "%s: sample %s (column %zu): the factor %g / %g is not finite as a float32\n", prog, names[s].c_str(),
+                    s + 4, T, (double)(*med)[s]);
+            return 1;
+        }
+        (*scale)[s] = f;
+    }
+    return 0;
+}
+
+int run_scales(const EArgs& a, FILE* out)
+{
+    Matrix m;
+    if (int rc = read_matrix(a.input, &m)) return rc;
+    gd_ctx* ctx = nullptr;
+    if (int rc = open_device("scales", &ctx)) return rc;
+    std::vector<float> scale, med;
+    std::vector<uint64_t> nonzero;
+    double secs[4] = {0, 0, 0, 0};
+    const int rc = sample_scales("scales", ctx, a, m, &scale, &med, &nonzero, secs);
+    gd_destroy(ctx);
+    if (rc) return rc;
+    const std::vector<std::string> names = sample_names(m);
+    std::string o;
+    char buf[64];
+    for (size_t s = 0; s < m.n; ++s) {
+        fprintf(stderr, "%s\t%.9g\t%llu\n", names[s].c_str(), (double)med[s], (unsigned long long)nonzero[s]);
+        snprintf(buf, sizeof buf, "%.9g\n", (double)scale[s]);
+        o += buf;
+    }
+    if (fwrite(o.data(), 1, o.size(), out) != o.size() || fflush(out) != 0) { fprintf(stderr, "scales: error writing the factors\n"); return 1; }
+    if (getenv("GOLEFT_EMDEPTH_TIMING"))
+        fprintf(stderr, "{\"rows\": %zu, \"samples\": %zu, \"medians_upload_s\": %.4f, \"medians_kernels_s\": %.4f, "
+                        "\"medians_readback_s\": %.4f, \"medians_passes\": %d}\n",
+                m.where.size(), m.n, secs[0], secs[1], secs[2], (int)secs[3]);
+    return 0;
+}
+
+int apply_scales(Matrix* m, const std::vector<float>& scale)
+{
+    const size_t N = m->n, rows = m->where.size();
+    for (size_t r = 0; r < rows; ++r)
+        for (size_t s = 0; s < N; ++s) {
+            const float d = m->depths[r * N + s] * scale[s];            // float32, one rounding
+            if (!std::isfinite(d)) {
+                fprintf(stderr, "emdepth: row %zu, sample %zu: the scaled depth is not finite\n", r + 1, s + 1);
+                return 1;
+            }
+            m->depths[r * N + s] = d;
+        }
+    return 0;
+}
+
 int run(const EArgs& a, FILE* out)
 {
     const bool timing = getenv("GOLEFT_EMDEPTH_TIMING") != nullptr;
@@ -307,15 +456,7 @@ int run(const EArgs& a, FILE* out)
     if (!a.scales.empty()) {
         std::vector<float> scale;
         if (int rc = read_scales(a.scales, N, &scale)) return rc;
-        for (size_t r = 0; r < rows; ++r)
-            for (size_t s = 0; s < N; ++s) {
-                const float d = m.depths[r * N + s] * scale[s];         // float32, one rounding
-                if (!std::isfinite(d)) {
-                    fprintf(stderr, "emdepth: row %zu, sample %zu: the scaled depth is not finite\n", r + 1, s + 1);
-                    return 1;
-                }
-                m.depths[r * N + s] = d;
-            }
+        if (int rc = apply_scales(&m, scale)) return rc;
     }
     const bool cnvs = !a.cnvs.empty();
     std::vector<uint32_t> starts, ends;
@@ -328,15 +469,16 @@ int run(const EArgs& a, FILE* out)
         if (v < 1) { fprintf(stderr, "emdepth: GOLEFT_EMDEPTH_ROWS must be at least 1\n"); return 1; }
         block = (size_t)v;
     }
-    int device = 0;
-    if (const char* e = getenv("GOLEFT_DEVICE")) device = atoi(e);
     gd_ctx* ctx = nullptr;
-    {
-        const int rc = gd_create(device, &ctx);
-        if (rc != GD_OK) {
-            fprintf(stderr, "emdepth: no usable MI355X device (%s); this build has no CPU path\n", gd_strerror(rc));
-            return 1;
-        }
+    if (int rc = open_device("emdepth", &ctx)) return rc;
+    double med_secs[4] = {0, 0, 0, 0};
+    if (a.normalize) {
+        // the matrix goes up once for the medians and again, scaled, in its blocks
+        std::vector<float> scale, med;
+        std::vector<uint64_t> nonzero;
+        int rc = sample_scales("emdepth", ctx, a, m, &scale, &med, &nonzero, med_secs);
+        if (rc == 0) rc = apply_scales(&m, scale);
+        if (rc) { gd_destroy(ctx); return rc; }
     }
     std::vector<uint8_t> cn(rows * N);
     double lib[3] = {0, 0, 0};
@@ -385,6 +527,10 @@ int run(const EArgs& a, FILE* out)
         if (int rc = write_text(a.cnvs, cnv_text)) return rc;
         t_cnv_write = now_s() - t0;
     }
+    if (timing && a.normalize)
+        fprintf(stderr, "{\"rows\": %zu, \"samples\": %zu, \"medians_upload_s\": %.4f, \"medians_kernels_s\": %.4f, "
+                        "\"medians_readback_s\": %.4f, \"medians_passes\": %d}\n",
+                rows, N, med_secs[0], med_secs[1], med_secs[2], (int)med_secs[3]);
     if (timing && cnvs)
         fprintf(stderr, "{\"rows\": %zu, \"samples\": %zu, \"block_rows\": %zu, \"total_s\": %.4f, \"read_s\": %.4f, \"upload_s\": %.4f, "
                         "\"kernel_s\": %.4f, \"cnv_kernels_s\": %.4f, \"readback_s\": %.4f, \"write_s\": %.4f, \"cnvs\": %llu, "
@@ -403,7 +549,7 @@ int run(const EArgs& a, FILE* out)
 extern "C" int gdh_emdepth_run(int argc, const char* const* argv, const char* out_path)
 {
     EArgs a;
-    const int p = parse_args(argc, argv, &a);
+    const int p = parse_args(argc, argv, &a, false);
     if (p > 0) return 0;
     if (p < 0) return 255;
     FILE* out = stdout;
@@ -417,3 +563,21 @@ extern "C" int gdh_emdepth_run(int argc, const char* const* argv, const char* ou
 }
 
 extern "C" int gdh_emdepth_main(int argc, const char* const* argv) { return gdh_emdepth_run(argc, argv, nullptr); }
+
+extern "C" int gdh_scales_run(int argc, const char* const* argv, const char* out_path)
+{
+    EArgs a;
+    const int p = parse_args(argc, argv, &a, true);
+    if (p > 0) return 0;
+    if (p < 0) return 255;
+    FILE* out = stdout;
+    if (out_path) {
+        out = fopen(out_path, "w");
+        if (!out) { fprintf(stderr, "scales: cannot create %s\n", out_path); return 1; }
+    }
+    int r = run_scales(a, out);
+    if (out_path) { if (fclose(out) != 0 && r == 0) r = 1; }
+    return r;
+}
+
+extern "C" int gdh_scales_main(int argc, const char* const* argv) { return gdh_scales_run(argc, argv, nullptr); }

@@ -1,21 +1,54 @@
-"""`emdepth` entry point: copy numbers per site of a depthwed matrix, goleft's emdepth.EMDepth run on the device
-(the matrix reading, the blocks of rows, the output rows and the exit codes live in the C++ host twin)."""
+"""`emdepth` and `scales` entry points: copy numbers per site of a depthwed matrix, goleft's emdepth.EMDepth run on the
+device, and the per-sample factors that normalise such a matrix first (the matrix reading, the blocks of rows, the output
+rows and the exit codes live in the C++ host twin)."""
 from __future__ import annotations
 
 import ctypes as C
 import sys
 
+import numpy as np
+
 from . import _hostlib
 
 
+def _argv(name, argv):
+    args = [name] + [str(a).encode() for a in argv]
+    return len(args), (C.c_char_p * len(args))(*args)
+
+
 def Main(argv, out_path=None) -> int:
-    """argv: the arguments after the program name, e.g. ["--scales", "scales.txt", "matrix.bed.gz"]: a depthwed
-    matrix (`#chrom start end samples...` and its rows), plain or gzipped, already normalised.
+    """argv: the arguments after the program name, e.g. ["--scales", "scales.txt", "matrix.bed.gz"] or
+    ["--normalize", "--level", "30", "--cnvs", "cnvs.tsv", "matrix.bed"]: a depthwed matrix (`#chrom start end
+    samples...` and its rows), plain or gzipped, already normalised unless --normalize is given.
     The rows go to out_path (stdout when None); returns the exit code."""
     lib = _hostlib.load()
-    args = [b"emdepth"] + [str(a).encode() for a in argv]
-    arr = (C.c_char_p * len(args))(*args)
-    return int(lib.gdh_emdepth_run(len(args), arr, out_path.encode() if out_path else None))
+    n, arr = _argv(b"emdepth", argv)
+    return int(lib.gdh_emdepth_run(n, arr, out_path.encode() if out_path else None))
+
+
+def Scales(argv, out_path=None) -> int:
+    """`goleft-depth scales`: argv e.g. ["--level", "1", "matrix.bed.gz"].  One factor per sample and line goes to
+    out_path (stdout when None), the file `emdepth --scales` takes; returns the exit code."""
+    lib = _hostlib.load()
+    n, arr = _argv(b"scales", argv)
+    return int(lib.gdh_scales_run(n, arr, out_path.encode() if out_path else None))
+
+
+def scales(med, level=None):
+    """The factors that carry every sample to one level, from DepthEngine.sample_medians' medians (all > 0):
+    float32(T / med[s]) with the division in float64 and T = sorted(med)[N // 2], or `level` (1: the 1 / med[s] dcnv's
+    NormalizeBySampleMedian divides by).  What `goleft-depth scales` writes and emdepth_cells takes as its scale."""
+    m = [float(v) for v in np.asarray(med).ravel()]
+    if not m or not all(v > 0 and np.isfinite(v) for v in m):
+        raise ValueError("scales: every sample needs a finite median above 0")
+    T = sorted(m)[len(m) // 2] if level is None else float(level)
+    if not (T > 0 and np.isfinite(T)):
+        raise ValueError("scales: the level must be a finite number > 0")
+    with np.errstate(over="ignore"):
+        out = np.array([np.float32(T / v) for v in m], np.float32)
+    if not np.isfinite(out).all():
+        raise ValueError("scales: a factor is not finite as a float32")
+    return out
 
 
 if __name__ == "__main__":

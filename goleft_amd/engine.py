@@ -331,6 +331,33 @@ class DepthEngine:
         self._chk(self._lib.gd_emdepth_timing(self._ctx, t, 3))
         return tuple(t)
 
+    def sample_medians(self, depths):
+        """dcnv's SampleMedians per column of a [rows][samples] float32 matrix (finite, >= 0; 1 .. 4096 samples, at
+        least one row): (med float32 [samples], nonzero uint64 [samples]).  med[s] is sorted[k + int(0.65 * n)] of
+        sample s, k its zeros and n the rest: the 0.65 quantile of its non-zero depths; 0 when it has none.
+        goleft_amd.emdepth.scales turns them into the factors emdepth_cells takes."""
+        d = np.ascontiguousarray(depths, np.float32)
+        assert d.ndim == 2
+        rows, n = d.shape
+        med, nz = np.empty(n, np.float32), np.empty(n, np.uint64)
+        self._chk(self._lib.gd_sample_medians(self._ctx, d.ctypes.data if d.size else None, rows, n, med.ctypes.data,
+                                              nz.ctypes.data))
+        return med, nz
+
+    def sample_medians_cells(self, dptr: int, rows: int, n_samples: int):
+        """The same for int64 cells in HBM (depthwed_device's pointer), exact for every non-negative int64:
+        (med int64 [samples], nonzero uint64 [samples])."""
+        med, nz = np.empty(n_samples, np.int64), np.empty(n_samples, np.uint64)
+        self._chk(self._lib.gd_sample_medians_cells(self._ctx, C.c_void_p(dptr), rows, n_samples, med.ctypes.data,
+                                                    nz.ctypes.data))
+        return med, nz
+
+    def sample_medians_timing(self):
+        """Of the last sample_medians call: (upload, kernels, read-back) seconds and the passes over the matrix."""
+        t = (C.c_double * 4)()
+        self._chk(self._lib.gd_sample_medians_timing(self._ctx, t, 4))
+        return t[0], t[1], t[2], int(t[3])
+
     def _emcnv_positions(self, starts, ends, rows: int):
         st, en = np.ascontiguousarray(starts, np.uint32), np.ascontiguousarray(ends, np.uint32)
         assert st.shape == (rows,) and en.shape == (rows,)

@@ -39,7 +39,7 @@ extern "C" {
 
 /* GD_ABI_VERSION changes when an existing entry point or structure changes; GD_ABI_REVISION counts the releases that only
  * ADDED entry points since then (revision 1: gd_indexcov_*; 2: gd_indexsplit_*; 3: gd_crai_sizes).  A caller built against (15, r) runs on any (15, r' >= r).
- * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, were added without a revision; look them up by symbol.
+ * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_* and gd_sample_medians*, were added without a revision; look them up by symbol.
  * Why indexcov did not become version 16: nothing that existed changed, so callers of ABI 15 need not be turned away, and
  * tests/test_host_cpu.py holds gd_abi_version() to 15 until something does change. */
 #define GD_ABI_VERSION 15
@@ -701,6 +701,25 @@ int gd_emcnv_read(gd_ctx* ctx, uint32_t* sample /* [n_cnvs] */, uint32_t* psize,
                   float* log2fc);
 int gd_emcnv_end(gd_ctx* ctx);
 int gd_emcnv_timing(gd_ctx* ctx, double* out, size_t n);
+/* ---- dcnv's SampleMedians (dcnv/dcnv.go:108-125): one order statistic per sample of a sites x samples matrix ----
+ * For sample s over all n_rows rows: with the column sorted ascending, k its leading zeros (-0.0 is a zero) and
+ * n = n_rows - k, med[s] = sorted[k + (int)(0.65 * (double)n)] -- the 0.65 quantile of the non-zero depths, not the median,
+ * the product taken in float64 and truncated -- and n_nonzero[s] = n.  An all-zero column (the reference panics) gives 0
+ * and 0.  The selection is exact (a radix select over the bit patterns on the device): med[s] is a value of the column.
+ * n_samples is 1 .. 4096 and n_rows 1 .. 2^31 - 1, GD_E_RANGE otherwise.  n_nonzero may be NULL.  Nothing is kept between
+ * calls; the temporaries are freed on return; a refused call leaves the context usable.
+ *   gd_sample_medians        depths: host float32 [n_rows][n_samples], each finite and >= 0 (GD_E_INVALID otherwise, found
+ *                            before anything runs)
+ *   gd_sample_medians_cells  d_cells: DEVICE int64 [n_rows][n_samples] as gd_depthwed_device leaves them; exact for every
+ *                            non-negative int64 (nothing passes through a float).  A negative cell is found by the
+ *                            first pass over the matrix: GD_E_INVALID, nothing written.  The matrix does not leave HBM.
+ * gd_sample_medians_timing: seconds of the last call (measurement only): upload, kernels, read-back; a fourth value, when
+ * asked for, is the number of passes over the matrix the call ran.  Fills min(n, 4) values. */
+int gd_sample_medians(gd_ctx* ctx, const float* depths, size_t n_rows, int n_samples, float* med /* [n_samples] */,
+                      uint64_t* n_nonzero /* [n_samples] or NULL */);
+int gd_sample_medians_cells(gd_ctx* ctx, const int64_t* d_cells, size_t n_rows, int n_samples, int64_t* med,
+                            uint64_t* n_nonzero);
+int gd_sample_medians_timing(gd_ctx* ctx, double* out, size_t n);
 int gd_ingest_abort(gd_ctx* ctx);
 /* Page-locked host memory for the byte range handed to gd_ingest_bgzf (read the file
  * straight into it: the H2D copy then runs at PCIe speed instead of through a bounce

@@ -192,7 +192,7 @@ int gdh_indexsplit_main(int argc, const char* const* argv);
 int gdh_indexsplit_run(int argc, const char* const* argv, const char* out_path);
 
 /* ---- `emdepth` (emdepth/emdepth.go EMDepth, CN): copy numbers per site of a depthwed matrix, fitted on the device
- * (gd_emdepth).  argv: [--scales FILE] [--cnvs FILE] matrix.bed[.gz] -- the `#chrom start end samples...` header and its rows as
+ * (gd_emdepth).  argv: [--scales FILE | --normalize [--level L]] [--cnvs FILE] matrix.bed[.gz] -- the `#chrom start end samples...` header and its rows as
  * dcnv/dcnv.go:153-186 reads them, 1 or 3 .. 4096 samples, cells parsed with strtod and narrowed to float32; --scales:
  * one factor per line in column order, multiplied in float32.  Nothing else is normalised.  Output: the header, and per
  * row chrom, start, end and one copy number (0 .. 9) per sample.  The file is checked before anything runs: a row whose
@@ -203,6 +203,18 @@ int gdh_indexsplit_run(int argc, const char* const* argv, const char* out_path);
 int gdh_emdepth_main(int argc, const char* const* argv);
 /* Same, writing to out_path (NULL = stdout). */
 int gdh_emdepth_run(int argc, const char* const* argv, const char* out_path);
+
+/* ---- `scales` and `emdepth --normalize [--level L]`: the factors `emdepth --scales` takes, from the matrix itself.  Every
+ * sample's 0.65 quantile of its non-zero depths (dcnv's SampleMedians, dcnv/dcnv.go:108-125; gd_sample_medians on the
+ * device) is carried to one level: scale[s] = (float)((double)T / (double)med[s]), T = sorted(med)[N / 2] or --level (finite
+ * and > 0; 1 gives the 1 / med[s] NormalizeBySampleMedian divides by).  argv: [--level L] matrix.bed[.gz], read and
+ * checked exactly as `emdepth` reads it.  stdout: one factor per line in column order, %.9g of the float32 (what --scales
+ * reads back bit for bit); stderr: per sample its name, median and non-zero count.  A sample without a depth above 0 has no
+ * factor: exit code 1, the sample named.  `emdepth --normalize` computes the same factors in-process and goes on as with
+ * --scales; it excludes --scales, and --level needs it (usage errors, 255). ------------------------------------------- */
+int gdh_scales_main(int argc, const char* const* argv);
+/* Same, writing to out_path (NULL = stdout). */
+int gdh_scales_run(int argc, const char* const* argv, const char* out_path);
 
 /* ---- the slices of a .crai (indexcov/crai/crai.go:129-192 ReadIndex), pure CPU: what `indexcov` and `indexsplit` read
  * from a CRAM index before the device tiles it.  The file is gzip (any number of members) of lines of six tab-separated
