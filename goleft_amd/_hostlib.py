@@ -36,7 +36,9 @@ SYMBOLS = {
     "gdh_emdepth_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p]),
     "gdh_scales_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_scales_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p]),
-    "gdh_samplename_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
+    "gdh_debias_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
+    "gdh_debias_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p]),
+    "gdh_samplename_main":(C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_crai_read": (C.c_int, [C.c_char_p, C.c_size_t, C.c_size_t, _P, _P, _P, _P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                 C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]),
     "gdh_round3g": (None, [_P, C.c_size_t, _P]),

@@ -4,7 +4,7 @@
 // gd_create / gd_destroy, the setters (stream, parameters, path, outputs, contigs, selection), options, statistics and
 // timing.  The rest of the ABI is in the gd_api_*.inc files included at the end, in this order: records (pinned
 // staging ring + copy stream, records host -> HBM, HBM-resident per-contig record streams), compute (route, launch
-// sequencing, look-back), results (read-back), aux, ingest, covstats, indexcov, indexsplit, crai, emdepth, emcnv, colselect, comm.
+// sequencing, look-back), results (read-back), aux, ingest, covstats, indexcov, indexsplit, crai, emdepth, emcnv, colselect, chunkdebias, comm.
 // Replaces gargs' process.Runner + the samtools child + the callback's parse loop of `goleft depth`
 // (depth/depth.go:392-394, :45, :282-325).
 #include "../../include/goleft_depth.h"
@@ -411,6 +411,7 @@ int gd_kernel_ms(gd_ctx* c, int id, float* ms)
 #include "gd_api_emdepth.inc"
 #include "gd_api_emcnv.inc"
 #include "gd_api_colselect.inc"
+#include "gd_api_chunkdebias.inc"
 #include "gd_api_comm.inc"
 
 }  // extern "C"

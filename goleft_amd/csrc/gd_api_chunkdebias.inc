@@ -1,0 +1,129 @@
+// gd_api_chunkdebias.inc -- dcnv's ChunkDebiaser per covariate chunk of a depth matrix (part of gd_api.hip, inside
+// extern "C"; DESIGN.md section 3.13).  The argsort of the covariate and the chunk walk (debiaser.go:140-148) are host work
+// inside the call; the medians and the division are gd_chunkdebias.hpp's kernels.  Nothing is kept between calls but the
+// timings.
+
+namespace {
+
+// the device buffers of one call, freed when it returns
+struct CdBufs {
+    void* cells = nullptr;
+    void* order = nullptr;
+    void* slices = nullptr;
+    void* chunk_of_row = nullptr;
+    void* med = nullptr;
+    void* out = nullptr;
+    void* out64 = nullptr;
+    ~CdBufs()
+    {
+        for (void* p : {cells, order, slices, chunk_of_row, med, out, out64})
+            if (p) (void)hipFree(p);
+    }
+};
+
+}  // namespace
+
+int gd_chunk_debias(gd_ctx* c, const float* depths, size_t n_rows, int n_samples, const double* vals, double score_window,
+                    float* out, double* out64, uint32_t* chunk_of_row, size_t* n_chunks, float* med, size_t med_rows)
+{
+    if (!c) return GD_E_INVALID;
+    if (n_samples < 1 || n_samples > gd::CD_MAX_N)
+        return fail(c, GD_E_RANGE, "chunk debias: 1 .. %d samples, not %d", gd::CD_MAX_N, n_samples);
+    if (n_rows < 1 || n_rows > 0x7fffffffull)
+        return fail(c, GD_E_RANGE, "chunk debias: 1 .. 2^31 - 1 rows, not %zu", n_rows);
+    if (!depths || !vals || !out) return GD_E_INVALID;
+    if (!std::isfinite(score_window) || !(score_window > 0))
+        return fail(c, GD_E_INVALID, "chunk debias: the score window must be a finite number > 0, not %g", score_window);
+    const size_t N = (size_t)n_samples;
+    for (size_t r = 0; r < n_rows; ++r)
+        if (!std::isfinite(vals[r])) return fail(c, GD_E_INVALID, "chunk debias: the value of row %zu is not finite", r);
+    for (size_t i = 0; i < n_rows * N; ++i)
+        if (!(depths[i] >= 0.0f) || !std::isfinite(depths[i]))
+            return fail(c, GD_E_INVALID, "chunk debias: the depth of row %zu, sample %zu is not a finite number >= 0", i / N, i % N);
+
+    // Sort (debiaser.go:56-76) as an index, and the chunk walk of :140-148 over the sorted values.  A boundary needs a
+    // difference above the window, so it never parts equal values: the order among them (here: by row) is immaterial.
+    const double t0 = ing_now();
+    std::vector<uint32_t> order(n_rows), slices, cor(n_rows);
+    for (size_t r = 0; r < n_rows; ++r) order[r] = (uint32_t)r;
+    std::sort(order.begin(), order.end(), [vals](uint32_t a, uint32_t b) { return vals[a] < vals[b] || (vals[a] == vals[b] && a < b); });
+    slices.push_back(0);
+    double v0 = vals[order[0]];
+    size_t largest = 0;
+    for (size_t i = 0; i < n_rows; ++i) {
+        const double v = vals[order[i]];
+        if (v - v0 > score_window) {
+            v0 = v;
+            largest = std::max(largest, i - (size_t)slices.back());
+            slices.push_back((uint32_t)i);
+        }
+        cor[order[i]] = (uint32_t)(slices.size() - 1);
+    }
+    largest = std::max(largest, n_rows - (size_t)slices.back());
+    slices.push_back((uint32_t)n_rows);
+    const size_t C = slices.size() - 1;
+    if (med && med_rows < C) {
+        if (n_chunks) *n_chunks = C;             // (what the medians need)
+        return fail(c, GD_E_CAPACITY, "chunk debias: %zu chunks, the medians have room for %zu", C, med_rows);
+    }
+    if (int r = set_device(c)) return r;
+    for (double& s : c->cd_secs) s = 0;
+    c->cd_secs[0] = ing_now() - t0;
+    c->cd_secs[4] = (double)C;
+    c->cd_secs[5] = (double)largest;
+
+    CdBufs b;
+    const size_t cells = n_rows * N;
+    const double t1 = ing_now();
+    HIPCHK(c, hipMalloc(&b.cells, cells * sizeof(float)));
+    HIPCHK(c, hipMalloc(&b.order, n_rows * sizeof(uint32_t)));
+    HIPCHK(c, hipMalloc(&b.slices, (C + 1) * sizeof(uint32_t)));
+    HIPCHK(c, hipMalloc(&b.chunk_of_row, n_rows * sizeof(uint32_t)));
+    HIPCHK(c, hipMalloc(&b.med, C * N * sizeof(uint32_t)));
+    HIPCHK(c, hipMalloc(&b.out, cells * sizeof(float)));
+    if (out64) HIPCHK(c, hipMalloc(&b.out64, cells * sizeof(double)));
+    HIPCHK(c, hipMemcpyAsync(b.cells, depths, cells * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.order, order.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.slices, slices.data(), (C + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.chunk_of_row, cor.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->cd_secs[1] = ing_now() - t1;
+
+    gd::CdJob j{};
+    j.cells = static_cast<const uint32_t*>(b.cells); j.n_rows = (int64_t)n_rows; j.n = n_samples; j.n_chunks = (uint32_t)C;
+    j.order = static_cast<const uint32_t*>(b.order); j.slices = static_cast<const uint32_t*>(b.slices);
+    j.chunk_of_row = static_cast<const uint32_t*>(b.chunk_of_row); j.med = static_cast<uint32_t*>(b.med);
+    j.out = static_cast<float*>(b.out); j.out64 = static_cast<double*>(b.out64);
+    const unsigned tiles = (unsigned)((N + gd::CD_COLS - 1) / gd::CD_COLS);
+    const dim3 mgrid((unsigned)std::min<size_t>(C, (size_t)gd::CD_MAX_GRID), tiles), mwg(gd::CD_WG);
+    const size_t turns = (n_rows + gd::CD_DIV_WAVES - 1) / gd::CD_DIV_WAVES;
+    const dim3 dgrid((unsigned)std::min<size_t>(turns, (size_t)gd::CD_DIV_MAX_GRID), tiles), dwg(gd::CD_DIV_WAVES * 64);
+    const double t2 = ing_now();
+    hipLaunchKernelGGL(gd::gd_chunkdebias_median_kernel, mgrid, mwg, 0, c->stream, j);
+    HIPCHK(c, hipGetLastError());
+    if (getenv("GOLEFT_CHUNKDEBIAS_SPLIT")) {    // (measurement: the two kernels timed apart)
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->cd_secs[6] = ing_now() - t2;
+    }
+    hipLaunchKernelGGL(gd::gd_chunkdebias_divide_kernel, dgrid, dwg, 0, c->stream, j);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->cd_secs[2] = ing_now() - t2;
+
+    const double t3 = ing_now();
+    HIPCHK(c, hipMemcpyAsync(out, b.out, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (out64) HIPCHK(c, hipMemcpyAsync(out64, b.out64, cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (med) HIPCHK(c, hipMemcpyAsync(med, b.med, C * N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->cd_secs[3] = ing_now() - t3;
+    if (chunk_of_row) memcpy(chunk_of_row, cor.data(), n_rows * sizeof(uint32_t));
+    if (n_chunks) *n_chunks = C;
+    return GD_OK;
+}
+
+int gd_chunk_debias_timing(gd_ctx* c, double* out, size_t n)
+{
+    if (!c || !out) return GD_E_INVALID;
+    for (size_t i = 0; i < n && i < 7; ++i) out[i] = c->cd_secs[i];
+    return GD_OK;
+}

@@ -264,6 +264,8 @@ struct gd_ctx {
     EcState* ec = nullptr;                                     // gd_emcnv_*: the positions, member bits and member values of the rows so far (gd_api_emcnv.inc)
     double sm_secs[3] = {0, 0, 0};                             // gd_sample_medians*: upload, kernels, read-back of the last call (gd_api_colselect.inc)
     int sm_passes = 0;                                         // ... and the passes over the matrix it ran
+    double cd_secs[7] = {0, 0, 0, 0, 0, 0, 0};                 // gd_chunk_debias: sort + chunking, upload, kernels, read-back of the last call; its chunks, its largest chunk;
+                                                               // the median kernel alone when GOLEFT_CHUNKDEBIAS_SPLIT is set (gd_api_chunkdebias.inc)
     double em_secs[3] = {0, 0, 0};                             // gd_emdepth*: upload, kernel, read-back of the last call (gd_api_emdepth.inc)
     uint8_t* h_walk = nullptr; size_t cap_walk = 0;            // gd_ingest_decode, gd_covstats_decode: per-segment tables of the record walk (page-locked host memory
                                                                // the walk kernels read and write over the link: no copy command)

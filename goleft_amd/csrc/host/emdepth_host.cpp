@@ -21,6 +21,19 @@
 // the device) carried to one level, scale[s] = (float)(T / med[s]) with T = sorted(med)[N / 2] or
 // --level.  `emdepth --normalize` computes the same factors in-process and goes on as with --scales: the matrix is
 // uploaded once for the medians and again, scaled, in its blocks.
+//
+//   goleft-depth debias (--gc-values FILE | --fasta ref.fa) [--window W] matrix.bed[.gz]
+//   goleft-depth emdepth (--gc-values FILE | --gc-fasta ref.fa) [--gc-window W] [--level L] [--cnvs FILE] matrix.bed[.gz]
+//
+// `debias` reads the same matrix with the same reader and writes it back with every cell divided by the "median" of its
+// sample over the rows of similar covariate: dcnv's ChunkDebiaser (dcnv/debiaser/debiaser.go:125-171; gd_chunk_debias on
+// the device).  The covariate is one float64 per row -- from a file, one per line in row order, or
+// the GC fraction of [max(start, 250) - 250, end) of a FASTA (dcnv/dcnv.go:82-86; counted by gd_seq_stats_ex under the
+// active GDH_STATS_* contract).  --window (the reference's ScoreWindow) defaults to 0.01: this project's choice, the
+// reference gives none.  Cells go out as %.9g of the float32, which the reader takes back bit for bit.  `emdepth` with a GC
+// flag debiases in-process and then normalises, in the reference's order (dcnv.go:331-337): the quotients are near 1 and
+// EMDepth stops on absolute thresholds, so they go back to depth scale -- the level is --level or the middle sample median
+// of the matrix AS READ, the factors T / med'[s] over the medians of the debiased matrix (this project's definition).
 #include <zlib.h>
 
 #include <algorithm>
@@ -34,13 +47,17 @@
 
 #include "../../../include/goleft_depth.h"
 #include "../../../include/goleft_depth_host.h"
+#include "fasta_stats.hpp"
 
 namespace {
 
+enum { CMD_EMDEPTH = 0, CMD_SCALES = 1, CMD_DEBIAS = 2 };
+
 struct EArgs {
-    std::string scales, cnvs, input;
-    bool normalize = false, has_level = false;
-    double level = 0;
+    std::string scales, cnvs, input, gc_values, gc_fasta;
+    bool normalize = false, has_level = false, has_window = false;
+    double level = 0, window = 0.01;
+    bool gc() const { return !gc_values.empty() || !gc_fasta.empty(); }
 };
 
 void usage_scales(FILE* f)
@@ -52,32 +69,61 @@ void usage_scales(FILE* f)
           "  --level  a finite number > 0 that replaces T (1: the factors 1 / q[s])\n", f);
 }
 
+void usage_debias(FILE* f)
+{
+    fputs("usage: debias (--gc-values FILE | --fasta REF.fa) [--window W] MATRIX\n"
+          "  MATRIX  a depthwed matrix (#chrom start end samples... and its rows), plain or gzipped\n"
+          "  writes the matrix with every cell divided by its sample's median over the rows of similar covariate (dcnv's\n"
+          "  ChunkDebiaser): the rows in covariate order are cut where a value exceeds the chunk's first by more than W\n"
+          "  --gc-values  the covariate: one number per line, one line per row, in row order (GC content or any other)\n"
+          "  --fasta  take the GC fraction of [max(start, 250) - 250, end) of REF.fa (needs REF.fa.fai) instead\n"
+          "  --window  W, a finite number > 0 (default 0.01)\n", f);
+}
+
 void usage(FILE* f)
 {
-    fputs("usage: emdepth [--scales FILE | --normalize [--level L]] [--cnvs FILE] MATRIX\n"
+    fputs("usage: emdepth [--scales FILE | --normalize [--level L] | (--gc-values FILE | --gc-fasta REF.fa) [--gc-window W] [--level L]]\n"
+          "               [--cnvs FILE] MATRIX\n"
           "  MATRIX  a depthwed matrix (#chrom start end samples... and its rows), plain or gzipped, already normalised\n"
           "  --scales  a file of one factor per line, in column order: every depth is multiplied by its sample's factor\n"
           "  --normalize  compute those factors here, as `scales` does: each sample's 0.65 quantile of its non-zero depths\n"
           "               carried to the middle one of them (--level L: to L)\n"
+          "  --gc-values, --gc-fasta, --gc-window  first remove the bias of a per-row covariate as `debias` does (its\n"
+          "               --gc-values, --fasta, --window), then --normalize: to --level, or to the middle one of the\n"
+          "               sample quantiles of the matrix as read\n"
           "  --cnvs  write the CNV calls of every sample (emdepth.Cache) to FILE: sample, index, psize, sites, positions, cn, depth, log2fc\n", f);
 }
 
-// scales_cmd: the `scales` entry, which takes --level alone
-int parse_args(int argc, const char* const* argv, EArgs* a, bool scales_cmd)
+// a finite number > 0 that is all of val
+bool parse_positive(const std::string& val, double* out)
 {
-    const auto usage = [scales_cmd](FILE* f) { scales_cmd ? usage_scales(f) : ::usage(f); };
+    char* end = nullptr;
+    *out = strtod(val.c_str(), &end);
+    return end == val.c_str() + val.size() && std::isfinite(*out) && *out > 0;
+}
+
+// cmd: which entry's arguments these are (CMD_*)
+int parse_args(int argc, const char* const* argv, EArgs* a, int cmd)
+{
+    const auto usage = [cmd](FILE* f) { cmd == CMD_SCALES ? usage_scales(f) : cmd == CMD_DEBIAS ? usage_debias(f) : ::usage(f); };
+    const char* const fasta_key = cmd == CMD_DEBIAS ? "--fasta" : "--gc-fasta";
+    const char* const window_key = cmd == CMD_DEBIAS ? "--window" : "--gc-window";
     std::vector<std::string> pos;
     for (int i = 1; i < argc; ++i) {
         std::string arg = argv[i];
         if (arg == "-h" || arg == "--help") { usage(stdout); return 1; }
         if (arg == "--") { for (++i; i < argc; ++i) pos.push_back(argv[i]); break; }
-        if (arg == "--normalize" && !scales_cmd) { a->normalize = true; continue; }
+        if (arg == "--normalize" && cmd == CMD_EMDEPTH) { a->normalize = true; continue; }
         if (arg.size() > 1 && arg[0] == '-') {
             std::string key = arg, val;
             bool has_val = false;
             const size_t eq = arg.find('=');
             if (eq != std::string::npos) { key = arg.substr(0, eq); val = arg.substr(eq + 1); has_val = true; }
-            if (key != "--level" && (scales_cmd || (key != "--scales" && key != "--cnvs"))) {
+            const bool gc_key = key == "--gc-values" || key == fasta_key || key == window_key;
+            const bool known = cmd == CMD_SCALES ? key == "--level"
+                             : cmd == CMD_DEBIAS ? gc_key
+                                                 : key == "--level" || key == "--scales" || key == "--cnvs" || gc_key;
+            if (!known) {
                 fprintf(stderr, "error: unknown argument %s\n", arg.c_str());
                 usage(stderr);
                 return -1;
@@ -87,18 +133,17 @@ int parse_args(int argc, const char* const* argv, EArgs* a, bool scales_cmd)
                 val = argv[++i];
             }
             if (val.empty()) { fprintf(stderr, "error: empty value for %s\n", key.c_str()); usage(stderr); return -1; }
-            if (key == "--level") {
-                char* end = nullptr;
-                a->level = strtod(val.c_str(), &end);
-                if (end != val.c_str() + val.size() || !std::isfinite(a->level) || !(a->level > 0)) {
-                    fprintf(stderr, "error: --level must be a finite number > 0, not '%s'\n", val.c_str());
+            if (key == "--level" || key == window_key) {
+                const bool level = key == "--level";
+                if (!parse_positive(val, level ? &a->level : &a->window)) {
+                    fprintf(stderr, "error: %s must be a finite number > 0, not '%s'\n", key.c_str(), val.c_str());
                     usage(stderr);
                     return -1;
                 }
-                a->has_level = true;
+                (level ? a->has_level : a->has_window) = true;
                 continue;
             }
-            (key == "--scales" ? a->scales : a->cnvs) = val;
+            (key == "--scales" ? a->scales : key == "--cnvs" ? a->cnvs : key == "--gc-values" ? a->gc_values : a->gc_fasta) = val;
             continue;
         }
         pos.push_back(arg);
@@ -108,7 +153,28 @@ int parse_args(int argc, const char* const* argv, EArgs* a, bool scales_cmd)
         usage(stderr);
         return -1;
     }
-    if (a->has_level && !a->normalize && !scales_cmd) {
+    if (!a->gc_values.empty() && !a->gc_fasta.empty()) {
+        fprintf(stderr, "error: --gc-values and %s both name the covariate: give one of them\n", fasta_key);
+        usage(stderr);
+        return -1;
+    }
+    if (cmd == CMD_DEBIAS && !a->gc()) {
+        fprintf(stderr, "error: the covariate is required: --gc-values FILE or --fasta REF.fa\n");
+        usage(stderr);
+        return -1;
+    }
+    if (a->gc() && !a->scales.empty()) {
+        fprintf(stderr, "error: the GC flags normalise after the debiasing, as --normalize does: --scales cannot be given with them\n");
+        usage(stderr);
+        return -1;
+    }
+    if (a->has_window && !a->gc()) {
+        fprintf(stderr, "error: %s is the window of the debiasing: it needs --gc-values or %s\n", window_key, fasta_key);
+        usage(stderr);
+        return -1;
+    }
+    if (a->gc() && cmd == CMD_EMDEPTH) a->normalize = true;
+    if (a->has_level && !a->normalize && cmd == CMD_EMDEPTH) {
         fprintf(stderr, "error: --level sets the level --normalize carries the samples to: it needs --normalize\n");
         usage(stderr);
         return -1;
@@ -364,9 +430,10 @@ int open_device(const char* prog, gd_ctx** ctx)
 
 // Every sample's factor: gd_sample_medians over the whole matrix, then N values of host work in float64.  The level T is
 // the middle median, sorted(med)[N / 2] -- the centre the reference's own scalers use (gmean, dcnv/scalers/scalers.go:
-// 126-130) -- or --level.  med and nonzero are left for the caller; secs: upload, kernels, read-back, passes.
+// 126-130) -- or --level.  med and nonzero are left for the caller; secs: upload, kernels, read-back, passes.  level_out
+// (or null) gets T; scale may be null when T is all that is wanted.
 int sample_scales(const char* prog, gd_ctx* ctx, const EArgs& a, const Matrix& m, std::vector<float>* scale,
-                  std::vector<float>* med, std::vector<uint64_t>* nonzero, double* secs)
+                  std::vector<float>* med, std::vector<uint64_t>* nonzero, double* secs, double* level_out = nullptr)
 {
     const size_t N = m.n, rows = m.where.size();
     if (rows == 0) { fprintf(stderr, "%s: %s has no rows\n", prog, a.input.c_str()); return 1; }
@@ -390,6 +457,8 @@ int sample_scales(const char* prog, gd_ctx* ctx, const EArgs& a, const Matrix& m
         std::sort(sorted.begin(), sorted.end());
         T = (double)sorted[N / 2];
     }
+    if (level_out) *level_out = T;
+    if (!scale) return 0;
     scale->resize(N);
     for (size_t s = 0; s < N; ++s) {
         const float f = (float)(T / (double)(*med)[s]);
@@ -428,6 +497,167 @@ int run_scales(const EArgs& a, FILE* out)
         fprintf(stderr, "{\"rows\": %zu, \"samples\": %zu, \"medians_upload_s\": %.4f, \"medians_kernels_s\": %.4f, "
                         "\"medians_readback_s\": %.4f, \"medians_passes\": %d}\n",
                 m.where.size(), m.n, secs[0], secs[1], secs[2], (int)secs[3]);
+    return 0;
+}
+
+// --gc-values: one float64 per line, one line per row, in row order
+int read_vals(const char* prog, const std::string& path, size_t rows, std::vector<double>* out)
+{
+    gzFile f = gzopen(path.c_str(), "rb");
+    if (!f) { fprintf(stderr, "%s: cannot open %s\n", prog, path.c_str()); return 1; }
+    struct Close { gzFile f; ~Close() { gzclose(f); } } closer{f};
+    std::string line;
+    long long lineno = 0;
+    while (read_line(f, &line)) {
+        ++lineno;
+        size_t a = 0, b = line.size();
+        while (a < b && (line[a] == ' ' || line[a] == '\t')) ++a;
+        while (b > a && (line[b - 1] == ' ' || line[b - 1] == '\t')) --b;
+        const std::string t = line.substr(a, b - a);
+        char* end = nullptr;
+        const double v = t.empty() ? 0 : strtod(t.c_str(), &end);
+        if (t.empty() || end != t.c_str() + t.size() || !std::isfinite(v)) {
+            fprintf(stderr, "%s: %s: line %lld is not a finite number\n", prog, path.c_str(), lineno);
+            return 1;
+        }
+        if (out->size() == rows) {
+            fprintf(stderr, "%s: %s: line %lld: the matrix has only %zu rows\n", prog, path.c_str(), lineno, rows);
+            return 1;
+        }
+        out->push_back(v);
+    }
+    if (out->size() != rows) {
+        fprintf(stderr, "%s: %s ends after line %lld: the matrix has %zu rows\n", prog, path.c_str(), lineno, rows);
+        return 1;
+    }
+    return 0;
+}
+
+// all of [s, e) as a decimal int64 below 2^62
+bool parse_i64(const char* s, const char* e, int64_t* out)
+{
+    if (s == e) return false;
+    int64_t v = 0;
+    for (; s < e; ++s) {
+        if (*s < '0' || *s > '9' || v > ((int64_t)1 << 58)) return false;
+        v = v * 10 + (int64_t)(*s - '0');
+    }
+    *out = v;
+    return true;
+}
+
+// --fasta: the GC fraction of [max(start, 250) - 250, end) of every row (dcnv/dcnv.go:82-86), as a float64: n_gc over the
+// denominator of the active GDH_STATS_* contract, 0 for an empty one.  Each chromosome goes to the device once
+// (gd_seq_load), in order of first appearance; the counts are gd_seq_stats_ex's.
+int fasta_vals(const char* prog, gd_ctx* ctx, const std::string& fasta, const std::string& path, const Matrix& m,
+               std::vector<double>* out)
+{
+    gdh::FastaStats fa;
+    std::string err;
+    if (!fa.open(fasta, &err)) { fprintf(stderr, "%s: %s\n", prog, err.c_str()); return 1; }
+    const size_t rows = m.where.size();
+    std::vector<std::string> chroms;             // in order of first appearance
+    std::vector<std::vector<size_t>> rows_of;
+    std::vector<int64_t> start(rows), end(rows);
+    for (size_t r = 0; r < rows; ++r) {
+        const std::string& w = m.where[r];
+        const size_t t1 = w.find('\t'), t2 = t1 == std::string::npos ? t1 : w.find('\t', t1 + 1);
+        if (t2 == std::string::npos || !parse_i64(w.c_str() + t1 + 1, w.c_str() + t2, &start[r]) ||
+            !parse_i64(w.c_str() + t2 + 1, w.c_str() + w.size(), &end[r])) {
+            fprintf(stderr, "%s: %s: line %lld: --fasta needs start and end as decimal numbers\n", prog, path.c_str(), m.lineno[r]);
+            return 1;
+        }
+        start[r] = std::max<int64_t>(start[r], 250) - 250;                     // dcnv.go:83-86
+        const std::string chrom = w.substr(0, t1);
+        size_t k = 0;
+        while (k < chroms.size() && chroms[k] != chrom) ++k;
+        if (k == chroms.size()) { chroms.push_back(chrom); rows_of.emplace_back(); }
+        rows_of[k].push_back(r);
+    }
+    const int contract = gdh_get_stats_contract();
+    out->assign(rows, 0.0);
+    std::string bases;
+    for (size_t k = 0; k < chroms.size(); ++k) {
+        int64_t line_bases = 0;
+        if (!fa.contig_bases(chroms[k], &bases, &line_bases)) {
+            fprintf(stderr, "%s: chromosome %s is not in %s.fai\n", prog, chroms[k].c_str(), fasta.c_str());
+            return 1;
+        }
+        int rc = gd_seq_load(ctx, reinterpret_cast<const uint8_t*>(bases.data()), (int64_t)bases.size());
+        const size_t n = rows_of[k].size();
+        std::vector<int64_t> s(n), e(n);
+        for (size_t i = 0; i < n; ++i) { s[i] = start[rows_of[k][i]]; e[i] = end[rows_of[k][i]]; }
+        std::vector<uint32_t> gc(n, 0), cpg(n, 0), low(n, 0), acgt(n, 0), lacgt(n, 0);
+        const bool raw = (contract & GDH_STATS_CPG_RAW_LINES) && line_bases > 0 && line_bases < 0x7fffffff;
+        if (rc == GD_OK)
+            rc = gd_seq_stats_ex(ctx, n, s.data(), e.data(), raw ? (int32_t)line_bases : 0, gc.data(), cpg.data(), low.data(),
+                                 acgt.data(), lacgt.data());
+        if (rc != GD_OK) { fprintf(stderr, "%s: gd_seq_stats: %s (%s)\n", prog, gd_strerror(rc), gd_last_error(ctx)); return 1; }
+        for (size_t i = 0; i < n; ++i) {
+            const double tot = (contract & GDH_STATS_DENOM_ACGT) ? (double)acgt[i] : (double)(e[i] - s[i]);
+            (*out)[rows_of[k][i]] = tot > 0 ? (double)gc[i] / tot : 0.0;
+        }
+    }
+    return 0;
+}
+
+// The covariate of --gc-values or the FASTA, then gd_chunk_debias over the whole matrix: m's depths become the quotients.
+// A quotient that is not finite as a float32 has no text the reader takes back: refused with its row and sample.
+// secs: gd_chunk_debias_timing's seven values.
+int debias_matrix(const char* prog, gd_ctx* ctx, const EArgs& a, Matrix* m, std::vector<double>* vals, double* secs)
+{
+    const size_t N = m->n, rows = m->where.size();
+    if (rows == 0) { fprintf(stderr, "%s: %s has no rows\n", prog, a.input.c_str()); return 1; }
+    if (!a.gc_values.empty()) {
+        if (int rc = read_vals(prog, a.gc_values, rows, vals)) return rc;
+    } else if (int rc = fasta_vals(prog, ctx, a.gc_fasta, a.input, *m, vals)) {
+        return rc;
+    }
+    std::vector<float> out(rows * N);
+    const int rc = gd_chunk_debias(ctx, m->depths.data(), rows, (int)N, vals->data(), a.window, out.data(), nullptr, nullptr,
+                                   nullptr, nullptr, 0);
+    if (rc != GD_OK) { fprintf(stderr, "%s: gd_chunk_debias: %s (%s)\n", prog, gd_strerror(rc), gd_last_error(ctx)); return 1; }
+    (void)gd_chunk_debias_timing(ctx, secs, 7);
+    for (size_t i = 0; i < rows * N; ++i)
+        if (!std::isfinite(out[i])) {
+            fprintf(stderr, "%s: row %zu, sample %zu: the debiased depth is not finite as a float32\n", prog, i / N + 1, i % N + 1);
+            return 1;
+        }
+    m->depths.swap(out);
+    return 0;
+}
+
+void print_debias_timing(size_t rows, size_t N, const double* secs)
+{
+    fprintf(stderr, "{\"rows\": %zu, \"samples\": %zu, \"debias_sort_s\": %.4f, \"debias_upload_s\": %.4f, \"debias_kernels_s\": %.4f, "
+                    "\"debias_readback_s\": %.4f, \"debias_chunks\": %llu, \"debias_largest_chunk\": %llu}\n",
+            rows, N, secs[0], secs[1], secs[2], secs[3], (unsigned long long)secs[4], (unsigned long long)secs[5]);
+}
+
+int run_debias(const EArgs& a, FILE* out)
+{
+    Matrix m;
+    if (int rc = read_matrix(a.input, &m)) return rc;
+    gd_ctx* ctx = nullptr;
+    if (int rc = open_device("debias", &ctx)) return rc;
+    std::vector<double> vals;
+    double secs[7] = {0, 0, 0, 0, 0, 0, 0};
+    const int rc = debias_matrix("debias", ctx, a, &m, &vals, secs);
+    gd_destroy(ctx);
+    if (rc) return rc;
+    const size_t N = m.n, rows = m.where.size();
+    if (!a.gc_fasta.empty())                     // the covariate the FASTA gave, for the record: --gc-values takes it back
+        for (size_t r = 0; r < rows; ++r) fprintf(stderr, "%s\t%.17g\n", m.where[r].c_str(), vals[r]);
+    std::string o = m.header;
+    o += '\n';
+    char buf[64];
+    for (size_t r = 0; r < rows; ++r) {
+        o += m.where[r];
+        for (size_t s = 0; s < N; ++s) { snprintf(buf, sizeof buf, "\t%.9g", (double)m.depths[r * N + s]); o += buf; }
+        o += '\n';
+    }
+    if (fwrite(o.data(), 1, o.size(), out) != o.size() || fflush(out) != 0) { fprintf(stderr, "debias: error writing the rows\n"); return 1; }
+    if (getenv("GOLEFT_EMDEPTH_TIMING")) print_debias_timing(rows, N, secs);
     return 0;
 }
 
@@ -471,12 +701,27 @@ int run(const EArgs& a, FILE* out)
     }
     gd_ctx* ctx = nullptr;
     if (int rc = open_device("emdepth", &ctx)) return rc;
-    double med_secs[4] = {0, 0, 0, 0};
+    double med_secs[4] = {0, 0, 0, 0}, gc_secs[7] = {0, 0, 0, 0, 0, 0, 0};
+    EArgs norm = a;                              // what the normalisation after a debiasing is asked for
+    if (a.gc()) {
+        // debias, then normalise (dcnv.go:331-337).  The quotients are near 1; the level that carries them back to depth
+        // scale is --level, or the T --normalize would have chosen on the matrix as read
+        int rc = 0;
+        if (!a.has_level) {
+            std::vector<float> med;
+            std::vector<uint64_t> nonzero;
+            rc = sample_scales("emdepth", ctx, a, m, nullptr, &med, &nonzero, med_secs, &norm.level);
+            norm.has_level = true;
+        }
+        std::vector<double> vals;
+        if (rc == 0) rc = debias_matrix("emdepth", ctx, a, &m, &vals, gc_secs);
+        if (rc) { gd_destroy(ctx); return rc; }
+    }
     if (a.normalize) {
         // the matrix goes up once for the medians and again, scaled, in its blocks
         std::vector<float> scale, med;
         std::vector<uint64_t> nonzero;
-        int rc = sample_scales("emdepth", ctx, a, m, &scale, &med, &nonzero, med_secs);
+        int rc = sample_scales("emdepth", ctx, norm, m, &scale, &med, &nonzero, med_secs);
         if (rc == 0) rc = apply_scales(&m, scale);
         if (rc) { gd_destroy(ctx); return rc; }
     }
@@ -527,6 +772,7 @@ int run(const EArgs& a, FILE* out)
         if (int rc = write_text(a.cnvs, cnv_text)) return rc;
         t_cnv_write = now_s() - t0;
     }
+    if (timing && a.gc()) print_debias_timing(rows, N, gc_secs);
     if (timing && a.normalize)
         fprintf(stderr, "{\"rows\": %zu, \"samples\": %zu, \"medians_upload_s\": %.4f, \"medians_kernels_s\": %.4f, "
                         "\"medians_readback_s\": %.4f, \"medians_passes\": %d}\n",
@@ -549,7 +795,7 @@ int run(const EArgs& a, FILE* out)
 extern "C" int gdh_emdepth_run(int argc, const char* const* argv, const char* out_path)
 {
     EArgs a;
-    const int p = parse_args(argc, argv, &a, false);
+    const int p = parse_args(argc, argv, &a, CMD_EMDEPTH);
     if (p > 0) return 0;
     if (p < 0) return 255;
     FILE* out = stdout;
@@ -567,7 +813,7 @@ extern "C" int gdh_emdepth_main(int argc, const char* const* argv) { return gdh_
 extern "C" int gdh_scales_run(int argc, const char* const* argv, const char* out_path)
 {
     EArgs a;
-    const int p = parse_args(argc, argv, &a, true);
+    const int p = parse_args(argc, argv, &a, CMD_SCALES);
     if (p > 0) return 0;
     if (p < 0) return 255;
     FILE* out = stdout;
@@ -581,3 +827,21 @@ extern "C" int gdh_scales_run(int argc, const char* const* argv, const char* out
 }
 
 extern "C" int gdh_scales_main(int argc, const char* const* argv) { return gdh_scales_run(argc, argv, nullptr); }
+
+extern "C" int gdh_debias_run(int argc, const char* const* argv, const char* out_path)
+{
+    EArgs a;
+    const int p = parse_args(argc, argv, &a, CMD_DEBIAS);
+    if (p > 0) return 0;
+    if (p < 0) return 255;
+    FILE* out = stdout;
+    if (out_path) {
+        out = fopen(out_path, "w");
+        if (!out) { fprintf(stderr, "debias: cannot create %s\n", out_path); return 1; }
+    }
+    int r = run_debias(a, out);
+    if (out_path) { if (fclose(out) != 0 && r == 0) r = 1; }
+    return r;
+}
+
+extern "C" int gdh_debias_main(int argc, const char* const* argv) { return gdh_debias_run(argc, argv, nullptr); }

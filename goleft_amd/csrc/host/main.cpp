@@ -8,7 +8,8 @@
 //   goleft-depth indexsplit -n N [--fai FAI] [-p BED] a.bam b.bam ...       (goleft indexsplit: N regions of about equal data)
 //   goleft-depth emdepth [--scales FILE | --normalize [--level L]] [--cnvs FILE] matrix.bed[.gz]   (goleft's emdepth package: copy numbers per site of a depthwed matrix)
 //   goleft-depth scales [--level L] matrix.bed[.gz]                         (the factors emdepth --scales takes: dcnv's sample medians carried to one level)
-//   goleft-depth samplename [-e] a.bam                                      (goleft samplename: the @RG SM values)
+//   goleft-depth debias (--gc-values FILE | --fasta ref.fa) [--window W] matrix.bed[.gz]   (dcnv's ChunkDebiaser: the matrix freed of GC bias; emdepth takes the same as --gc-values | --gc-fasta, --gc-window)
+//   goleft-depth samplename [-e] a.bam                                     (goleft samplename: the @RG SM values)
 //   samtools depth -Q q -d D -r REGION in.bam                   (the same program installed under the NAME samtools,
 //                                                                goleft_amd/shim/samtools: an unmodified goleft finds it on PATH)
 #include <unistd.h>
@@ -77,6 +78,11 @@ int main(int argc, char** argv)
         av.push_back("scales");
         for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
         return leave(gdh_scales_main((int)av.size(), av.data()));
+    }
+    if (argc > 1 && strcmp(argv[1], "debias") == 0) {
+        av.push_back("debias");
+        for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
+        return leave(gdh_debias_main((int)av.size(), av.data()));
     }
     if (argc > 1 && strcmp(argv[1], "samplename") == 0) {
         av.push_back("samplename");

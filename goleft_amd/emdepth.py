@@ -1,5 +1,6 @@
-"""`emdepth` and `scales` entry points: copy numbers per site of a depthwed matrix, goleft's emdepth.EMDepth run on the
-device, and the per-sample factors that normalise such a matrix first (the matrix reading, the blocks of rows, the output
+"""`emdepth`, `scales` and `debias` entry points: copy numbers per site of a depthwed matrix, goleft's emdepth.EMDepth run
+on the device, the per-sample factors that normalise such a matrix first, and dcnv's ChunkDebiaser, which frees it of GC
+bias before that (the matrix reading, the blocks of rows, the output
 rows and the exit codes live in the C++ host twin)."""
 from __future__ import annotations
 
@@ -18,8 +19,9 @@ def _argv(name, argv):
 
 def Main(argv, out_path=None) -> int:
     """argv: the arguments after the program name, e.g. ["--scales", "scales.txt", "matrix.bed.gz"] or
-    ["--normalize", "--level", "30", "--cnvs", "cnvs.tsv", "matrix.bed"]: a depthwed matrix (`#chrom start end
-    samples...` and its rows), plain or gzipped, already normalised unless --normalize is given.
+    ["--normalize", "--level", "30", "--cnvs", "cnvs.tsv", "matrix.bed"] or ["--gc-values", "gc.txt", "matrix.bed"]: a
+    depthwed matrix (`#chrom start end samples...` and its rows), plain or gzipped, already normalised unless --normalize
+    or a GC flag (--gc-values FILE | --gc-fasta REF.fa, [--gc-window W]: debias as Debias does, then normalise) is given.
     The rows go to out_path (stdout when None); returns the exit code."""
     lib = _hostlib.load()
     n, arr = _argv(b"emdepth", argv)
@@ -32,6 +34,15 @@ def Scales(argv, out_path=None) -> int:
     lib = _hostlib.load()
     n, arr = _argv(b"scales", argv)
     return int(lib.gdh_scales_run(n, arr, out_path.encode() if out_path else None))
+
+
+def Debias(argv, out_path=None) -> int:
+    """`goleft-depth debias`: argv e.g. ["--gc-values", "gc.txt", "--window", "0.02", "matrix.bed.gz"] or ["--fasta",
+    "ref.fa", "matrix.bed"].  The matrix with every cell divided by its sample's median over the rows of similar covariate
+    (dcnv's ChunkDebiaser) goes to out_path (stdout when None); returns the exit code."""
+    lib = _hostlib.load()
+    n, arr = _argv(b"debias", argv)
+    return int(lib.gdh_debias_run(n, arr, out_path.encode() if out_path else None))
 
 
 def scales(med, level=None):

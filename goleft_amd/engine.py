@@ -358,6 +358,35 @@ class DepthEngine:
         self._chk(self._lib.gd_sample_medians_timing(self._ctx, t, 4))
         return t[0], t[1], t[2], int(t[3])
 
+    def chunk_debias(self, depths, vals, window, want64=False):
+        """dcnv's ChunkDebiaser on a [rows][samples] float32 matrix (finite, >= 0; 1 .. 4096 samples, at least one row):
+        the rows are cut into chunks by vals (float64 [rows], finite; a row more than `window` above the value that
+        opened the current chunk opens the next) and every sample's cells of a chunk are divided, in float64, by
+        sorted[(n - k) / 2] of them (k their zeros) when that is > 0.  Returns (out float32 [rows, samples],
+        chunk_of_row uint32 [rows], med float32 [chunks, samples]); with want64 the float64 quotients come fourth."""
+        d = np.ascontiguousarray(depths, np.float32)
+        v = np.ascontiguousarray(vals, np.float64)
+        assert d.ndim == 2 and v.ndim == 1
+        rows, n = d.shape
+        assert v.shape == (rows,)
+        out, cor = np.empty((rows, n), np.float32), np.empty(rows, np.uint32)
+        out64 = np.empty((rows, n), np.float64) if want64 else None
+        med = np.empty((rows, n), np.float32)        # (room for a chunk a row; only the chunks' rows are ever touched)
+        nc = C.c_size_t()
+        self._chk(self._lib.gd_chunk_debias(self._ctx, d.ctypes.data if d.size else None, rows, n,
+                                            v.ctypes.data if v.size else None, float(window), out.ctypes.data,
+                                            out64.ctypes.data if want64 else None, cor.ctypes.data, C.byref(nc),
+                                            med.ctypes.data, rows))
+        med = med[:nc.value].copy()
+        return (out, cor, med, out64) if want64 else (out, cor, med)
+
+    def chunk_debias_timing(self):
+        """Of the last chunk_debias call: (host sort + chunking, upload, kernels, read-back) seconds, the chunks, the rows
+        of the largest chunk, and the median kernel's seconds alone (0 unless GOLEFT_CHUNKDEBIAS_SPLIT is set)."""
+        t = (C.c_double * 7)()
+        self._chk(self._lib.gd_chunk_debias_timing(self._ctx, t, 7))
+        return t[0], t[1], t[2], t[3], int(t[4]), int(t[5]), t[6]
+
     def _emcnv_positions(self, starts, ends, rows: int):
         st, en = np.ascontiguousarray(starts, np.uint32), np.ascontiguousarray(ends, np.uint32)
         assert st.shape == (rows,) and en.shape == (rows,)

@@ -39,7 +39,7 @@ extern "C" {
 
 /* GD_ABI_VERSION changes when an existing entry point or structure changes; GD_ABI_REVISION counts the releases that only
  * ADDED entry points since then (revision 1: gd_indexcov_*; 2: gd_indexsplit_*; 3: gd_crai_sizes).  A caller built against (15, r) runs on any (15, r' >= r).
- * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_* and gd_sample_medians*, were added without a revision; look them up by symbol.
+ * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, gd_sample_medians* and gd_chunk_debias*, were added without a revision; look them up by symbol.
  * Why indexcov did not become version 16: nothing that existed changed, so callers of ABI 15 need not be turned away, and
  * tests/test_host_cpu.py holds gd_abi_version() to 15 until something does change. */
 #define GD_ABI_VERSION 15
@@ -720,6 +720,28 @@ int gd_sample_medians(gd_ctx* ctx, const float* depths, size_t n_rows, int n_sam
 int gd_sample_medians_cells(gd_ctx* ctx, const int64_t* d_cells, size_t n_rows, int n_samples, int64_t* med,
                             uint64_t* n_nonzero);
 int gd_sample_medians_timing(gd_ctx* ctx, double* out, size_t n);
+/* ---- dcnv's ChunkDebiaser (dcnv/debiaser/debiaser.go:125-171): a depth matrix freed of a per-row covariate's bias ----
+ * vals[r] is the covariate of row r (GC content, say).  The rows, taken in ascending vals order, are cut into chunks: the
+ * first row opens one, and a row whose value exceeds the value that OPENED the current chunk by more than score_window (a
+ * float64 subtraction, strictly greater) opens the next.  For every chunk and sample: with the n cells sorted ascending and
+ * k the leading zeros (-0.0 is a zero), median = sorted[(n - k) / 2] -- the index counts from the start, so n < 3k gives 0;
+ * when the median is > 0 every cell becomes (double)d / (double)median, otherwise the cells stay.  out gets the quotients
+ * narrowed to float32 (an overflow is stored as the IEEE result, inf), out64 (or NULL) the float64 quotients themselves: for
+ * a matrix whose cells are float32 values these are the reference's, bit for bit, whatever order its argsort gives tied
+ * vals.  chunk_of_row (or NULL) gets every row's chunk, n_chunks (or NULL) their number C, med (or NULL) the C x n_samples
+ * medians (values of the matrix, +0.0 for a zero); med_rows is med's capacity in rows: fewer than C is GD_E_CAPACITY (with
+ * n_chunks set).  n_samples is 1 .. 4096 and n_rows 1 .. 2^31 - 1, GD_E_RANGE otherwise; a depth that is not finite and
+ * >= 0, a val that is not finite, a score_window that is not finite and > 0 (the reference panics on 0): GD_E_INVALID.  All
+ * refusals happen before anything runs and leave the context usable.  The argsort and the chunk walk are host work inside
+ * the call; nothing is kept between calls; the temporaries are freed on return.
+ * gd_chunk_debias_timing (measurement only), of the last call: seconds of host sort + chunking, upload, kernels, read-back;
+ * then the chunk count and the rows of the largest chunk; a seventh value is the median kernel's seconds alone when the
+ * environment has GOLEFT_CHUNKDEBIAS_SPLIT (the kernels are then synchronised apart).  Fills min(n, 7) values. */
+int gd_chunk_debias(gd_ctx* ctx, const float* depths, size_t n_rows, int n_samples, const double* vals /* [n_rows] */,
+                    double score_window, float* out /* [n_rows][n_samples] */, double* out64 /* same shape or NULL */,
+                    uint32_t* chunk_of_row /* [n_rows] or NULL */, size_t* n_chunks /* or NULL */,
+                    float* med /* [n_chunks][n_samples] or NULL; capacity med_rows */, size_t med_rows);
+int gd_chunk_debias_timing(gd_ctx* ctx, double* out, size_t n);
 int gd_ingest_abort(gd_ctx* ctx);
 /* Page-locked host memory for the byte range handed to gd_ingest_bgzf (read the file
  * straight into it: the H2D copy then runs at PCIe speed instead of through a bounce

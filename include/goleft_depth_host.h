@@ -199,6 +199,7 @@ int gdh_indexsplit_run(int argc, const char* const* argv, const char* out_path);
  * column count differs from the header's, or a cell that is not a finite number >= 0, is reported with its line number.
  * --cnvs: also join every sample's aberrant sites into CNV calls as emdepth.Cache does (gd_emcnv_*) and write them to
  * FILE, one line per call; start and end must then be decimal numbers below 2^32 (reported with the line number).
+ * (--gc-values FILE | --gc-fasta REF.fa) [--gc-window W] [--level L]: debias first, then normalise -- see `debias` below.
  * Returns the exit code (1 on an error, with no row written; 255 on a usage error). ---------------------------------- */
 int gdh_emdepth_main(int argc, const char* const* argv);
 /* Same, writing to out_path (NULL = stdout). */
@@ -215,6 +216,25 @@ int gdh_emdepth_run(int argc, const char* const* argv, const char* out_path);
 int gdh_scales_main(int argc, const char* const* argv);
 /* Same, writing to out_path (NULL = stdout). */
 int gdh_scales_run(int argc, const char* const* argv, const char* out_path);
+
+/* ---- `debias` and `emdepth --gc-values FILE | --gc-fasta REF.fa [--gc-window W] [--level L]`: dcnv's ChunkDebiaser
+ * (dcnv/debiaser/debiaser.go:125-171; gd_chunk_debias on the device) on a depthwed matrix.  argv: (--gc-values FILE |
+ * --fasta REF.fa) [--window W] matrix.bed[.gz], the matrix read and checked exactly as `emdepth` reads it.  The covariate is
+ * one float64 per row: --gc-values, one number per line and one line per row in row order (a count or parse error names the
+ * line), or --fasta, the GC fraction of [max(start, 250) - 250, end) as dcnv/dcnv.go:82-86 takes it -- n_gc over the
+ * denominator of the active GDH_STATS_* contract, 0 for an empty one; each chromosome is loaded once, in order of first
+ * appearance; one missing from the .fai is an error that names it; faidx.Stats is external, so parity is unpinned as for
+ * --stats; stderr then gets every row's `chrom start end` and its value as %.17g.  The printed start is not altered.
+ * --window (ScoreWindow) is finite and > 0 and defaults to 0.01, this project's choice (the reference gives none).  stdout:
+ * the header, and per row chrom, start, end as read and %.9g of every float32 quotient, which the reader takes back bit for
+ * bit; a quotient that is not finite as a float32 is an error that names row and sample.  `emdepth` with a GC flag debiases
+ * in-process and then normalises as --normalize does (the flags imply it; --scales with them is a usage error): to --level,
+ * or to the middle sample quantile of the matrix AS READ; its output is that of `debias ... | emdepth --normalize --level L`
+ * byte for byte.  With GOLEFT_EMDEPTH_TIMING both print the split of gd_chunk_debias and the chunk count.  Returns the exit
+ * code (1 on an error, with no row written; 255 on a usage error). ------------------------------------------------------ */
+int gdh_debias_main(int argc, const char* const* argv);
+/* Same, writing to out_path (NULL = stdout). */
+int gdh_debias_run(int argc, const char* const* argv, const char* out_path);
 
 /* ---- the slices of a .crai (indexcov/crai/crai.go:129-192 ReadIndex), pure CPU: what `indexcov` and `indexsplit` read
  * from a CRAM index before the device tiles it.  The file is gzip (any number of members) of lines of six tab-separated
