@@ -136,6 +136,12 @@ SYMBOLS = {
     "gd_chunk_debias": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, C.c_double, _P, _P, _P, C.POINTER(C.c_size_t), _P,
                                   C.c_size_t]),
     "gd_chunk_debias_timing": (C.c_int, [_P, _P, C.c_size_t]),
+    "gd_chunk_debias_cells": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, C.c_double, _P, _P, C.POINTER(C.c_size_t), _P,
+                                        C.c_size_t]),
+    "gd_device_scale": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P]),
+    "gd_sample_medians_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P]),
+    "gd_emdepth_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P, _P, _P]),
+    "gd_emcnv_add_device": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P]),
     "gd_ingest_finish": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_uint64)]),
     "gd_ingest_decode": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_uint64)]),
     "gd_ingest_decode_part": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_size_t, C.c_uint64, C.c_uint, C.c_double,

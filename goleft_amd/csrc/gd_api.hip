@@ -408,6 +408,7 @@ int gd_kernel_ms(gd_ctx* c, int id, float* ms)
 #include "gd_api_indexcov.inc"
 #include "gd_api_indexsplit.inc"
 #include "gd_api_crai.inc"
+#include "gd_api_devmat.inc"
 #include "gd_api_emdepth.inc"
 #include "gd_api_emcnv.inc"
 #include "gd_api_colselect.inc"

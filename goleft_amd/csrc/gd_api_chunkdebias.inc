@@ -1,7 +1,8 @@
 // gd_api_chunkdebias.inc -- dcnv's ChunkDebiaser per covariate chunk of a depth matrix (part of gd_api.hip, inside
 // extern "C"; DESIGN.md section 3.13).  The argsort of the covariate and the chunk walk (debiaser.go:140-148) are host work
-// inside the call; the medians and the division are gd_chunkdebias.hpp's kernels.  Nothing is kept between calls but the
-// timings.
+// inside the call; the medians and the division are gd_chunkdebias.hpp's kernels.  gd_chunk_debias_cells is the form for the
+// int64 cells gd_depthwed_device leaves: gd_devmat.hpp's conversion into the caller's device matrix, then the same two
+// kernels on it, the division in place (section 3.14).  Nothing is kept between calls but the timings.
 
 namespace {
 
@@ -21,26 +22,30 @@ struct CdBufs {
     }
 };
 
-}  // namespace
-
-int gd_chunk_debias(gd_ctx* c, const float* depths, size_t n_rows, int n_samples, const double* vals, double score_window,
-                    float* out, double* out64, uint32_t* chunk_of_row, size_t* n_chunks, float* med, size_t med_rows)
+// what both forms check before anything else, in gd_chunk_debias's order
+static int cd_check(gd_ctx* c, size_t n_rows, int n_samples, bool pointers, const double* vals, double score_window)
 {
-    if (!c) return GD_E_INVALID;
     if (n_samples < 1 || n_samples > gd::CD_MAX_N)
         return fail(c, GD_E_RANGE, "chunk debias: 1 .. %d samples, not %d", gd::CD_MAX_N, n_samples);
     if (n_rows < 1 || n_rows > 0x7fffffffull)
         return fail(c, GD_E_RANGE, "chunk debias: 1 .. 2^31 - 1 rows, not %zu", n_rows);
-    if (!depths || !vals || !out) return GD_E_INVALID;
+    if (!pointers || !vals) return GD_E_INVALID;
     if (!std::isfinite(score_window) || !(score_window > 0))
         return fail(c, GD_E_INVALID, "chunk debias: the score window must be a finite number > 0, not %g", score_window);
-    const size_t N = (size_t)n_samples;
     for (size_t r = 0; r < n_rows; ++r)
         if (!std::isfinite(vals[r])) return fail(c, GD_E_INVALID, "chunk debias: the value of row %zu is not finite", r);
-    for (size_t i = 0; i < n_rows * N; ++i)
-        if (!(depths[i] >= 0.0f) || !std::isfinite(depths[i]))
-            return fail(c, GD_E_INVALID, "chunk debias: the depth of row %zu, sample %zu is not a finite number >= 0", i / N, i % N);
+    return GD_OK;
+}
 
+// The host's share of a call (the chunking) and the device's, after the checks.  Host form (d_resident null): depths goes up
+// into a buffer of the call's own, the quotients into another and back to out / out64.  Resident form: d_resident is the
+// caller's device matrix; it gets (float)d_from first, the medians are taken on it, and the division runs on it in place
+// (every thread reads and writes its own index only); depths, out and out64 are null.
+static int cd_run(gd_ctx* c, const float* depths, const int64_t* d_from, float* d_resident, size_t n_rows, int n_samples,
+                  const double* vals, double score_window, float* out, double* out64, uint32_t* chunk_of_row, size_t* n_chunks,
+                  float* med, size_t med_rows)
+{
+    const size_t N = (size_t)n_samples;
     // Sort (debiaser.go:56-76) as an index, and the chunk walk of :140-148 over the sorted values.  A boundary needs a
     // difference above the window, so it never parts equal values: the order among them (here: by row) is immaterial.
     const double t0 = ing_now();
@@ -73,16 +78,17 @@ int gd_chunk_debias(gd_ctx* c, const float* depths, size_t n_rows, int n_samples
     c->cd_secs[5] = (double)largest;
 
     CdBufs b;
+    DmWord negative;
     const size_t cells = n_rows * N;
     const double t1 = ing_now();
-    HIPCHK(c, hipMalloc(&b.cells, cells * sizeof(float)));
+    if (!d_resident) HIPCHK(c, hipMalloc(&b.cells, cells * sizeof(float)));
     HIPCHK(c, hipMalloc(&b.order, n_rows * sizeof(uint32_t)));
     HIPCHK(c, hipMalloc(&b.slices, (C + 1) * sizeof(uint32_t)));
     HIPCHK(c, hipMalloc(&b.chunk_of_row, n_rows * sizeof(uint32_t)));
     HIPCHK(c, hipMalloc(&b.med, C * N * sizeof(uint32_t)));
-    HIPCHK(c, hipMalloc(&b.out, cells * sizeof(float)));
+    if (!d_resident) HIPCHK(c, hipMalloc(&b.out, cells * sizeof(float)));
     if (out64) HIPCHK(c, hipMalloc(&b.out64, cells * sizeof(double)));
-    HIPCHK(c, hipMemcpyAsync(b.cells, depths, cells * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (!d_resident) HIPCHK(c, hipMemcpyAsync(b.cells, depths, cells * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(b.order, order.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(b.slices, slices.data(), (C + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(b.chunk_of_row, cor.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
@@ -90,15 +96,24 @@ int gd_chunk_debias(gd_ctx* c, const float* depths, size_t n_rows, int n_samples
     c->cd_secs[1] = ing_now() - t1;
 
     gd::CdJob j{};
-    j.cells = static_cast<const uint32_t*>(b.cells); j.n_rows = (int64_t)n_rows; j.n = n_samples; j.n_chunks = (uint32_t)C;
+    j.cells = static_cast<const uint32_t*>(d_resident ? (void*)d_resident : b.cells);
+    j.n_rows = (int64_t)n_rows; j.n = n_samples; j.n_chunks = (uint32_t)C;
     j.order = static_cast<const uint32_t*>(b.order); j.slices = static_cast<const uint32_t*>(b.slices);
     j.chunk_of_row = static_cast<const uint32_t*>(b.chunk_of_row); j.med = static_cast<uint32_t*>(b.med);
-    j.out = static_cast<float*>(b.out); j.out64 = static_cast<double*>(b.out64);
+    j.out = d_resident ? d_resident : static_cast<float*>(b.out); j.out64 = static_cast<double*>(b.out64);
     const unsigned tiles = (unsigned)((N + gd::CD_COLS - 1) / gd::CD_COLS);
     const dim3 mgrid((unsigned)std::min<size_t>(C, (size_t)gd::CD_MAX_GRID), tiles), mwg(gd::CD_WG);
     const size_t turns = (n_rows + gd::CD_DIV_WAVES - 1) / gd::CD_DIV_WAVES;
     const dim3 dgrid((unsigned)std::min<size_t>(turns, (size_t)gd::CD_DIV_MAX_GRID), tiles), dwg(gd::CD_DIV_WAVES * 64);
     const double t2 = ing_now();
+    if (d_resident) {
+        // The conversion, and its verdict before anything else runs: a negative cell leaves the host outputs alone.
+        if (int r = dm_from_cells(c, d_from, d_resident, n_rows, n_samples, negative)) return r;
+        uint32_t flag = 0;
+        HIPCHK(c, hipMemcpyAsync(&flag, negative.p, sizeof flag, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (flag) return fail(c, GD_E_INVALID, "chunk debias: a cell of the device matrix is negative");
+    }
     hipLaunchKernelGGL(gd::gd_chunkdebias_median_kernel, mgrid, mwg, 0, c->stream, j);
     HIPCHK(c, hipGetLastError());
     if (getenv("GOLEFT_CHUNKDEBIAS_SPLIT")) {    // (measurement: the two kernels timed apart)
@@ -111,7 +126,7 @@ int gd_chunk_debias(gd_ctx* c, const float* depths, size_t n_rows, int n_samples
     c->cd_secs[2] = ing_now() - t2;
 
     const double t3 = ing_now();
-    HIPCHK(c, hipMemcpyAsync(out, b.out, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (out) HIPCHK(c, hipMemcpyAsync(out, b.out, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (out64) HIPCHK(c, hipMemcpyAsync(out64, b.out64, cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (med) HIPCHK(c, hipMemcpyAsync(med, b.med, C * N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -119,6 +134,34 @@ int gd_chunk_debias(gd_ctx* c, const float* depths, size_t n_rows, int n_samples
     if (chunk_of_row) memcpy(chunk_of_row, cor.data(), n_rows * sizeof(uint32_t));
     if (n_chunks) *n_chunks = C;
     return GD_OK;
+}
+
+}  // namespace
+
+int gd_chunk_debias(gd_ctx* c, const float* depths, size_t n_rows, int n_samples, const double* vals, double score_window,
+                    float* out, double* out64, uint32_t* chunk_of_row, size_t* n_chunks, float* med, size_t med_rows)
+{
+    if (!c) return GD_E_INVALID;
+    if (int r = cd_check(c, n_rows, n_samples, depths && out, vals, score_window)) return r;
+    const size_t N = (size_t)n_samples;
+    for (size_t i = 0; i < n_rows * N; ++i)
+        if (!(depths[i] >= 0.0f) || !std::isfinite(depths[i]))
+            return fail(c, GD_E_INVALID, "chunk debias: the depth of row %zu, sample %zu is not a finite number >= 0", i / N, i % N);
+    return cd_run(c, depths, nullptr, nullptr, n_rows, n_samples, vals, score_window, out, out64, chunk_of_row, n_chunks, med,
+                  med_rows);
+}
+
+int gd_chunk_debias_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, int n_samples, const double* vals,
+                          double score_window, float* d_out, uint32_t* chunk_of_row, size_t* n_chunks, float* med,
+                          size_t med_rows)
+{
+    if (!c) return GD_E_INVALID;
+    if (int r = cd_check(c, n_rows, n_samples, d_cells && d_out, vals, score_window)) return r;
+    const size_t cells = n_rows * (size_t)n_samples;
+    if (dm_overlap(d_cells, cells * sizeof(int64_t), d_out, cells * sizeof(float)))
+        return fail(c, GD_E_INVALID, "chunk debias: the quotients would overlap the cells they are made of");
+    return cd_run(c, nullptr, d_cells, d_out, n_rows, n_samples, vals, score_window, nullptr, nullptr, chunk_of_row, n_chunks,
+                  med, med_rows);
 }
 
 int gd_chunk_debias_timing(gd_ctx* c, double* out, size_t n)

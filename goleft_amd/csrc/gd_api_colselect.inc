@@ -132,6 +132,26 @@ int gd_sample_medians_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, in
     return GD_OK;
 }
 
+// gd_sample_medians for a float32 matrix that is in HBM already: gd_devmat.hpp's check in place of the host's, no upload
+int gd_sample_medians_device(gd_ctx* c, const float* d_depths, size_t n_rows, int n_samples, float* med, uint64_t* n_nonzero)
+{
+    if (!c) return GD_E_INVALID;
+    if (int r = cs_check(c, n_rows, n_samples)) return r;
+    if (!d_depths || !med) return GD_E_INVALID;
+    if (int r = set_device(c)) return r;
+    if (int r = dm_check(c, "sample medians", d_depths, n_rows, n_samples)) return r;
+    c->sm_secs[0] = c->sm_secs[1] = c->sm_secs[2] = 0;
+    c->sm_passes = 0;
+    CsBufs b;
+    std::vector<uint64_t> keys((size_t)n_samples);
+    if (int r = cs_run(c, false, d_depths, n_rows, n_samples, keys.data(), n_nonzero, b)) return r;
+    for (size_t s = 0; s < keys.size(); ++s) {
+        const uint32_t bits = (uint32_t)keys[s];
+        memcpy(&med[s], &bits, sizeof bits);
+    }
+    return GD_OK;
+}
+
 int gd_sample_medians_timing(gd_ctx* c, double* out, size_t n)
 {
     if (!c || !out) return GD_E_INVALID;

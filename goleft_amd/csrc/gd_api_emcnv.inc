@@ -264,6 +264,17 @@ int gd_emcnv_add_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, const f
     return ec_add(c, s, true, d_cells, scale ? s.scale : nullptr, n_rows, starts, ends, cn_out);
 }
 
+// gd_emcnv_add for float32 rows that are in HBM already: gd_devmat.hpp's check in place of the host's, no upload
+int gd_emcnv_add_device(gd_ctx* c, const float* d_depths, size_t n_rows, const uint32_t* starts, const uint32_t* ends,
+                        uint8_t* cn_out)
+{
+    EC_STATE(c);
+    if (int r = ec_check_add(c, s, n_rows, d_depths, starts, ends)) return r;
+    if (n_rows == 0) return GD_OK;
+    if (int r = dm_check(c, "emcnv", d_depths, n_rows, s.n)) return r;
+    return ec_add(c, s, false, d_depths, nullptr, n_rows, starts, ends, cn_out);
+}
+
 int gd_emcnv_finish(gd_ctx* c, uint64_t* n_cnvs, uint64_t* n_members)
 {
     EC_STATE(c);

@@ -128,6 +128,24 @@ int gd_emdepth_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, int n_sam
     return em_run(c, true, d_cells, b.scale, n_rows, n_samples, lambda, iters, cn, log2fc, b);
 }
 
+// gd_emdepth for a float32 matrix that is in HBM already: gd_devmat.hpp's check in place of the host's, no upload
+int gd_emdepth_device(gd_ctx* c, const float* d_depths, size_t n_rows, int n_samples, double* lambda, uint8_t* iters,
+                      uint8_t* cn, float* log2fc)
+{
+    if (!c) return GD_E_INVALID;
+    if (int r = em_check_n(c, n_samples)) return r;
+    if (n_rows == 0) return GD_OK;
+    if (!d_depths) return GD_E_INVALID;
+    const size_t N = (size_t)n_samples;
+    if (n_rows > (SIZE_MAX / sizeof(double)) / (N > gd::EM_CENTRES ? N : gd::EM_CENTRES))
+        return fail(c, GD_E_RANGE, "emdepth: %zu rows of %d samples do not fit an allocation", n_rows, n_samples);
+    if (int r = set_device(c)) return r;
+    if (int r = dm_check(c, "emdepth", d_depths, n_rows, n_samples)) return r;
+    c->em_secs[0] = c->em_secs[1] = c->em_secs[2] = 0;
+    EmBufs b;
+    return em_run(c, false, d_depths, nullptr, n_rows, n_samples, lambda, iters, cn, log2fc, b);
+}
+
 int gd_emdepth_timing(gd_ctx* c, double* out, size_t n)
 {
     if (!c || !out) return GD_E_INVALID;

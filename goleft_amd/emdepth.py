@@ -62,5 +62,54 @@ def scales(med, level=None):
     return out
 
 
+def _factors(med, nonzero, T):
+    """scales() with the two refusals of the command line's sample_scales, each naming the sample; T None: the level"""
+    for s, k in enumerate(np.asarray(nonzero).tolist()):
+        if k == 0:
+            raise ValueError("cohort_cnvs: sample %d has no depth above 0: it has no factor" % s)
+    if T is None:
+        return float(sorted(np.asarray(med).tolist())[len(med) // 2])
+    with np.errstate(over="ignore", divide="ignore"):
+        out = np.array([np.float32(float(T) / float(v)) for v in np.asarray(med).ravel()], np.float32)
+    for s, f in enumerate(out.tolist()):
+        if not np.isfinite(f):
+            raise ValueError("cohort_cnvs: sample %d: the factor %g / %g is not finite as a float32" % (s, T, float(med[s])))
+    return out
+
+
+def cohort_cnvs(eng, dptr, rows, n_samples, starts, ends, vals=None, window=0.01, level=None, block_rows=None,
+                site_cn=False):
+    """From DepthEngine.depthwed_device's int64 cells (dptr, rows) to CNV calls without the matrix leaving HBM: the
+    resident twin of `goleft-depth emdepth --normalize --cnvs` (vals None) and of `emdepth --gc-values --cnvs` (vals: the
+    covariate of every row, window: --gc-window).  level: --level; None is the middle sample median of the matrix as
+    read.  Returns (factors float32 [samples], level, what DepthEngine.emdepth_cnvs* returns); the per-site copy numbers
+    are read back only when site_cn is set, everything else that comes back is O(samples + calls).
+
+    With vals the order is the command line's (DESIGN.md sections 3.13, 3.14): the level from the cells, ChunkDebiaser
+    into a device float32 matrix of this call's own, the sample medians of the quotients, the factors
+    float32(level / med[s]), the quotients scaled in place, emdepth.Cache over them.  ValueError names a sample that has
+    no depth above 0 or whose factor is not finite as a float32; the engine's refusals come as GdError."""
+    if level is not None and not (float(level) > 0 and np.isfinite(float(level))):
+        raise ValueError("cohort_cnvs: the level must be a finite number > 0")
+    T = None if level is None else float(level)
+    if T is None or vals is None:
+        med, nz = eng.sample_medians_cells(dptr, rows, n_samples)
+        # (float)median: the rounding is monotone, so this is the median of the float32 matrix the command line reads
+        med = med.astype(np.float32)
+        if T is None:
+            T = _factors(med, nz, None)
+    if vals is None:
+        f = _factors(med, nz, T)
+        return f, T, eng.emdepth_cnvs_cells(dptr, rows, n_samples, starts, ends, scale=f, block_rows=block_rows, site_cn=site_cn)
+    out = eng.device_alloc(max(rows * n_samples * 4, 1))
+    try:
+        eng.chunk_debias_cells(dptr, rows, n_samples, vals, window, out)
+        f = _factors(*eng.sample_medians_device(out, rows, n_samples), T)
+        eng.scale_device(out, rows, n_samples, f)
+        return f, T, eng.emdepth_cnvs_device(out, rows, n_samples, starts, ends, block_rows=block_rows, site_cn=site_cn)
+    finally:
+        eng.device_free(out)
+
+
 if __name__ == "__main__":
     sys.exit(Main(sys.argv[1:]))

@@ -444,6 +444,66 @@ class DepthEngine:
                                                    en[r0:r1].ctypes.data, cn[r0:r1].ctypes.data if site_cn else None))
         return self._emcnv_result(cn)
 
+    # ---- the matrix stays in HBM: dptr / out_ptr are device addresses ----
+    def device_alloc(self, nbytes: int) -> int:
+        """Device memory of this engine's GPU (device_free gives it back)."""
+        p = C.c_void_p()
+        self._chk(self._lib.gd_device_alloc(self._ctx, nbytes, C.byref(p)))
+        return p.value
+
+    def device_free(self, ptr: int) -> None:
+        self._chk(self._lib.gd_device_free(self._ctx, C.c_void_p(ptr)))
+
+    def chunk_debias_cells(self, dptr: int, rows: int, n_samples: int, vals, window, out_ptr: int):
+        """chunk_debias for int64 cells in HBM (depthwed_device's pointer): the quotients of float32(cell) go to the device
+        float32 [rows][n_samples] matrix at out_ptr, which must not overlap the cells.  Returns (chunk_of_row uint32
+        [rows], med float32 [chunks, samples])."""
+        v = np.ascontiguousarray(vals, np.float64)
+        assert v.shape == (rows,)
+        cor, nc = np.empty(rows, np.uint32), C.c_size_t()
+        med = np.empty((rows, n_samples), np.float32)
+        self._chk(self._lib.gd_chunk_debias_cells(self._ctx, C.c_void_p(dptr), rows, n_samples,
+                                                  v.ctypes.data if v.size else None, float(window), C.c_void_p(out_ptr),
+                                                  cor.ctypes.data, C.byref(nc), med.ctypes.data, rows))
+        return cor, med[:nc.value].copy()
+
+    def scale_device(self, dptr: int, rows: int, n_samples: int, scale) -> None:
+        """In place on a device float32 [rows][n_samples] matrix: every cell times scale[sample] (finite, >= 0), in
+        float32."""
+        s = np.ascontiguousarray(scale, np.float32)
+        assert s.shape == (n_samples,)
+        self._chk(self._lib.gd_device_scale(self._ctx, C.c_void_p(dptr), rows, n_samples, s.ctypes.data))
+
+    def sample_medians_device(self, dptr: int, rows: int, n_samples: int):
+        """sample_medians for a device float32 [rows][n_samples] matrix, which a pass on the device holds to finite and
+        >= 0 first: (med float32 [samples], nonzero uint64 [samples])."""
+        med, nz = np.empty(n_samples, np.float32), np.empty(n_samples, np.uint64)
+        self._chk(self._lib.gd_sample_medians_device(self._ctx, C.c_void_p(dptr), rows, n_samples, med.ctypes.data,
+                                                     nz.ctypes.data))
+        return med, nz
+
+    def emdepth_device(self, dptr: int, rows: int, n_samples: int):
+        """emdepth for a device float32 [rows][n_samples] matrix (checked on the device first).  Returns what emdepth
+        returns."""
+        lam, it, cn, fc = self._emdepth_outputs(rows, n_samples)
+        self._chk(self._lib.gd_emdepth_device(self._ctx, C.c_void_p(dptr), rows, n_samples, lam.ctypes.data, it.ctypes.data,
+                                              cn.ctypes.data, fc.ctypes.data))
+        return lam, it, cn, fc
+
+    def emdepth_cnvs_device(self, dptr: int, rows: int, n_samples: int, starts, ends, block_rows=None, site_cn=False):
+        """emdepth_cnvs for a device float32 [rows][n_samples] matrix (each block checked on the device first); site_cn
+        and block_rows as in emdepth_cnvs_cells."""
+        st, en = self._emcnv_positions(starts, ends, rows)
+        cn = np.empty((rows, n_samples), np.uint8) if site_cn else None
+        self._chk(self._lib.gd_emcnv_begin(self._ctx, n_samples))
+        step = rows if not block_rows else int(block_rows)
+        for r0 in range(0, rows, max(step, 1)):
+            r1 = min(rows, r0 + step)
+            self._chk(self._lib.gd_emcnv_add_device(self._ctx, C.c_void_p(dptr + r0 * n_samples * 4), r1 - r0,
+                                                    st[r0:r1].ctypes.data, en[r0:r1].ctypes.data,
+                                                    cn[r0:r1].ctypes.data if site_cn else None))
+        return self._emcnv_result(cn)
+
     def emcnv_timing(self):
         """Seconds since the last gd_emcnv_begin: (upload, emdepth kernel, CNV kernels, read-back)."""
         t = (C.c_double * 4)()

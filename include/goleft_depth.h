@@ -39,7 +39,7 @@ extern "C" {
 
 /* GD_ABI_VERSION changes when an existing entry point or structure changes; GD_ABI_REVISION counts the releases that only
  * ADDED entry points since then (revision 1: gd_indexcov_*; 2: gd_indexsplit_*; 3: gd_crai_sizes).  A caller built against (15, r) runs on any (15, r' >= r).
- * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, gd_sample_medians* and gd_chunk_debias*, were added without a revision; look them up by symbol.
+ * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, gd_sample_medians*, gd_chunk_debias*, gd_device_scale and the *_device entries, were added without a revision; look them up by symbol.
  * Why indexcov did not become version 16: nothing that existed changed, so callers of ABI 15 need not be turned away, and
  * tests/test_host_cpu.py holds gd_abi_version() to 15 until something does change. */
 #define GD_ABI_VERSION 15
@@ -742,6 +742,39 @@ int gd_chunk_debias(gd_ctx* ctx, const float* depths, size_t n_rows, int n_sampl
                     uint32_t* chunk_of_row /* [n_rows] or NULL */, size_t* n_chunks /* or NULL */,
                     float* med /* [n_chunks][n_samples] or NULL; capacity med_rows */, size_t med_rows);
 int gd_chunk_debias_timing(gd_ctx* ctx, double* out, size_t n);
+/* ---- the matrix stays in HBM: debias, normalise and call CNVs on gd_depthwed_device's cells ----
+ * Every d_* argument is a DEVICE pointer (gd_device_alloc, or any allocation of the context's device); everything else is
+ * host memory.  Added without a revision; look them up by symbol.
+ *   gd_chunk_debias_cells     gd_chunk_debias for d_cells, DEVICE int64 [n_rows][n_samples] as gd_depthwed_device leaves
+ *                             them: d_out, a caller-owned DEVICE float32 matrix of the same shape, receives the quotients --
+ *                             bit for bit what gd_chunk_debias gives for (float)cell, one rounding to nearest even.  vals,
+ *                             the chunking, chunk_of_row, n_chunks, med, med_rows and every refusal are gd_chunk_debias's;
+ *                             besides: d_out overlapping d_cells is GD_E_INVALID before anything runs, and a negative cell
+ *                             (found by the pass that converts) is GD_E_INVALID with the host outputs untouched and d_out
+ *                             unspecified.  gd_chunk_debias_timing reports this call too: its upload is the three tables of
+ *                             the chunking, its kernels include the conversion, its read-back is med.
+ *   gd_device_scale           d_depths[r][s] = d_depths[r][s] * scale[s] in float32, in place: what `emdepth --scales` does
+ *                             to a cell.  scale: host [n_samples], each finite and >= 0 (GD_E_INVALID otherwise, nothing
+ *                             touched); n_samples 1 .. 4096 (GD_E_RANGE); n_rows == 0 is GD_OK.  The cells are not checked.
+ *   gd_sample_medians_device  gd_sample_medians,
+ *   gd_emdepth_device         gd_emdepth and
+ *   gd_emcnv_add_device       gd_emcnv_add for a DEVICE float32 matrix: no host validation, no upload.  A pass over the matrix
+ *                             first finds a cell that is not finite and >= 0 (-0.0 and denormals pass, as on the host):
+ *                             GD_E_INVALID, gd_last_error naming the row and sample of the first one, nothing written, the
+ *                             context and any gd_emcnv state as they were.  Then the same kernels on the same bits: every
+ *                             output is byte for byte the host twin's.  Ranges, n_rows == 0 and GD_E_STATE as for the twins.
+ *                             The matrix is only read. */
+int gd_chunk_debias_cells(gd_ctx* ctx, const int64_t* d_cells, size_t n_rows, int n_samples, const double* vals /* [n_rows] */,
+                          double score_window, float* d_out /* DEVICE [n_rows][n_samples] */,
+                          uint32_t* chunk_of_row /* [n_rows] or NULL */, size_t* n_chunks /* or NULL */,
+                          float* med /* [n_chunks][n_samples] or NULL; capacity med_rows */, size_t med_rows);
+int gd_device_scale(gd_ctx* ctx, float* d_depths, size_t n_rows, int n_samples, const float* scale /* [n_samples] */);
+int gd_sample_medians_device(gd_ctx* ctx, const float* d_depths, size_t n_rows, int n_samples, float* med /* [n_samples] */,
+                             uint64_t* n_nonzero /* [n_samples] or NULL */);
+int gd_emdepth_device(gd_ctx* ctx, const float* d_depths, size_t n_rows, int n_samples, double* lambda, uint8_t* iters,
+                      uint8_t* cn, float* log2fc);
+int gd_emcnv_add_device(gd_ctx* ctx, const float* d_depths, size_t n_rows, const uint32_t* starts, const uint32_t* ends,
+                        uint8_t* cn_out);
 int gd_ingest_abort(gd_ctx* ctx);
 /* Page-locked host memory for the byte range handed to gd_ingest_bgzf (read the file
  * straight into it: the H2D copy then runs at PCIe speed instead of through a bounce
