@@ -4,7 +4,7 @@
 // gd_create / gd_destroy, the setters (stream, parameters, path, outputs, contigs, selection), options, statistics and
 // timing.  The rest of the ABI is in the gd_api_*.inc files included at the end, in this order: records (pinned
 // staging ring + copy stream, records host -> HBM, HBM-resident per-contig record streams), compute (route, launch
-// sequencing, look-back), results (read-back), aux, ingest, covstats, indexcov, indexsplit, crai, emdepth, emcnv, colselect, chunkdebias, comm.
+// sequencing, look-back), results (read-back), aux, ingest, covstats, indexcov, indexsplit, crai, emdepth, emcnv, colselect, chunkdebias, movdebias, comm.
 // Replaces gargs' process.Runner + the samtools child + the callback's parse loop of `goleft depth`
 // (depth/depth.go:392-394, :45, :282-325).
 #include "../../include/goleft_depth.h"
@@ -332,6 +332,10 @@ int gd_set_option(gd_ctx* c, int option, int64_t value)
         if (value < 0 || value > 1) return fail(c, GD_E_INVALID, "inflate kernel: 0 (a lane per member) or 1 (a workgroup per member)");
         c->inflate_kernel = (int)value;
         break;
+    case GD_OPT_MOVDEBIAS_SEGMENT:
+        if (value < 0 || value > (1 << 30)) return fail(c, GD_E_INVALID, "moving debias segment: 0 (the default for the window) or 1 .. 2^30 sorted rows");
+        c->md_segment = value;
+        break;
     // retired (include/goleft_depth.h): the number is reserved and only the default is accepted
     case GD_OPT_INGEST_PIECE_STREAMS: case GD_OPT_INFLATE_LDS_PAD: case GD_OPT_INGEST_HYBRID: case GD_OPT_INGEST_BATCHES:
     case GD_OPT_INGEST_WALK_CUS:
@@ -363,6 +367,7 @@ int gd_get_option(gd_ctx* c, int option, int64_t* value)
     case GD_OPT_INGEST_CU_SPLIT: *value = c->ing_cu_split; break;
     case GD_OPT_INGEST_RANGE_HINT: *value = (int64_t)c->ing_range_hint; break;
     case GD_OPT_INFLATE_KERNEL: *value = c->inflate_kernel; break;
+    case GD_OPT_MOVDEBIAS_SEGMENT: *value = c->md_segment; break;
     case GD_OPT_INGEST_PIECE_STREAMS: case GD_OPT_INFLATE_LDS_PAD: case GD_OPT_INGEST_HYBRID: case GD_OPT_INGEST_BATCHES:
     case GD_OPT_INGEST_WALK_CUS: *value = retired_option_default(option); break;
     default: return fail(c, GD_E_INVALID, "unknown option %d", option);
@@ -413,6 +418,7 @@ int gd_kernel_ms(gd_ctx* c, int id, float* ms)
 #include "gd_api_emcnv.inc"
 #include "gd_api_colselect.inc"
 #include "gd_api_chunkdebias.inc"
+#include "gd_api_movdebias.inc"
 #include "gd_api_comm.inc"
 
 }  // extern "C"

@@ -266,6 +266,8 @@ struct gd_ctx {
     int sm_passes = 0;                                         // ... and the passes over the matrix it ran
     double cd_secs[7] = {0, 0, 0, 0, 0, 0, 0};                 // gd_chunk_debias: sort + chunking, upload, kernels, read-back of the last call; its chunks, its largest chunk;
                                                                // the median kernel alone when GOLEFT_CHUNKDEBIAS_SPLIT is set (gd_api_chunkdebias.inc)
+    double md_secs[4] = {0, 0, 0, 0};                          // gd_moving_debias*: sort, upload, kernel, read-back of the last call (gd_api_movdebias.inc)
+    int64_t md_segment = 0;                                    // GD_OPT_MOVDEBIAS_SEGMENT: sorted rows a workgroup owns (0: by the window)
     double em_secs[3] = {0, 0, 0};                             // gd_emdepth*: upload, kernel, read-back of the last call (gd_api_emdepth.inc)
     uint8_t* h_walk = nullptr; size_t cap_walk = 0;            // gd_ingest_decode, gd_covstats_decode: per-segment tables of the record walk (page-locked host memory
                                                                // the walk kernels read and write over the link: no copy command)

@@ -22,15 +22,16 @@
 // --level.  `emdepth --normalize` computes the same factors in-process and goes on as with --scales: the matrix is
 // uploaded once for the medians and again, scaled, in its blocks.
 //
-//   goleft-depth debias (--gc-values FILE | --fasta ref.fa) [--window W] matrix.bed[.gz]
-//   goleft-depth emdepth (--gc-values FILE | --gc-fasta ref.fa) [--gc-window W] [--level L] [--cnvs FILE] matrix.bed[.gz]
+//   goleft-depth debias (--gc-values FILE | --fasta ref.fa) [--window W | --moving ROWS] matrix.bed[.gz]
+//   goleft-depth emdepth (--gc-values FILE | --gc-fasta ref.fa) [--gc-window W | --gc-moving ROWS] [--level L] [--cnvs FILE] matrix.bed[.gz]
 //
 // `debias` reads the same matrix with the same reader and writes it back with every cell divided by the "median" of its
 // sample over the rows of similar covariate: dcnv's ChunkDebiaser (dcnv/debiaser/debiaser.go:125-171; gd_chunk_debias on
 // the device).  The covariate is one float64 per row -- from a file, one per line in row order, or
 // the GC fraction of [max(start, 250) - 250, end) of a FASTA (dcnv/dcnv.go:82-86; counted by gd_seq_stats_ex under the
 // active GDH_STATS_* contract).  --window (the reference's ScoreWindow) defaults to 0.01: this project's choice, the
-// reference gives none.  Cells go out as %.9g of the float32, which the reader takes back bit for bit.  `emdepth` with a GC
+// reference gives none.  With --moving ROWS the divisor is instead the moving median over ROWS rows in covariate order of
+// dcnv's GeneralDebiaser (debiaser.go:98-123, what dcnv's main runs with 9; gd_moving_debias, section 3.15).  Cells go out as %.9g of the float32, which the reader takes back bit for bit.  `emdepth` with a GC
 // flag debiases in-process and then normalises, in the reference's order (dcnv.go:331-337): the quotients are near 1 and
 // EMDepth stops on absolute thresholds, so they go back to depth scale -- the level is --level or the middle sample median
 // of the matrix AS READ, the factors T / med'[s] over the medians of the debiased matrix (this project's definition).
@@ -55,8 +56,9 @@ enum { CMD_EMDEPTH = 0, CMD_SCALES = 1, CMD_DEBIAS = 2 };
 
 struct EArgs {
     std::string scales, cnvs, input, gc_values, gc_fasta;
-    bool normalize = false, has_level = false, has_window = false;
+    bool normalize = false, has_level = false, has_window = false, has_moving = false;
     double level = 0, window = 0.01;
+    int moving = 0;                              // --moving / --gc-moving: the GeneralDebiaser's window, in rows
     bool gc() const { return !gc_values.empty() || !gc_fasta.empty(); }
 };
 
@@ -71,25 +73,27 @@ void usage_scales(FILE* f)
 
 void usage_debias(FILE* f)
 {
-    fputs("usage: debias (--gc-values FILE | --fasta REF.fa) [--window W] MATRIX\n"
+    fputs("usage: debias (--gc-values FILE | --fasta REF.fa) [--window W | --moving ROWS] MATRIX\n"
           "  MATRIX  a depthwed matrix (#chrom start end samples... and its rows), plain or gzipped\n"
           "  writes the matrix with every cell divided by its sample's median over the rows of similar covariate (dcnv's\n"
           "  ChunkDebiaser): the rows in covariate order are cut where a value exceeds the chunk's first by more than W\n"
           "  --gc-values  the covariate: one number per line, one line per row, in row order (GC content or any other)\n"
           "  --fasta  take the GC fraction of [max(start, 250) - 250, end) of REF.fa (needs REF.fa.fai) instead\n"
-          "  --window  W, a finite number > 0 (default 0.01)\n", f);
+          "  --window  W, a finite number > 0 (default 0.01)\n"
+          "  --moving  divide by a moving median over ROWS rows in covariate order instead (dcnv's GeneralDebiaser; dcnv runs\n"
+          "            it with 9): an odd number, 1 .. 255.  Not with --window\n", f);
 }
 
 void usage(FILE* f)
 {
-    fputs("usage: emdepth [--scales FILE | --normalize [--level L] | (--gc-values FILE | --gc-fasta REF.fa) [--gc-window W] [--level L]]\n"
+    fputs("usage: emdepth [--scales FILE | --normalize [--level L] | (--gc-values FILE | --gc-fasta REF.fa) [--gc-window W | --gc-moving ROWS] [--level L]]\n"
           "               [--cnvs FILE] MATRIX\n"
           "  MATRIX  a depthwed matrix (#chrom start end samples... and its rows), plain or gzipped, already normalised\n"
           "  --scales  a file of one factor per line, in column order: every depth is multiplied by its sample's factor\n"
           "  --normalize  compute those factors here, as `scales` does: each sample's 0.65 quantile of its non-zero depths\n"
           "               carried to the middle one of them (--level L: to L)\n"
-          "  --gc-values, --gc-fasta, --gc-window  first remove the bias of a per-row covariate as `debias` does (its\n"
-          "               --gc-values, --fasta, --window), then --normalize: to --level, or to the middle one of the\n"
+          "  --gc-values, --gc-fasta, --gc-window, --gc-moving  first remove the bias of a per-row covariate as `debias` does (its\n"
+          "               --gc-values, --fasta, --window, --moving), then --normalize: to --level, or to the middle one of the\n"
           "               sample quantiles of the matrix as read\n"
           "  --cnvs  write the CNV calls of every sample (emdepth.Cache) to FILE: sample, index, psize, sites, positions, cn, depth, log2fc\n", f);
 }
@@ -108,6 +112,7 @@ int parse_args(int argc, const char* const* argv, EArgs* a, int cmd)
     const auto usage = [cmd](FILE* f) { cmd == CMD_SCALES ? usage_scales(f) : cmd == CMD_DEBIAS ? usage_debias(f) : ::usage(f); };
     const char* const fasta_key = cmd == CMD_DEBIAS ? "--fasta" : "--gc-fasta";
     const char* const window_key = cmd == CMD_DEBIAS ? "--window" : "--gc-window";
+    const char* const moving_key = cmd == CMD_DEBIAS ? "--moving" : "--gc-moving";
     std::vector<std::string> pos;
     for (int i = 1; i < argc; ++i) {
         std::string arg = argv[i];
@@ -119,7 +124,7 @@ int parse_args(int argc, const char* const* argv, EArgs* a, int cmd)
             bool has_val = false;
             const size_t eq = arg.find('=');
             if (eq != std::string::npos) { key = arg.substr(0, eq); val = arg.substr(eq + 1); has_val = true; }
-            const bool gc_key = key == "--gc-values" || key == fasta_key || key == window_key;
+            const bool gc_key = key == "--gc-values" || key == fasta_key || key == window_key || key == moving_key;
             const bool known = cmd == CMD_SCALES ? key == "--level"
                              : cmd == CMD_DEBIAS ? gc_key
                                                  : key == "--level" || key == "--scales" || key == "--cnvs" || gc_key;
@@ -133,6 +138,18 @@ int parse_args(int argc, const char* const* argv, EArgs* a, int cmd)
                 val = argv[++i];
             }
             if (val.empty()) { fprintf(stderr, "error: empty value for %s\n", key.c_str()); usage(stderr); return -1; }
+            if (key == moving_key) {
+                char* end = nullptr;
+                const long v = strtol(val.c_str(), &end, 10);
+                if (end != val.c_str() + val.size() || v < 1 || v > 255 || v % 2 == 0) {
+                    fprintf(stderr, "error: %s must be an odd number of rows, 1 .. 255, not '%s'\n", key.c_str(), val.c_str());
+                    usage(stderr);
+                    return -1;
+                }
+                a->moving = (int)v;
+                a->has_moving = true;
+                continue;
+            }
             if (key == "--level" || key == window_key) {
                 const bool level = key == "--level";
                 if (!parse_positive(val, level ? &a->level : &a->window)) {
@@ -172,6 +189,16 @@ int parse_args(int argc, const char* const* argv, EArgs* a, int cmd)
         fprintf(stderr, "error: %s is the window of the debiasing: it needs --gc-values or %s\n", window_key, fasta_key);
         usage(stderr);
         return -1;
+    }
+    if (a->has_moving && !a->gc()) {
+        fprintf(stderr, "error: %s is the window of the debiasing: it needs --gc-values or %s\n", moving_key, fasta_key);
+        usage(stderr);
+        return -1;
+    }
+    if (a->has_moving && a->has_window) {
+        fprintf(stderr, "error: %s and %s choose the debiaser: give one of them\n", window_key, moving_key);
+        usage(stderr);
+        return -2;                               // (exit code 1: the two flags are each valid)
     }
     if (a->gc() && cmd == CMD_EMDEPTH) a->normalize = true;
     if (a->has_level && !a->normalize && cmd == CMD_EMDEPTH) {
@@ -614,10 +641,16 @@ int debias_matrix(const char* prog, gd_ctx* ctx, const EArgs& a, Matrix* m, std:
         return rc;
     }
     std::vector<float> out(rows * N);
-    const int rc = gd_chunk_debias(ctx, m->depths.data(), rows, (int)N, vals->data(), a.window, out.data(), nullptr, nullptr,
-                                   nullptr, nullptr, 0);
-    if (rc != GD_OK) { fprintf(stderr, "%s: gd_chunk_debias: %s (%s)\n", prog, gd_strerror(rc), gd_last_error(ctx)); return 1; }
-    (void)gd_chunk_debias_timing(ctx, secs, 7);
+    if (a.has_moving) {                          // dcnv's GeneralDebiaser; secs: its four values
+        const int rc = gd_moving_debias(ctx, m->depths.data(), rows, (int)N, vals->data(), a.moving, out.data(), nullptr);
+        if (rc != GD_OK) { fprintf(stderr, "%s: gd_moving_debias: %s (%s)\n", prog, gd_strerror(rc), gd_last_error(ctx)); return 1; }
+        (void)gd_moving_debias_timing(ctx, secs, 4);
+    } else {
+        const int rc = gd_chunk_debias(ctx, m->depths.data(), rows, (int)N, vals->data(), a.window, out.data(), nullptr, nullptr,
+                                       nullptr, nullptr, 0);
+        if (rc != GD_OK) { fprintf(stderr, "%s: gd_chunk_debias: %s (%s)\n", prog, gd_strerror(rc), gd_last_error(ctx)); return 1; }
+        (void)gd_chunk_debias_timing(ctx, secs, 7);
+    }
     for (size_t i = 0; i < rows * N; ++i)
         if (!std::isfinite(out[i])) {
             fprintf(stderr, "%s: row %zu, sample %zu: the debiased depth is not finite as a float32\n", prog, i / N + 1, i % N + 1);
@@ -797,7 +830,7 @@ extern "C" int gdh_emdepth_run(int argc, const char* const* argv, const char* ou
     EArgs a;
     const int p = parse_args(argc, argv, &a, CMD_EMDEPTH);
     if (p > 0) return 0;
-    if (p < 0) return 255;
+    if (p < 0) return p == -2 ? 1 : 255;
     FILE* out = stdout;
     if (out_path) {
         out = fopen(out_path, "w");
@@ -833,7 +866,7 @@ extern "C" int gdh_debias_run(int argc, const char* const* argv, const char* out
     EArgs a;
     const int p = parse_args(argc, argv, &a, CMD_DEBIAS);
     if (p > 0) return 0;
-    if (p < 0) return 255;
+    if (p < 0) return p == -2 ? 1 : 255;
     FILE* out = stdout;
     if (out_path) {
         out = fopen(out_path, "w");

@@ -1,6 +1,6 @@
 """`emdepth`, `scales` and `debias` entry points: copy numbers per site of a depthwed matrix, goleft's emdepth.EMDepth run
-on the device, the per-sample factors that normalise such a matrix first, and dcnv's ChunkDebiaser, which frees it of GC
-bias before that (the matrix reading, the blocks of rows, the output
+on the device, the per-sample factors that normalise such a matrix first, and dcnv's ChunkDebiaser or GeneralDebiaser,
+which free it of GC bias before that (the matrix reading, the blocks of rows, the output
 rows and the exit codes live in the C++ host twin)."""
 from __future__ import annotations
 
@@ -21,7 +21,7 @@ def Main(argv, out_path=None) -> int:
     """argv: the arguments after the program name, e.g. ["--scales", "scales.txt", "matrix.bed.gz"] or
     ["--normalize", "--level", "30", "--cnvs", "cnvs.tsv", "matrix.bed"] or ["--gc-values", "gc.txt", "matrix.bed"]: a
     depthwed matrix (`#chrom start end samples...` and its rows), plain or gzipped, already normalised unless --normalize
-    or a GC flag (--gc-values FILE | --gc-fasta REF.fa, [--gc-window W]: debias as Debias does, then normalise) is given.
+    or a GC flag (--gc-values FILE | --gc-fasta REF.fa, [--gc-window W | --gc-moving ROWS]: debias as Debias does, then normalise) is given.
     The rows go to out_path (stdout when None); returns the exit code."""
     lib = _hostlib.load()
     n, arr = _argv(b"emdepth", argv)
@@ -39,7 +39,8 @@ def Scales(argv, out_path=None) -> int:
 def Debias(argv, out_path=None) -> int:
     """`goleft-depth debias`: argv e.g. ["--gc-values", "gc.txt", "--window", "0.02", "matrix.bed.gz"] or ["--fasta",
     "ref.fa", "matrix.bed"].  The matrix with every cell divided by its sample's median over the rows of similar covariate
-    (dcnv's ChunkDebiaser) goes to out_path (stdout when None); returns the exit code."""
+    (dcnv's ChunkDebiaser; with ["--moving", "9"] in place of --window by the moving median of dcnv's GeneralDebiaser) goes
+    to out_path (stdout when None); returns the exit code."""
     lib = _hostlib.load()
     n, arr = _argv(b"debias", argv)
     return int(lib.gdh_debias_run(n, arr, out_path.encode() if out_path else None))
@@ -77,11 +78,12 @@ def _factors(med, nonzero, T):
     return out
 
 
-def cohort_cnvs(eng, dptr, rows, n_samples, starts, ends, vals=None, window=0.01, level=None, block_rows=None,
-                site_cn=False):
+def cohort_cnvs(eng, dptr, rows, n_samples, starts, ends, vals=None, window=None, level=None, block_rows=None,
+                site_cn=False, moving=None):
     """From DepthEngine.depthwed_device's int64 cells (dptr, rows) to CNV calls without the matrix leaving HBM: the
     resident twin of `goleft-depth emdepth --normalize --cnvs` (vals None) and of `emdepth --gc-values --cnvs` (vals: the
-    covariate of every row, window: --gc-window).  level: --level; None is the middle sample median of the matrix as
+    covariate of every row, window: --gc-window, 0.01 when None; or moving: --gc-moving, the odd window of dcnv's
+    GeneralDebiaser in place of the ChunkDebiaser -- giving both is a ValueError).  level: --level; None is the middle sample median of the matrix as
     read.  Returns (factors float32 [samples], level, what DepthEngine.emdepth_cnvs* returns); the per-site copy numbers
     are read back only when site_cn is set, everything else that comes back is O(samples + calls).
 
@@ -91,6 +93,10 @@ def cohort_cnvs(eng, dptr, rows, n_samples, starts, ends, vals=None, window=0.01
     no depth above 0 or whose factor is not finite as a float32; the engine's refusals come as GdError."""
     if level is not None and not (float(level) > 0 and np.isfinite(float(level))):
         raise ValueError("cohort_cnvs: the level must be a finite number > 0")
+    if moving is not None and window is not None:
+        raise ValueError("cohort_cnvs: window (the ChunkDebiaser) and moving (the GeneralDebiaser) exclude each other")
+    if moving is not None and vals is None:
+        raise ValueError("cohort_cnvs: moving needs the covariate of every row")
     T = None if level is None else float(level)
     if T is None or vals is None:
         med, nz = eng.sample_medians_cells(dptr, rows, n_samples)
@@ -103,7 +109,10 @@ def cohort_cnvs(eng, dptr, rows, n_samples, starts, ends, vals=None, window=0.01
         return f, T, eng.emdepth_cnvs_cells(dptr, rows, n_samples, starts, ends, scale=f, block_rows=block_rows, site_cn=site_cn)
     out = eng.device_alloc(max(rows * n_samples * 4, 1))
     try:
-        eng.chunk_debias_cells(dptr, rows, n_samples, vals, window, out)
+        if moving is not None:
+            eng.moving_debias_cells(dptr, rows, n_samples, vals, moving, out)
+        else:
+            eng.chunk_debias_cells(dptr, rows, n_samples, vals, 0.01 if window is None else window, out)
         f = _factors(*eng.sample_medians_device(out, rows, n_samples), T)
         eng.scale_device(out, rows, n_samples, f)
         return f, T, eng.emdepth_cnvs_device(out, rows, n_samples, starts, ends, block_rows=block_rows, site_cn=site_cn)

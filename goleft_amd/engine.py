@@ -387,6 +387,30 @@ class DepthEngine:
         self._chk(self._lib.gd_chunk_debias_timing(self._ctx, t, 7))
         return t[0], t[1], t[2], t[3], int(t[4]), int(t[5]), t[6]
 
+    def moving_debias(self, depths, vals, window, want_med=False):
+        """dcnv's GeneralDebiaser on a [rows][samples] float32 matrix (finite, >= 0; 1 .. 4096 samples): the rows are taken
+        in ascending order of vals (float64 [rows], finite; ties by row) and every sample's cell is divided, in float64, by
+        max(median, 1) of the reference's moving window of `window` rows (odd, 1 .. 255; at least (window - 1) / 2 + 1
+        rows).  Returns out float32 [rows, samples]; with want_med (out, med float64 [rows, samples]: the medians before
+        the max)."""
+        d = np.ascontiguousarray(depths, np.float32)
+        v = np.ascontiguousarray(vals, np.float64)
+        assert d.ndim == 2 and v.ndim == 1
+        rows, n = d.shape
+        assert v.shape == (rows,)
+        out = np.empty((rows, n), np.float32)
+        med = np.empty((rows, n), np.float64) if want_med else None
+        self._chk(self._lib.gd_moving_debias(self._ctx, d.ctypes.data if d.size else None, rows, n,
+                                             v.ctypes.data if v.size else None, int(window), out.ctypes.data,
+                                             med.ctypes.data if want_med else None))
+        return (out, med) if want_med else out
+
+    def moving_debias_timing(self):
+        """Of the last moving_debias call: (host sort, upload, kernels, read-back) seconds."""
+        t = (C.c_double * 4)()
+        self._chk(self._lib.gd_moving_debias_timing(self._ctx, t, 4))
+        return t[0], t[1], t[2], t[3]
+
     def _emcnv_positions(self, starts, ends, rows: int):
         st, en = np.ascontiguousarray(starts, np.uint32), np.ascontiguousarray(ends, np.uint32)
         assert st.shape == (rows,) and en.shape == (rows,)
@@ -466,6 +490,14 @@ class DepthEngine:
                                                   v.ctypes.data if v.size else None, float(window), C.c_void_p(out_ptr),
                                                   cor.ctypes.data, C.byref(nc), med.ctypes.data, rows))
         return cor, med[:nc.value].copy()
+
+    def moving_debias_cells(self, dptr: int, rows: int, n_samples: int, vals, window, out_ptr: int) -> None:
+        """moving_debias for int64 cells in HBM (depthwed_device's pointer): the quotients of float32(cell) go to the
+        device float32 [rows][n_samples] matrix at out_ptr, which must not overlap the cells."""
+        v = np.ascontiguousarray(vals, np.float64)
+        assert v.shape == (rows,)
+        self._chk(self._lib.gd_moving_debias_cells(self._ctx, C.c_void_p(dptr), rows, n_samples,
+                                                   v.ctypes.data if v.size else None, int(window), C.c_void_p(out_ptr)))
 
     def scale_device(self, dptr: int, rows: int, n_samples: int, scale) -> None:
         """In place on a device float32 [rows][n_samples] matrix: every cell times scale[sample] (finite, >= 0), in

@@ -39,7 +39,7 @@ extern "C" {
 
 /* GD_ABI_VERSION changes when an existing entry point or structure changes; GD_ABI_REVISION counts the releases that only
  * ADDED entry points since then (revision 1: gd_indexcov_*; 2: gd_indexsplit_*; 3: gd_crai_sizes).  A caller built against (15, r) runs on any (15, r' >= r).
- * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, gd_sample_medians*, gd_chunk_debias*, gd_device_scale and the *_device entries, were added without a revision; look them up by symbol.
+ * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, gd_sample_medians*, gd_chunk_debias*, gd_device_scale, the *_device entries and gd_moving_debias*, were added without a revision; look them up by symbol.
  * Why indexcov did not become version 16: nothing that existed changed, so callers of ABI 15 need not be turned away, and
  * tests/test_host_cpu.py holds gd_abi_version() to 15 until something does change. */
 #define GD_ABI_VERSION 15
@@ -234,6 +234,8 @@ enum { GD_OPT_NT_STORES = 3,        /* 1 (default): non-temporal per-base stores
                                        from the next gd_compute, which refuses to run on records that failed (the context
                                        needs a gd_reset then).  For producers that are short of CPU -- a decoder's threads --
                                        and do not need the verdict block by block; gdh_produce_in_place runs this way */
+       GD_OPT_MOVDEBIAS_SEGMENT = 26, /* gd_moving_debias*: sorted rows a workgroup owns: 0 (default) 256 for a window up to 63, 1024
+                                       above; 1 .. 2^30.  A test knob: the results do not depend on it */
 
        /* ---- RETIRED ----
         * Switches of link and occupancy experiments that were measured neutral or worse on an MI355X; their code is gone
@@ -775,6 +777,30 @@ int gd_emdepth_device(gd_ctx* ctx, const float* d_depths, size_t n_rows, int n_s
                       uint8_t* cn, float* log2fc);
 int gd_emcnv_add_device(gd_ctx* ctx, const float* d_depths, size_t n_rows, const uint32_t* starts, const uint32_t* ends,
                         uint8_t* cn_out);
+/* ---- moving-median debias: dcnv's GeneralDebiaser, the debiaser dcnv's main runs with Window = 9 ----
+ * Added without a revision; look them up by symbol.  The rows are taken in ascending order of vals, tied vals by row index
+ * (the reference's argsort is unstable there).  For every sample, with c[0 .. R) its column in that order, W = window (odd,
+ * 1 .. 255) and mid = (W - 1) / 2 + 1, the reference pushes P[t] = c[t] (t < mid), c[t + mid] (t >= mid) -- rows
+ * mid .. 2 mid - 1 never enter a window -- and divides row i by the median of P[lo .. hi): hi = mid for i < mid, else
+ * min(i + 1, max(mid, R - mid)); lo = max(0, hi - W).  The median of a full window is its (W + 1) / 2-th smallest value; of
+ * m < W values it is (sorted[(m - 1) / 2] + sorted[m / 2]) / 2 in float64 (this library's definition: the reference's
+ * moving-median library is not part of it).  out[row][s] = (float)((double)c[i] / max(median, 1.0)), at the row's original
+ * place; med (or NULL) gets the medians themselves, before the max (-0.0 counts as 0.0 there).  n_samples is 1 .. 4096;
+ * window even or outside 1 .. 255, n_rows < mid (the reference indexes past the column) or > 2^31 - 1: GD_E_RANGE; a depth
+ * that is not finite and >= 0, a val that is not finite: GD_E_INVALID.  All refusals happen before anything runs and leave
+ * the context usable.  The argsort is host work inside the call; nothing is kept between calls.
+ *   gd_moving_debias_cells    the same for d_cells, DEVICE int64 [n_rows][n_samples] as gd_depthwed_device leaves them:
+ *                             d_out, a caller-owned DEVICE float32 matrix of the same shape, receives what gd_moving_debias
+ *                             gives for (float)cell, bit for bit.  d_out overlapping d_cells is GD_E_INVALID before anything
+ *                             runs; a negative cell (found by the pass that converts) is GD_E_INVALID with d_out untouched.
+ *                             The call holds a float32 copy of the matrix of its own while it runs.
+ *   gd_moving_debias_timing   (measurement only) of the last call: seconds of host sort, upload, kernels (the conversion
+ *                             included), read-back.  Fills min(n, 4) values. */
+int gd_moving_debias(gd_ctx* ctx, const float* depths, size_t n_rows, int n_samples, const double* vals /* [n_rows] */,
+                     int window, float* out /* [n_rows][n_samples] */, double* med /* same shape or NULL */);
+int gd_moving_debias_cells(gd_ctx* ctx, const int64_t* d_cells, size_t n_rows, int n_samples, const double* vals /* [n_rows] */,
+                           int window, float* d_out /* DEVICE [n_rows][n_samples] */);
+int gd_moving_debias_timing(gd_ctx* ctx, double* out, size_t n);
 int gd_ingest_abort(gd_ctx* ctx);
 /* Page-locked host memory for the byte range handed to gd_ingest_bgzf (read the file
  * straight into it: the H2D copy then runs at PCIe speed instead of through a bounce

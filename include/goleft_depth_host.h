@@ -217,20 +217,23 @@ int gdh_scales_main(int argc, const char* const* argv);
 /* Same, writing to out_path (NULL = stdout). */
 int gdh_scales_run(int argc, const char* const* argv, const char* out_path);
 
-/* ---- `debias` and `emdepth --gc-values FILE | --gc-fasta REF.fa [--gc-window W] [--level L]`: dcnv's ChunkDebiaser
+/* ---- `debias` and `emdepth --gc-values FILE | --gc-fasta REF.fa [--gc-window W | --gc-moving ROWS] [--level L]`: dcnv's ChunkDebiaser
  * (dcnv/debiaser/debiaser.go:125-171; gd_chunk_debias on the device) on a depthwed matrix.  argv: (--gc-values FILE |
- * --fasta REF.fa) [--window W] matrix.bed[.gz], the matrix read and checked exactly as `emdepth` reads it.  The covariate is
+ * --fasta REF.fa) [--window W | --moving ROWS] matrix.bed[.gz], the matrix read and checked exactly as `emdepth` reads it.  The covariate is
  * one float64 per row: --gc-values, one number per line and one line per row in row order (a count or parse error names the
  * line), or --fasta, the GC fraction of [max(start, 250) - 250, end) as dcnv/dcnv.go:82-86 takes it -- n_gc over the
  * denominator of the active GDH_STATS_* contract, 0 for an empty one; each chromosome is loaded once, in order of first
  * appearance; one missing from the .fai is an error that names it; faidx.Stats is external, so parity is unpinned as for
  * --stats; stderr then gets every row's `chrom start end` and its value as %.17g.  The printed start is not altered.
- * --window (ScoreWindow) is finite and > 0 and defaults to 0.01, this project's choice (the reference gives none).  stdout:
+ * --window (ScoreWindow) is finite and > 0 and defaults to 0.01, this project's choice (the reference gives none).  With
+ * --moving ROWS (`emdepth`: --gc-moving ROWS; odd, 1 .. 255, a usage error otherwise) the debiaser is dcnv's GeneralDebiaser
+ * instead (debiaser.go:98-123, what dcnv's main runs with 9; gd_moving_debias on the device): every cell over max(1, the moving
+ * median of its sample over ROWS rows in covariate order); giving it together with --window is refused with exit code 1.  stdout:
  * the header, and per row chrom, start, end as read and %.9g of every float32 quotient, which the reader takes back bit for
  * bit; a quotient that is not finite as a float32 is an error that names row and sample.  `emdepth` with a GC flag debiases
  * in-process and then normalises as --normalize does (the flags imply it; --scales with them is a usage error): to --level,
  * or to the middle sample quantile of the matrix AS READ; its output is that of `debias ... | emdepth --normalize --level L`
- * byte for byte.  With GOLEFT_EMDEPTH_TIMING both print the split of gd_chunk_debias and the chunk count.  Returns the exit
+ * byte for byte.  With GOLEFT_EMDEPTH_TIMING both print the split of gd_chunk_debias (gd_moving_debias) and the chunk count.  Returns the exit
  * code (1 on an error, with no row written; 255 on a usage error). ------------------------------------------------------ */
 int gdh_debias_main(int argc, const char* const* argv);
 /* Same, writing to out_path (NULL = stdout). */
