@@ -4,11 +4,13 @@
 // gd_create / gd_destroy, the setters (stream, parameters, path, outputs, contigs, selection), options, statistics and
 // timing.  The rest of the ABI is in the gd_api_*.inc files included at the end, in this order: records (pinned
 // staging ring + copy stream, records host -> HBM, HBM-resident per-contig record streams), compute (route, launch
-// sequencing, look-back), results (read-back), aux, ingest, covstats, indexcov, indexsplit, crai, emdepth, emcnv, colselect, chunkdebias, movdebias, comm.
+// sequencing, look-back), results (read-back), aux, ingest, covstats, indexcov, indexsplit, crai, devmat, emdepth, emcnv,
+// colselect, chunkdebias, movdebias, comm.
 // Replaces gargs' process.Runner + the samtools child + the callback's parse loop of `goleft depth`
 // (depth/depth.go:392-394, :45, :282-325).
 #include "../../include/goleft_depth.h"
 #include "gd_kernels.hpp"
+#include "gd_matcheck.hpp"
 
 #include <algorithm>
 #include <atomic>

@@ -116,9 +116,9 @@ int gd_seq_stats_ex(gd_ctx* c, size_t n_windows, const int64_t* start, const int
     if (n_windows > 0x7fffffffull * 4) return fail(c, GD_E_RANGE, "too many windows");
     // one scratch allocation: starts, ends (int64), then the five count arrays (uint32)
     const size_t bytes = n_windows * (2 * sizeof(int64_t) + 5 * sizeof(uint32_t));
-    uint8_t* d = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), bytes));
-    int64_t* d_s = reinterpret_cast<int64_t*>(d);
+    DevBuf d;
+    if (int r = d.alloc(c, bytes)) return r;
+    int64_t* d_s = d.as<int64_t>();
     int64_t* d_e = d_s + n_windows;
     uint32_t* d_c = reinterpret_cast<uint32_t*>(d_e + n_windows);
     gd::SeqStatsJob j{};
@@ -129,26 +129,21 @@ int gd_seq_stats_ex(gd_ctx* c, size_t n_windows, const int64_t* start, const int
     j.masked_acgt = n_masked_acgt ? d_c + 4 * n_windows : nullptr;
     j.n_win = (int64_t)n_windows;
     j.line_bases = (uint32_t)line_bases;
-    hipError_t e1 = hipMemcpyAsync(d_s, start, n_windows * sizeof(int64_t), hipMemcpyHostToDevice, c->stream);
-    hipError_t e2 = hipMemcpyAsync(d_e, end, n_windows * sizeof(int64_t), hipMemcpyHostToDevice, c->stream);
+    HIPCHK(c, hipMemcpyAsync(d_s, start, n_windows * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_e, end, n_windows * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     if (c->profiling) (void)hipEventRecord(c->ev[0], c->stream);
     hipLaunchKernelGGL(gd::gd_seq_stats_kernel, dim3((unsigned)((n_windows + 3) / 4)), dim3(256), 0, c->stream, j);
     if (c->profiling) (void)hipEventRecord(c->ev[1], c->stream);
-    hipError_t e3 = hipMemcpyAsync(n_gc, j.gc, n_windows * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-    hipError_t e4 = hipMemcpyAsync(n_cpg, j.cpg, n_windows * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-    hipError_t e5 = hipMemcpyAsync(n_masked, j.masked, n_windows * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-    hipError_t e7 = hipSuccess, e8 = hipSuccess;
-    if (n_acgt) e7 = hipMemcpyAsync(n_acgt, j.acgt, n_windows * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-    if (n_masked_acgt) e8 = hipMemcpyAsync(n_masked_acgt, j.masked_acgt, n_windows * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-    hipError_t e6 = hipStreamSynchronize(c->stream);
-    if (c->profiling && e6 == hipSuccess) {
+    HIPCHK(c, hipMemcpyAsync(n_gc, j.gc, n_windows * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(n_cpg, j.cpg, n_windows * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(n_masked, j.masked, n_windows * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (n_acgt) HIPCHK(c, hipMemcpyAsync(n_acgt, j.acgt, n_windows * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (n_masked_acgt) HIPCHK(c, hipMemcpyAsync(n_masked_acgt, j.masked_acgt, n_windows * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->profiling) {
         float ms = 0;
         if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) c->kernel_ms[GD_K_SEQSTATS] = ms;
     }
-    (void)hipFree(d);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess ||
-        e6 != hipSuccess || e7 != hipSuccess || e8 != hipSuccess)
-        return fail(c, GD_E_HIP, "sequence statistics kernel failed");
     return GD_OK;
 }
 
@@ -192,25 +187,22 @@ int gd_md_flags(gd_ctx* c, int n_samples, const int32_t* tids, int32_t min_cov, 
     c->md_len = -1;
     if (need == 0) { c->md_len = 0; c->md_tids.assign(tids, tids + n_samples); return GD_OK; }
     if (int r = ensure_dev(c, &c->d_md_bits, &c->cap_md, 2 * need)) return r;
-    const int32_t** d_ptrs = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d_ptrs), ptrs.size() * sizeof(ptrs[0])));
+    DevBuf d_ptrs;
+    if (int r = d_ptrs.alloc(c, ptrs.size() * sizeof(ptrs[0]))) return r;
     gd::MdFlagsJob j{};
-    j.depth = d_ptrs; j.n_samples = n_samples; j.len = len; j.min_cov = min_cov; j.min_samples = min_samples;
+    j.depth = d_ptrs.as<const int32_t*>(); j.n_samples = n_samples; j.len = len; j.min_cov = min_cov; j.min_samples = min_samples;
     j.any_bits = c->d_md_bits; j.suf_bits = c->d_md_bits + need;
-    hipError_t e1 = hipMemcpyAsync(d_ptrs, ptrs.data(), ptrs.size() * sizeof(ptrs[0]), hipMemcpyHostToDevice, c->stream);
+    HIPCHK(c, hipMemcpyAsync(d_ptrs.p, ptrs.data(), ptrs.size() * sizeof(ptrs[0]), hipMemcpyHostToDevice, c->stream));
     if (c->profiling) (void)hipEventRecord(c->ev[0], c->stream);
     hipLaunchKernelGGL(gd::gd_md_flags_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, j);
     if (c->profiling) (void)hipEventRecord(c->ev[1], c->stream);
-    hipError_t e2 = hipMemcpyAsync(any_bits, j.any_bits, need * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-    hipError_t e3 = hipMemcpyAsync(suf_bits, j.suf_bits, need * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-    hipError_t e4 = hipStreamSynchronize(c->stream);
-    if (c->profiling && e4 == hipSuccess) {
+    HIPCHK(c, hipMemcpyAsync(any_bits, j.any_bits, need * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(suf_bits, j.suf_bits, need * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->profiling) {
         float ms = 0;
         if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) c->kernel_ms[GD_K_MDFLAGS] = ms;
     }
-    (void)hipFree(d_ptrs);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess)
-        return fail(c, GD_E_HIP, "multidepth flag kernel failed");
     c->md_len = len;
     c->md_tids.assign(tids, tids + n_samples);
     return GD_OK;
@@ -247,16 +239,14 @@ int gd_md_accumulate(gd_ctx* c, int n_samples, const int32_t* tids, int32_t min_
     if (c->md_acc_samples + (int64_t)n_samples > 65535) return fail(c, GD_E_RANGE, "more than 65535 samples");
     c->md_acc_samples += n_samples;
     if (len == 0) return GD_OK;
-    const int32_t** d_ptrs = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d_ptrs), ptrs.size() * sizeof(ptrs[0])));
+    DevBuf d_ptrs;
+    if (int r = d_ptrs.alloc(c, ptrs.size() * sizeof(ptrs[0]))) return r;
     gd::MdAccJob j{};
-    j.depth = d_ptrs; j.n_samples = n_samples; j.len = len; j.min_cov = min_cov;
+    j.depth = d_ptrs.as<const int32_t*>(); j.n_samples = n_samples; j.len = len; j.min_cov = min_cov;
     j.cnt = c->d_md_cnt; j.any_bits = c->d_md_bits;
-    hipError_t e1 = hipMemcpyAsync(d_ptrs, ptrs.data(), ptrs.size() * sizeof(ptrs[0]), hipMemcpyHostToDevice, c->stream);
+    HIPCHK(c, hipMemcpyAsync(d_ptrs.p, ptrs.data(), ptrs.size() * sizeof(ptrs[0]), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(gd::gd_md_acc_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, j);
-    hipError_t e2 = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_ptrs);
-    if (e1 != hipSuccess || e2 != hipSuccess) return fail(c, GD_E_HIP, "multidepth accumulate kernel failed");
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return GD_OK;
 }
 
@@ -311,25 +301,21 @@ int gd_md_blocks(gd_ctx* c, int64_t chunk, int32_t max_skip, int32_t min_size, i
     // every chunk's stream is walked by one thread (the reference uses 5 Mb / 1 Mb chunks: at most ~2 000 per contig)
     if (n_chunks > (1 << 20)) return fail(c, GD_E_RANGE, "%lld chunks of %lld positions (at most 2^20)", (long long)n_chunks, (long long)chunk);
     // scratch: everything but the run / pair / block arrays, whose sizes are only known after the scans
-    struct Scratch {
-        std::vector<void*> p;
-        ~Scratch() { for (void* q : p) if (q) (void)hipFree(q); }
-        hipError_t get(void** out, size_t bytes) { hipError_t e = hipMalloc(out, bytes ? bytes : 1); if (e == hipSuccess) p.push_back(*out); return e; }
-    } sc;
+    DevList sc;
     gd::MdBlkJob j{};
     j.any_bits = c->d_md_bits; j.suf_bits = c->d_md_bits + nw;
     j.len = len; j.nw = nw; j.chunk = chunk; j.max_skip = max_skip; j.min_size = min_size; j.window = window;
     j.n_chunks = n_chunks;
-    HIPCHK(c, sc.get(reinterpret_cast<void**>(&j.rs), (size_t)nw * 4));
-    HIPCHK(c, sc.get(reinterpret_cast<void**>(&j.re), (size_t)nw * 4));
-    HIPCHK(c, sc.get(reinterpret_cast<void**>(&j.ps), ((size_t)nw + 1) * 4));
-    HIPCHK(c, sc.get(reinterpret_cast<void**>(&j.prs), ((size_t)nw + 1) * 4));
-    HIPCHK(c, sc.get(reinterpret_cast<void**>(&j.pre), ((size_t)nw + 1) * 4));
-    HIPCHK(c, sc.get(reinterpret_cast<void**>(&j.z0), (size_t)n_chunks * 8));
-    HIPCHK(c, sc.get(reinterpret_cast<void**>(&j.E), (size_t)n_chunks * 8));
-    HIPCHK(c, sc.get(reinterpret_cast<void**>(&j.pa), (size_t)n_chunks * 8));
-    HIPCHK(c, sc.get(reinterpret_cast<void**>(&j.k_lo), (size_t)n_chunks * 4));
-    HIPCHK(c, sc.get(reinterpret_cast<void**>(&j.pair_off), ((size_t)n_chunks + 1) * 4));
+    if (int r = sc.alloc(c, &j.rs, (size_t)nw)) return r;
+    if (int r = sc.alloc(c, &j.re, (size_t)nw)) return r;
+    if (int r = sc.alloc(c, &j.ps, (size_t)nw + 1)) return r;
+    if (int r = sc.alloc(c, &j.prs, (size_t)nw + 1)) return r;
+    if (int r = sc.alloc(c, &j.pre, (size_t)nw + 1)) return r;
+    if (int r = sc.alloc(c, &j.z0, (size_t)n_chunks)) return r;
+    if (int r = sc.alloc(c, &j.E, (size_t)n_chunks)) return r;
+    if (int r = sc.alloc(c, &j.pa, (size_t)n_chunks)) return r;
+    if (int r = sc.alloc(c, &j.k_lo, (size_t)n_chunks)) return r;
+    if (int r = sc.alloc(c, &j.pair_off, (size_t)n_chunks + 1)) return r;
     const unsigned wgrid = (unsigned)((nw + 255) / 256);
     hipLaunchKernelGGL(gd::gd_md_runs_kernel, dim3(wgrid), dim3(256), 0, c->stream, j);
     if (int r = launch_scan(c, j.ps, (uint32_t)nw)) return r;
@@ -340,8 +326,8 @@ int gd_md_blocks(gd_ctx* c, int64_t chunk, int32_t max_skip, int32_t min_size, i
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (n_runs == 0) return GD_OK;
-    HIPCHK(c, sc.get(reinterpret_cast<void**>(&j.starts), (size_t)n_runs * 4));
-    HIPCHK(c, sc.get(reinterpret_cast<void**>(&j.ends), (size_t)n_runs * 4));
+    if (int r = sc.alloc(c, &j.starts, (size_t)n_runs)) return r;
+    if (int r = sc.alloc(c, &j.ends, (size_t)n_runs)) return r;
     hipLaunchKernelGGL(gd::gd_md_compact_kernel, dim3(wgrid), dim3(256), 0, c->stream, j);
     hipLaunchKernelGGL(gd::gd_md_chunks_kernel, dim3(1), dim3(256), 0, c->stream, j);
     uint32_t n_pairs = 0;
@@ -349,7 +335,7 @@ int gd_md_blocks(gd_ctx* c, int64_t chunk, int32_t max_skip, int32_t min_size, i
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (n_pairs == 0) return GD_OK;
-    HIPCHK(c, sc.get(reinterpret_cast<void**>(&j.nblk), ((size_t)n_pairs + 1) * 4));
+    if (int r = sc.alloc(c, &j.nblk, (size_t)n_pairs + 1)) return r;
     HIPCHK(c, hipMemsetAsync(j.nblk + n_pairs, 0, 4, c->stream));
     const unsigned pgrid = (unsigned)((n_pairs + 255u) / 256u);
     hipLaunchKernelGGL(gd::gd_md_count_kernel, dim3(pgrid), dim3(256), 0, c->stream, j, n_pairs);
@@ -361,8 +347,8 @@ int gd_md_blocks(gd_ctx* c, int64_t chunk, int32_t max_skip, int32_t min_size, i
     *n_blocks = nb;
     if (nb == 0) return GD_OK;
     if ((size_t)nb > cap || !starts || !ends) return fail(c, GD_E_CAPACITY, "%u blocks, room for %zu", nb, cap);
-    HIPCHK(c, sc.get(reinterpret_cast<void**>(&j.bstart), (size_t)nb * 8));
-    HIPCHK(c, sc.get(reinterpret_cast<void**>(&j.bend), (size_t)nb * 8));
+    if (int r = sc.alloc(c, &j.bstart, (size_t)nb)) return r;
+    if (int r = sc.alloc(c, &j.bend, (size_t)nb)) return r;
     hipLaunchKernelGGL(gd::gd_md_blocks_kernel, dim3(pgrid), dim3(256), 0, c->stream, j, n_pairs);
     HIPCHK(c, hipMemcpyAsync(starts, j.bstart, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(ends, j.bend, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
@@ -404,23 +390,20 @@ static int md_sums_impl(gd_ctx* c, int n_samples, const int32_t* tids, size_t n_
             return fail(c, GD_E_RANGE, "block %zu [%lld, %lld) outside the contig", b, (long long)start[b], (long long)end[b]);
     const size_t n_cells = n_blocks * (size_t)n_samples;
     const size_t bytes = ptrs.size() * sizeof(ptrs[0]) + 2 * n_blocks * sizeof(int64_t) + n_cells * sizeof(double);
-    uint8_t* d = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), bytes));
-    const int32_t** d_ptrs = reinterpret_cast<const int32_t**>(d);
-    int64_t* d_s = reinterpret_cast<int64_t*>(d + ptrs.size() * sizeof(ptrs[0]));
+    DevBuf d;
+    if (int r = d.alloc(c, bytes)) return r;
+    const int32_t** d_ptrs = d.as<const int32_t*>();
+    int64_t* d_s = reinterpret_cast<int64_t*>(d.as<uint8_t>() + ptrs.size() * sizeof(ptrs[0]));
     int64_t* d_e = d_s + n_blocks;
     double* d_sums = reinterpret_cast<double*>(d_e + n_blocks);
     gd::MdSumsJob j{};
     j.depth = d_ptrs; j.suf_bits = c->d_md_bits + (size_t)((len + 31) / 32);
     j.start = d_s; j.end = d_e; j.sums = d_sums; j.n_blocks = (int64_t)n_blocks; j.n_samples = n_samples;
-    hipError_t e1 = hipMemcpyAsync(d_ptrs, ptrs.data(), ptrs.size() * sizeof(ptrs[0]), hipMemcpyHostToDevice, c->stream);
-    hipError_t e2 = hipMemcpyAsync(d_s, start, n_blocks * sizeof(int64_t), hipMemcpyHostToDevice, c->stream);
-    hipError_t e3 = hipMemcpyAsync(d_e, end, n_blocks * sizeof(int64_t), hipMemcpyHostToDevice, c->stream);
+    HIPCHK(c, hipMemcpyAsync(d_ptrs, ptrs.data(), ptrs.size() * sizeof(ptrs[0]), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_s, start, n_blocks * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_e, end, n_blocks * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(gd::gd_md_sums_kernel, dim3((unsigned)((n_cells + 63) / 64)), dim3(64), 0, c->stream, j);
-    hipError_t e4 = hipMemcpyAsync(sums, d_sums, n_cells * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    hipError_t e5 = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess)
-        return fail(c, GD_E_HIP, "multidepth block-sum kernel failed");
+    HIPCHK(c, hipMemcpyAsync(sums, d_sums, n_cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return GD_OK;
 }

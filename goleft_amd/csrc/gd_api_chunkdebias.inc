@@ -1,26 +1,10 @@
 // gd_api_chunkdebias.inc -- dcnv's ChunkDebiaser per covariate chunk of a depth matrix (part of gd_api.hip, inside
 // extern "C"; DESIGN.md section 3.13).  The argsort of the covariate and the chunk walk (debiaser.go:140-148) are host work
-// inside the call; the medians and the division are gd_chunkdebias.hpp's kernels.  gd_chunk_debias_cells is the form for the
+// inside the call (gd_matcheck.hpp); the medians and the division are gd_chunkdebias.hpp's kernels.  gd_chunk_debias_cells is the form for the
 // int64 cells gd_depthwed_device leaves: gd_devmat.hpp's conversion into the caller's device matrix, then the same two
 // kernels on it, the division in place (section 3.14).  Nothing is kept between calls but the timings.
 
 namespace {
-
-// the device buffers of one call, freed when it returns
-struct CdBufs {
-    void* cells = nullptr;
-    void* order = nullptr;
-    void* slices = nullptr;
-    void* chunk_of_row = nullptr;
-    void* med = nullptr;
-    void* out = nullptr;
-    void* out64 = nullptr;
-    ~CdBufs()
-    {
-        for (void* p : {cells, order, slices, chunk_of_row, med, out, out64})
-            if (p) (void)hipFree(p);
-    }
-};
 
 // what both forms check before anything else, in gd_chunk_debias's order
 static int cd_check(gd_ctx* c, size_t n_rows, int n_samples, bool pointers, const double* vals, double score_window)
@@ -46,27 +30,11 @@ static int cd_run(gd_ctx* c, const float* depths, const int64_t* d_from, float* 
                   float* med, size_t med_rows)
 {
     const size_t N = (size_t)n_samples;
-    // Sort (debiaser.go:56-76) as an index, and the chunk walk of :140-148 over the sorted values.  A boundary needs a
-    // difference above the window, so it never parts equal values: the order among them (here: by row) is immaterial.
+    // the order of the rows and the chunks over it (gd_matcheck.hpp)
     const double t0 = ing_now();
-    std::vector<uint32_t> order(n_rows), slices, cor(n_rows);
-    for (size_t r = 0; r < n_rows; ++r) order[r] = (uint32_t)r;
-    std::sort(order.begin(), order.end(), [vals](uint32_t a, uint32_t b) { return vals[a] < vals[b] || (vals[a] == vals[b] && a < b); });
-    slices.push_back(0);
-    double v0 = vals[order[0]];
-    size_t largest = 0;
-    for (size_t i = 0; i < n_rows; ++i) {
-        const double v = vals[order[i]];
-        if (v - v0 > score_window) {
-            v0 = v;
-            largest = std::max(largest, i - (size_t)slices.back());
-            slices.push_back((uint32_t)i);
-        }
-        cor[order[i]] = (uint32_t)(slices.size() - 1);
-    }
-    largest = std::max(largest, n_rows - (size_t)slices.back());
-    slices.push_back((uint32_t)n_rows);
-    const size_t C = slices.size() - 1;
+    const std::vector<uint32_t> order = gdm::argsort(vals, n_rows);
+    const gdm::Chunks ch = gdm::chunk_walk(vals, order, score_window);
+    const size_t C = ch.count();
     if (med && med_rows < C) {
         if (n_chunks) *n_chunks = C;             // (what the medians need)
         return fail(c, GD_E_CAPACITY, "chunk debias: %zu chunks, the medians have room for %zu", C, med_rows);
@@ -75,32 +43,31 @@ static int cd_run(gd_ctx* c, const float* depths, const int64_t* d_from, float* 
     for (double& s : c->cd_secs) s = 0;
     c->cd_secs[0] = ing_now() - t0;
     c->cd_secs[4] = (double)C;
-    c->cd_secs[5] = (double)largest;
+    c->cd_secs[5] = (double)ch.largest;
 
-    CdBufs b;
-    DmWord negative;
+    DevBuf d_cells, d_order, d_slices, d_cor, d_med, d_out, d_out64, negative;
     const size_t cells = n_rows * N;
     const double t1 = ing_now();
-    if (!d_resident) HIPCHK(c, hipMalloc(&b.cells, cells * sizeof(float)));
-    HIPCHK(c, hipMalloc(&b.order, n_rows * sizeof(uint32_t)));
-    HIPCHK(c, hipMalloc(&b.slices, (C + 1) * sizeof(uint32_t)));
-    HIPCHK(c, hipMalloc(&b.chunk_of_row, n_rows * sizeof(uint32_t)));
-    HIPCHK(c, hipMalloc(&b.med, C * N * sizeof(uint32_t)));
-    if (!d_resident) HIPCHK(c, hipMalloc(&b.out, cells * sizeof(float)));
-    if (out64) HIPCHK(c, hipMalloc(&b.out64, cells * sizeof(double)));
-    if (!d_resident) HIPCHK(c, hipMemcpyAsync(b.cells, depths, cells * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b.order, order.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b.slices, slices.data(), (C + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b.chunk_of_row, cor.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (!d_resident) if (int r = d_cells.alloc(c, cells * sizeof(float))) return r;
+    if (int r = d_order.alloc(c, n_rows * sizeof(uint32_t))) return r;
+    if (int r = d_slices.alloc(c, (C + 1) * sizeof(uint32_t))) return r;
+    if (int r = d_cor.alloc(c, n_rows * sizeof(uint32_t))) return r;
+    if (int r = d_med.alloc(c, C * N * sizeof(uint32_t))) return r;
+    if (!d_resident) if (int r = d_out.alloc(c, cells * sizeof(float))) return r;
+    if (out64) if (int r = d_out64.alloc(c, cells * sizeof(double))) return r;
+    if (!d_resident) HIPCHK(c, hipMemcpyAsync(d_cells.p, depths, cells * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_order.p, order.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_slices.p, ch.slices.data(), (C + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_cor.p, ch.chunk_of_row.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cd_secs[1] = ing_now() - t1;
 
     gd::CdJob j{};
-    j.cells = static_cast<const uint32_t*>(d_resident ? (void*)d_resident : b.cells);
+    j.cells = static_cast<const uint32_t*>(d_resident ? (void*)d_resident : d_cells.p);
     j.n_rows = (int64_t)n_rows; j.n = n_samples; j.n_chunks = (uint32_t)C;
-    j.order = static_cast<const uint32_t*>(b.order); j.slices = static_cast<const uint32_t*>(b.slices);
-    j.chunk_of_row = static_cast<const uint32_t*>(b.chunk_of_row); j.med = static_cast<uint32_t*>(b.med);
-    j.out = d_resident ? d_resident : static_cast<float*>(b.out); j.out64 = static_cast<double*>(b.out64);
+    j.order = d_order.as<const uint32_t>(); j.slices = d_slices.as<const uint32_t>();
+    j.chunk_of_row = d_cor.as<const uint32_t>(); j.med = d_med.as<uint32_t>();
+    j.out = d_resident ? d_resident : d_out.as<float>(); j.out64 = d_out64.as<double>();
     const unsigned tiles = (unsigned)((N + gd::CD_COLS - 1) / gd::CD_COLS);
     const dim3 mgrid((unsigned)std::min<size_t>(C, (size_t)gd::CD_MAX_GRID), tiles), mwg(gd::CD_WG);
     const size_t turns = (n_rows + gd::CD_DIV_WAVES - 1) / gd::CD_DIV_WAVES;
@@ -109,10 +76,7 @@ static int cd_run(gd_ctx* c, const float* depths, const int64_t* d_from, float* 
     if (d_resident) {
         // The conversion, and its verdict before anything else runs: a negative cell leaves the host outputs alone.
         if (int r = dm_from_cells(c, d_from, d_resident, n_rows, n_samples, negative)) return r;
-        uint32_t flag = 0;
-        HIPCHK(c, hipMemcpyAsync(&flag, negative.p, sizeof flag, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (flag) return fail(c, GD_E_INVALID, "chunk debias: a cell of the device matrix is negative");
+        if (int r = dm_refuse_negative(c, "chunk debias", negative)) return r;
     }
     hipLaunchKernelGGL(gd::gd_chunkdebias_median_kernel, mgrid, mwg, 0, c->stream, j);
     HIPCHK(c, hipGetLastError());
@@ -126,12 +90,12 @@ static int cd_run(gd_ctx* c, const float* depths, const int64_t* d_from, float* 
     c->cd_secs[2] = ing_now() - t2;
 
     const double t3 = ing_now();
-    if (out) HIPCHK(c, hipMemcpyAsync(out, b.out, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (out64) HIPCHK(c, hipMemcpyAsync(out64, b.out64, cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (med) HIPCHK(c, hipMemcpyAsync(med, b.med, C * N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (out) HIPCHK(c, hipMemcpyAsync(out, d_out.p, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (out64) HIPCHK(c, hipMemcpyAsync(out64, d_out64.p, cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (med) HIPCHK(c, hipMemcpyAsync(med, d_med.p, C * N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cd_secs[3] = ing_now() - t3;
-    if (chunk_of_row) memcpy(chunk_of_row, cor.data(), n_rows * sizeof(uint32_t));
+    if (chunk_of_row) memcpy(chunk_of_row, ch.chunk_of_row.data(), n_rows * sizeof(uint32_t));
     if (n_chunks) *n_chunks = C;
     return GD_OK;
 }
@@ -143,10 +107,7 @@ int gd_chunk_debias(gd_ctx* c, const float* depths, size_t n_rows, int n_samples
 {
     if (!c) return GD_E_INVALID;
     if (int r = cd_check(c, n_rows, n_samples, depths && out, vals, score_window)) return r;
-    const size_t N = (size_t)n_samples;
-    for (size_t i = 0; i < n_rows * N; ++i)
-        if (!(depths[i] >= 0.0f) || !std::isfinite(depths[i]))
-            return fail(c, GD_E_INVALID, "chunk debias: the depth of row %zu, sample %zu is not a finite number >= 0", i / N, i % N);
+    if (int r = mat_check(c, "chunk debias", depths, n_rows, n_samples)) return r;
     return cd_run(c, depths, nullptr, nullptr, n_rows, n_samples, vals, score_window, out, out64, chunk_of_row, n_chunks, med,
                   med_rows);
 }
@@ -158,7 +119,7 @@ int gd_chunk_debias_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, int 
     if (!c) return GD_E_INVALID;
     if (int r = cd_check(c, n_rows, n_samples, d_cells && d_out, vals, score_window)) return r;
     const size_t cells = n_rows * (size_t)n_samples;
-    if (dm_overlap(d_cells, cells * sizeof(int64_t), d_out, cells * sizeof(float)))
+    if (gdm::overlap(d_cells, cells * sizeof(int64_t), d_out, cells * sizeof(float)))
         return fail(c, GD_E_INVALID, "chunk debias: the quotients would overlap the cells they are made of");
     return cd_run(c, nullptr, d_cells, d_out, n_rows, n_samples, vals, score_window, nullptr, nullptr, chunk_of_row, n_chunks,
                   med, med_rows);

@@ -4,23 +4,6 @@
 
 namespace {
 
-// the device buffers of one call, freed when it returns
-struct CsBufs {
-    void* in = nullptr;
-    uint32_t* counts = nullptr;
-    uint32_t* zeros = nullptr;
-    uint64_t* prefix = nullptr;
-    int32_t* rem = nullptr;
-    uint32_t* rank = nullptr;
-    uint64_t* nonzero = nullptr;
-    uint32_t* flags = nullptr;
-    ~CsBufs()
-    {
-        for (void* p : {in, (void*)counts, (void*)zeros, (void*)prefix, (void*)rem, (void*)rank, (void*)nonzero, (void*)flags})
-            if (p) (void)hipFree(p);
-    }
-};
-
 static int cs_check(gd_ctx* c, size_t n_rows, int n_samples)
 {
     if (n_samples < 1 || n_samples > gd::CS_MAX_N)
@@ -33,24 +16,25 @@ static int cs_check(gd_ctx* c, size_t n_rows, int n_samples)
 // d_in: the matrix on the device (float32 when !cells, int64 otherwise).  prefix_out: host [n_samples], the answers as
 // keys (a float's bits or the cell); nonzero_out: host [n_samples] or nullptr.
 static int cs_run(gd_ctx* c, bool cells, const void* d_in, size_t n_rows, int n_samples, uint64_t* prefix_out,
-                  uint64_t* nonzero_out, CsBufs& b)
+                  uint64_t* nonzero_out)
 {
     const size_t N = (size_t)n_samples;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.counts), N * gd::CS_BINS * sizeof(uint32_t)));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.zeros), N * sizeof(uint32_t)));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.prefix), N * sizeof(uint64_t)));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.rem), N * sizeof(int32_t)));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.rank), N * sizeof(uint32_t)));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.nonzero), N * sizeof(uint64_t)));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.flags), 2 * sizeof(uint32_t)));
+    DevBuf counts, zeros, prefix, rem, rank, nonzero, flags;
+    if (int r = counts.alloc(c, N * gd::CS_BINS * sizeof(uint32_t))) return r;
+    if (int r = zeros.alloc(c, N * sizeof(uint32_t))) return r;
+    if (int r = prefix.alloc(c, N * sizeof(uint64_t))) return r;
+    if (int r = rem.alloc(c, N * sizeof(int32_t))) return r;
+    if (int r = rank.alloc(c, N * sizeof(uint32_t))) return r;
+    if (int r = nonzero.alloc(c, N * sizeof(uint64_t))) return r;
+    if (int r = flags.alloc(c, 2 * sizeof(uint32_t))) return r;
     const double t0 = ing_now();
-    HIPCHK(c, hipMemsetAsync(b.counts, 0, N * gd::CS_BINS * sizeof(uint32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(b.zeros, 0, N * sizeof(uint32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(b.flags, 0, 2 * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(counts.p, 0, N * gd::CS_BINS * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(zeros.p, 0, N * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(flags.p, 0, 2 * sizeof(uint32_t), c->stream));
     gd::CsJob j{};
     j.cells = d_in; j.n_rows = (int64_t)n_rows; j.n = n_samples;
-    j.counts = b.counts; j.zeros = b.zeros; j.prefix = b.prefix; j.rem = b.rem; j.rank = b.rank; j.nonzero = b.nonzero;
-    j.flags = b.flags;
+    j.counts = counts.as<uint32_t>(); j.zeros = zeros.as<uint32_t>(); j.prefix = prefix.as<uint64_t>(); j.rem = rem.as<int32_t>();
+    j.rank = rank.as<uint32_t>(); j.nonzero = nonzero.as<uint64_t>(); j.flags = flags.as<uint32_t>();
     // the column tiles share CS_MAX_GRID workgroups; each strides over the slabs of rows
     const unsigned tiles = (unsigned)((N + gd::CS_COLS - 1) / gd::CS_COLS);
     const size_t slabs = (n_rows + gd::CS_SLAB - 1) / gd::CS_SLAB;
@@ -62,11 +46,11 @@ static int cs_run(gd_ctx* c, bool cells, const void* d_in, size_t n_rows, int n_
         hipLaunchKernelGGL((gd::gd_colselect_hist_kernel<int64_t, true>), grid, wg, 0, c->stream, j);
         hipLaunchKernelGGL((gd::gd_colselect_pick_kernel<gd::CS_PICK_LENGTH>), pgrid, pwg, 0, c->stream, j);
         HIPCHK(c, hipGetLastError());
-        uint32_t flags[2] = {0, 0};
-        HIPCHK(c, hipMemcpyAsync(flags, b.flags, sizeof flags, hipMemcpyDeviceToHost, c->stream));
+        uint32_t seen[2] = {0, 0};
+        HIPCHK(c, hipMemcpyAsync(seen, flags.p, sizeof seen, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (flags[1]) return fail(c, GD_E_INVALID, "sample medians: a cell of the device matrix is negative");
-        passes = (int)flags[0];                  // the longest answer, in bytes
+        if (seen[1]) return fail(c, GD_E_INVALID, "sample medians: a cell of the device matrix is negative");
+        passes = (int)seen[0];                  // the longest answer, in bytes
     } else {
         hipLaunchKernelGGL((gd::gd_colselect_hist_kernel<float, true>), grid, wg, 0, c->stream, j);
         hipLaunchKernelGGL((gd::gd_colselect_pick_kernel<gd::CS_PICK_FLOAT_FIRST>), pgrid, pwg, 0, c->stream, j);
@@ -81,8 +65,8 @@ static int cs_run(gd_ctx* c, bool cells, const void* d_in, size_t n_rows, int n_
     c->sm_secs[1] = ing_now() - t0;
     c->sm_passes = 1 + passes;
     const double t1 = ing_now();
-    HIPCHK(c, hipMemcpyAsync(prefix_out, b.prefix, N * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (nonzero_out) HIPCHK(c, hipMemcpyAsync(nonzero_out, b.nonzero, N * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(prefix_out, prefix.p, N * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (nonzero_out) HIPCHK(c, hipMemcpyAsync(nonzero_out, nonzero.p, N * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->sm_secs[2] = ing_now() - t1;
     return GD_OK;
@@ -95,25 +79,20 @@ int gd_sample_medians(gd_ctx* c, const float* depths, size_t n_rows, int n_sampl
     if (!c) return GD_E_INVALID;
     if (int r = cs_check(c, n_rows, n_samples)) return r;
     if (!depths || !med) return GD_E_INVALID;
-    const size_t N = (size_t)n_samples;
-    for (size_t i = 0; i < n_rows * N; ++i)
-        if (!(depths[i] >= 0.0f) || !std::isfinite(depths[i]))
-            return fail(c, GD_E_INVALID, "sample medians: the depth of row %zu, sample %zu is not a finite number >= 0", i / N, i % N);
+    if (int r = mat_check(c, "sample medians", depths, n_rows, n_samples)) return r;
     if (int r = set_device(c)) return r;
     c->sm_secs[0] = c->sm_secs[1] = c->sm_secs[2] = 0;
     c->sm_passes = 0;
-    CsBufs b;
+    const size_t bytes = n_rows * (size_t)n_samples * sizeof(float);
+    DevBuf in;
     const double t0 = ing_now();
-    HIPCHK(c, hipMalloc(&b.in, n_rows * N * sizeof(float)));
-    HIPCHK(c, hipMemcpyAsync(b.in, depths, n_rows * N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (int r = in.alloc(c, bytes)) return r;
+    HIPCHK(c, hipMemcpyAsync(in.p, depths, bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->sm_secs[0] = ing_now() - t0;
-    std::vector<uint64_t> keys(N);
-    if (int r = cs_run(c, false, b.in, n_rows, n_samples, keys.data(), n_nonzero, b)) return r;
-    for (size_t s = 0; s < N; ++s) {
-        const uint32_t bits = (uint32_t)keys[s];
-        memcpy(&med[s], &bits, sizeof bits);
-    }
+    std::vector<uint64_t> keys((size_t)n_samples);
+    if (int r = cs_run(c, false, in.p, n_rows, n_samples, keys.data(), n_nonzero)) return r;
+    mat_keys_to_float(keys, med);
     return GD_OK;
 }
 
@@ -125,9 +104,8 @@ int gd_sample_medians_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, in
     if (int r = set_device(c)) return r;
     c->sm_secs[0] = c->sm_secs[1] = c->sm_secs[2] = 0;
     c->sm_passes = 0;
-    CsBufs b;
     std::vector<uint64_t> keys((size_t)n_samples);
-    if (int r = cs_run(c, true, d_cells, n_rows, n_samples, keys.data(), n_nonzero, b)) return r;
+    if (int r = cs_run(c, true, d_cells, n_rows, n_samples, keys.data(), n_nonzero)) return r;
     for (size_t s = 0; s < keys.size(); ++s) med[s] = (int64_t)keys[s];
     return GD_OK;
 }
@@ -142,13 +120,9 @@ int gd_sample_medians_device(gd_ctx* c, const float* d_depths, size_t n_rows, in
     if (int r = dm_check(c, "sample medians", d_depths, n_rows, n_samples)) return r;
     c->sm_secs[0] = c->sm_secs[1] = c->sm_secs[2] = 0;
     c->sm_passes = 0;
-    CsBufs b;
     std::vector<uint64_t> keys((size_t)n_samples);
-    if (int r = cs_run(c, false, d_depths, n_rows, n_samples, keys.data(), n_nonzero, b)) return r;
-    for (size_t s = 0; s < keys.size(); ++s) {
-        const uint32_t bits = (uint32_t)keys[s];
-        memcpy(&med[s], &bits, sizeof bits);
-    }
+    if (int r = cs_run(c, false, d_depths, n_rows, n_samples, keys.data(), n_nonzero)) return r;
+    mat_keys_to_float(keys, med);
     return GD_OK;
 }
 

@@ -3,16 +3,6 @@
 
 namespace {
 
-struct CraiBufs {
-    int64_t *seq_off = nullptr, *start = nullptr, *span = nullptr, *tile_off = nullptr, *sizes = nullptr;
-    int32_t *len = nullptr, *status = nullptr;
-    ~CraiBufs()
-    {
-        void* all[] = {seq_off, start, span, tile_off, sizes, len, status};
-        for (void* p : all) if (p) (void)hipFree(p);
-    }
-};
-
 constexpr int64_t kCraiMaxPos = 0x7fffffffLL;    // |alnStart| and alnSpan: what a BAM coordinate can hold
 
 }  // namespace
@@ -37,29 +27,28 @@ int gd_crai_sizes(gd_ctx* c, int32_t n_seq, const int64_t* seq_off, const int64_
         if (aln_span[i] < 0 || aln_span[i] > kCraiMaxPos)
             return fail(c, GD_E_RANGE, "crai: alignment span %lld of slice %lld is outside 0 .. 2^31 - 1", (long long)aln_span[i], (long long)i);
     }
-    CraiBufs b;
-    const size_t nl = std::max<size_t>((size_t)L, 1);
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.seq_off), (S + 1) * sizeof(int64_t)));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.tile_off), (S + 1) * sizeof(int64_t)));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.status), S * sizeof(int32_t)));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.start), nl * sizeof(int64_t)));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.span), nl * sizeof(int64_t)));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.len), nl * sizeof(int32_t)));
-    HIPCHK(c, hipMemcpyAsync(b.seq_off, seq_off, (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    DevBuf d_seq_off, d_tile_off, d_status, d_start, d_span, d_len, d_sizes;
+    if (int r = d_seq_off.alloc(c, (S + 1) * sizeof(int64_t))) return r;
+    if (int r = d_tile_off.alloc(c, (S + 1) * sizeof(int64_t))) return r;
+    if (int r = d_status.alloc(c, S * sizeof(int32_t))) return r;
+    if (int r = d_start.alloc(c, (size_t)L * sizeof(int64_t))) return r;
+    if (int r = d_span.alloc(c, (size_t)L * sizeof(int64_t))) return r;
+    if (int r = d_len.alloc(c, (size_t)L * sizeof(int32_t))) return r;
+    HIPCHK(c, hipMemcpyAsync(d_seq_off.p, seq_off, (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     if (L > 0) {
-        HIPCHK(c, hipMemcpyAsync(b.start, aln_start, (size_t)L * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(b.span, aln_span, (size_t)L * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(b.len, slice_len, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_start.p, aln_start, (size_t)L * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_span.p, aln_span, (size_t)L * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_len.p, slice_len, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     }
     gd::CraiJob j{};
     j.n_seq = n_seq;
-    j.seq_off = b.seq_off; j.aln_start = b.start; j.aln_span = b.span; j.slice_len = b.len;
-    j.tile_off = b.tile_off; j.status = b.status;
+    j.seq_off = d_seq_off.as<int64_t>(); j.aln_start = d_start.as<int64_t>(); j.aln_span = d_span.as<int64_t>();
+    j.slice_len = d_len.as<int32_t>(); j.tile_off = d_tile_off.as<int64_t>(); j.status = d_status.as<int32_t>();
     const unsigned grid = (unsigned)std::min<size_t>((S + gd::CRAI_WAVES - 1) / gd::CRAI_WAVES, 2048);
     hipLaunchKernelGGL(gd::gd_crai_kernel<false>, dim3(grid), dim3(gd::CRAI_WAVES * 64), 0, c->stream, j);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(tile_off, b.tile_off, (S + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(status, b.status, S * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(tile_off, d_tile_off.p, (S + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(status, d_status.p, S * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // the scan: the total decides whether the write pass runs at all, so it is needed here either way
     tile_off[0] = 0;
@@ -68,12 +57,12 @@ int gd_crai_sizes(gd_ctx* c, int32_t n_seq, const int64_t* seq_off, const int64_
     if (!sizes) return GD_OK;                                  // count only
     if ((uint64_t)total > (uint64_t)cap) return fail(c, GD_E_CAPACITY, "crai: %lld tiles, room for %zu", (long long)total, cap);
     if (total == 0) return GD_OK;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.sizes), (size_t)total * sizeof(int64_t)));
-    HIPCHK(c, hipMemcpyAsync(b.tile_off, tile_off, (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    j.sizes = b.sizes;
+    if (int r = d_sizes.alloc(c, (size_t)total * sizeof(int64_t))) return r;
+    HIPCHK(c, hipMemcpyAsync(d_tile_off.p, tile_off, (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    j.sizes = d_sizes.as<int64_t>();
     hipLaunchKernelGGL(gd::gd_crai_kernel<true>, dim3(grid), dim3(gd::CRAI_WAVES * 64), 0, c->stream, j);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(sizes, b.sizes, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sizes, d_sizes.p, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));              // (the buffers are freed on return)
     return GD_OK;
 }

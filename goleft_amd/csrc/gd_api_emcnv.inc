@@ -54,49 +54,6 @@ static void ec_drop(gd_ctx* c)
     c->ec = nullptr;
 }
 
-extern "C++" {
-// room for `need` elements, the first `used` kept (all on the context's stream)
-template <typename Tp>
-static int ec_grow(gd_ctx* c, Tp** p, size_t* cap, size_t need, size_t used)
-{
-    if (need <= *cap && *p) return GD_OK;
-    size_t ncap = std::max(need, *cap + *cap / 2);
-    if (ncap == 0) ncap = 1;
-    Tp* np = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&np), ncap * sizeof(Tp)));
-    if (*p) {
-        hipError_t e = hipSuccess;
-        if (used) e = hipMemcpyAsync(np, *p, used * sizeof(Tp), hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(np);
-            HIPCHK(c, e);
-        }
-        HIPCHK(c, hipFree(*p));
-    }
-    *p = np;
-    *cap = ncap;
-    return GD_OK;
-}
-}  // extern "C++"
-
-// buffers of gd_emcnv_finish that do not outlive it
-struct EcTemps {
-    std::vector<void*> v;
-    ~EcTemps() { for (void* p : v) (void)hipFree(p); }
-};
-
-extern "C++" {
-template <typename Tp>
-static int ec_alloc(gd_ctx* c, Tp** p, size_t count, EcTemps* owner = nullptr, bool zero = false)
-{
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(Tp)));
-    if (owner) owner->v.push_back(*p);
-    if (zero) HIPCHK(c, hipMemsetAsync(*p, 0, (count ? count : 1) * sizeof(Tp), c->stream));
-    return GD_OK;
-}
-}  // extern "C++"
-
 // workgroups of the two per-block kernels, which stride over the rows
 static unsigned ec_grid(uint64_t items, uint64_t per_wg)
 {
@@ -110,7 +67,7 @@ static unsigned ec_cover(uint64_t items, uint64_t per_wg) { return (unsigned)std
 static int ec_scan(gd_ctx* c, EcState& s, const uint32_t* in, uint64_t n, uint64_t base, uint64_t* out, uint64_t* d_total)
 {
     const uint64_t tiles = (n + gd::EMCNV_SCAN_TILE - 1) / gd::EMCNV_SCAN_TILE;
-    if (int r = ec_grow(c, &s.tiles, &s.cap_tiles, (size_t)tiles, 0)) return r;
+    if (int r = ensure_dev(c, &s.tiles, &s.cap_tiles, (size_t)tiles)) return r;
     hipLaunchKernelGGL(gd::gd_emcnv_scan_tile_kernel, dim3((unsigned)tiles), dim3(gd::EMCNV_WG), 0, c->stream, in, n, s.tiles);
     hipLaunchKernelGGL(gd::gd_emcnv_scan_top_kernel, dim3(1), dim3(gd::EMCNV_WG), 0, c->stream, s.tiles, tiles, base, d_total);
     hipLaunchKernelGGL(gd::gd_emcnv_scan_apply_kernel, dim3((unsigned)tiles), dim3(gd::EMCNV_WG), 0, c->stream, in, n,
@@ -132,14 +89,16 @@ static int ec_add(gd_ctx* c, EcState& s, bool cells, const void* d_in, const flo
 {
     const size_t N = (size_t)s.n, W = (size_t)s.words, R = s.R;
     double t0 = ing_now();
-    if (int r = ec_grow(c, &s.start, &s.cap_start, R + B, R)) return r;
-    if (int r = ec_grow(c, &s.end, &s.cap_end, R + B, R)) return r;
-    if (int r = ec_grow(c, &s.mbits, &s.cap_mbits, (R + B) * W, R * W)) return r;
-    if (int r = ec_grow(c, &s.rowoff, &s.cap_rowoff, R + B, R)) return r;
-    if (int r = ec_grow(c, &s.lambda, &s.cap_lambda, B * gd::EM_CENTRES, 0)) return r;
-    if (int r = ec_grow(c, &s.cn, &s.cap_cn, B * N, 0)) return r;
-    if (int r = ec_grow(c, &s.fc, &s.cap_fc, B * N, 0)) return r;
-    if (int r = ec_grow(c, &s.rowcnt, &s.cap_rowcnt, B, 0)) return r;
+    // (ensure_dev copies what is kept on the copy stream and waits for both streams: the copy stream is idle during a run,
+    // and the compute stream has been waited for wherever an array that is kept grows)
+    if (int r = ensure_dev(c, &s.start, &s.cap_start, R + B, true, R)) return r;
+    if (int r = ensure_dev(c, &s.end, &s.cap_end, R + B, true, R)) return r;
+    if (int r = ensure_dev(c, &s.mbits, &s.cap_mbits, (R + B) * W, true, R * W)) return r;
+    if (int r = ensure_dev(c, &s.rowoff, &s.cap_rowoff, R + B, true, R)) return r;
+    if (int r = ensure_dev(c, &s.lambda, &s.cap_lambda, B * gd::EM_CENTRES)) return r;
+    if (int r = ensure_dev(c, &s.cn, &s.cap_cn, B * N)) return r;
+    if (int r = ensure_dev(c, &s.fc, &s.cap_fc, B * N)) return r;
+    if (int r = ensure_dev(c, &s.rowcnt, &s.cap_rowcnt, B)) return r;
     HIPCHK(c, hipMemcpyAsync(s.start + R, starts, B * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(s.end + R, ends, B * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -163,9 +122,9 @@ static int ec_add(gd_ctx* c, EcState& s, bool cells, const void* d_in, const flo
     uint64_t total = 0;
     if (int r = ec_fetch(c, s.total, &total)) return r;
     if (total > s.members) {
-        if (int r = ec_grow(c, &s.m_depth, &s.cap_m_depth, (size_t)total, (size_t)s.members)) return r;
-        if (int r = ec_grow(c, &s.m_cn, &s.cap_m_cn, (size_t)total, (size_t)s.members)) return r;
-        if (int r = ec_grow(c, &s.m_fc, &s.cap_m_fc, (size_t)total, (size_t)s.members)) return r;
+        if (int r = ensure_dev(c, &s.m_depth, &s.cap_m_depth, (size_t)total, true, (size_t)s.members)) return r;
+        if (int r = ensure_dev(c, &s.m_cn, &s.cap_m_cn, (size_t)total, true, (size_t)s.members)) return r;
+        if (int r = ensure_dev(c, &s.m_fc, &s.cap_m_fc, (size_t)total, true, (size_t)s.members)) return r;
         j.m_depth = s.m_depth; j.m_cn = s.m_cn; j.m_fc = s.m_fc;
         if (cells) hipLaunchKernelGGL(gd::gd_emcnv_gather_kernel<int64_t>, grid, wg, 0, c->stream, j);
         else hipLaunchKernelGGL(gd::gd_emcnv_gather_kernel<float>, grid, wg, 0, c->stream, j);
@@ -198,9 +157,7 @@ static int ec_check_add(gd_ctx* c, EcState& s, size_t n_rows, const void* rows, 
     if (!rows || !starts || !ends) return GD_E_INVALID;
     // (F holds R + 1 in 32 bits)
     if (n_rows > 0xfffffffdull - s.R) return fail(c, GD_E_RANGE, "emcnv: more than 2^32 - 3 rows");
-    if (n_rows > (SIZE_MAX / sizeof(double)) / ((size_t)s.n > gd::EM_CENTRES ? (size_t)s.n : gd::EM_CENTRES))
-        return fail(c, GD_E_RANGE, "emcnv: %zu rows of %d samples do not fit an allocation", n_rows, s.n);
-    return GD_OK;
+    return em_check_fit(c, "emcnv", n_rows, s.n);
 }
 
 }  // namespace
@@ -233,11 +190,9 @@ int gd_emcnv_add(gd_ctx* c, const float* depths, size_t n_rows, const uint32_t* 
     if (int r = ec_check_add(c, s, n_rows, depths, starts, ends)) return r;
     if (n_rows == 0) return GD_OK;
     const size_t N = (size_t)s.n;
-    for (size_t i = 0; i < n_rows * N; ++i)
-        if (!(depths[i] >= 0.0f) || !std::isfinite(depths[i]))
-            return fail(c, GD_E_INVALID, "emcnv: the depth of row %zu, sample %zu is not a finite number >= 0", i / N, i % N);
+    if (int r = mat_check(c, "emcnv", depths, n_rows, s.n)) return r;
     const double t0 = ing_now();
-    if (int r = ec_grow(c, &s.in, &s.cap_in, n_rows * N, 0)) return r;
+    if (int r = ensure_dev(c, &s.in, &s.cap_in, n_rows * N)) return r;
     HIPCHK(c, hipMemcpyAsync(s.in, depths, n_rows * N * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     s.secs[0] += ing_now() - t0;
@@ -249,10 +204,7 @@ int gd_emcnv_add_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, const f
 {
     EC_STATE(c);
     const size_t N = (size_t)s.n;
-    if (scale)
-        for (size_t k = 0; k < N; ++k)
-            if (!(scale[k] >= 0.0f) || !std::isfinite(scale[k]))
-                return fail(c, GD_E_INVALID, "emcnv: the scale of sample %zu is not a finite number >= 0", k);
+    if (scale) if (int r = mat_check_scale(c, "emcnv", scale, s.n)) return r;
     if (int r = ec_check_add(c, s, n_rows, d_cells, starts, ends)) return r;
     if (n_rows == 0) return GD_OK;
     if (scale) {
@@ -282,7 +234,7 @@ int gd_emcnv_finish(gd_ctx* c, uint64_t* n_cnvs, uint64_t* n_members)
         const double t0 = ing_now();
         const size_t R = s.R, W = (size_t)s.words, pad = W * 64;
         const size_t n_chunks = (R + gd::EMCNV_CHUNK - 1) / gd::EMCNV_CHUNK;
-        EcTemps tmp;
+        DevList tmp;
         gd::EmcnvJob j{};
         j.R = (uint32_t)R; j.n = s.n; j.words = s.words; j.n_chunks = (uint32_t)n_chunks;
         j.start = s.start; j.end = s.end; j.mbits = s.mbits; j.rowoff = s.rowoff;
@@ -290,17 +242,17 @@ int gd_emcnv_finish(gd_ctx* c, uint64_t* n_cnvs, uint64_t* n_members)
         uint32_t* ecnt = nullptr;
         uint64_t* eoff = nullptr;
         const size_t n1 = (R + 63) / 64, n2 = (n1 + 63) / 64;
-        if (int r = ec_alloc(c, &j.F, R, &tmp)) return r;
-        if (int r = ec_alloc(c, &j.span1, n1 * 4, &tmp)) return r;
-        if (int r = ec_alloc(c, &j.span2, n2 * 4, &tmp)) return r;
-        if (int r = ec_alloc(c, &j.first, n_chunks * pad, &tmp)) return r;
-        if (int r = ec_alloc(c, &j.last, n_chunks * pad, &tmp)) return r;
-        if (int r = ec_alloc(c, &j.lastF, n_chunks * pad, &tmp)) return r;
-        if (int r = ec_alloc(c, &j.tail, n_chunks * pad, &tmp)) return r;
-        if (int r = ec_alloc(c, &j.psize, R + 1, &tmp, true)) return r;
-        if (int r = ec_alloc(c, &ecnt, R + 1, &tmp, true)) return r;
-        if (int r = ec_alloc(c, &j.ebits, (R + 1) * W, &tmp, true)) return r;
-        if (int r = ec_alloc(c, &eoff, R + 1, &tmp)) return r;
+        if (int r = tmp.alloc(c, &j.F, R)) return r;
+        if (int r = tmp.alloc(c, &j.span1, n1 * 4)) return r;
+        if (int r = tmp.alloc(c, &j.span2, n2 * 4)) return r;
+        if (int r = tmp.alloc(c, &j.first, n_chunks * pad)) return r;
+        if (int r = tmp.alloc(c, &j.last, n_chunks * pad)) return r;
+        if (int r = tmp.alloc(c, &j.lastF, n_chunks * pad)) return r;
+        if (int r = tmp.alloc(c, &j.tail, n_chunks * pad)) return r;
+        if (int r = tmp.alloc(c, &j.psize, R + 1, true)) return r;
+        if (int r = tmp.alloc(c, &ecnt, R + 1, true)) return r;
+        if (int r = tmp.alloc(c, &j.ebits, (R + 1) * W, true)) return r;
+        if (int r = tmp.alloc(c, &eoff, R + 1)) return r;
         j.ecnt = ecnt; j.eoff = eoff;
         const dim3 wg(gd::EMCNV_WG), walk(ec_cover(n_chunks * W, gd::EMCNV_WAVES));
         hipLaunchKernelGGL(gd::gd_emcnv_span_kernel<1>, dim3(ec_cover(n1, gd::EMCNV_WAVES)), wg, 0, c->stream, j);
@@ -315,17 +267,17 @@ int gd_emcnv_finish(gd_ctx* c, uint64_t* n_cnvs, uint64_t* n_members)
         if (int r = ec_fetch(c, s.total, &n_c)) return r;
         if (n_c > 0x7fffffffull * gd::EMCNV_WAVES) return fail(c, GD_E_RANGE, "emcnv: more than 2^33 - 4 CNVs");
         // the result is the state's only once it is whole
-        EcTemps res;
+        DevList res;
         uint32_t *c_sample, *c_psize, *c_emit, *c_count, *c_last, *o_row = nullptr;
         uint64_t* member_off;
         float *o_depth = nullptr, *o_fc = nullptr;
         uint8_t* o_cn = nullptr;
-        if (int r = ec_alloc(c, &c_sample, n_c, &res)) return r;
-        if (int r = ec_alloc(c, &c_psize, n_c, &res)) return r;
-        if (int r = ec_alloc(c, &c_emit, n_c, &res)) return r;
-        if (int r = ec_alloc(c, &c_count, n_c, &res)) return r;
-        if (int r = ec_alloc(c, &c_last, n_c, &res)) return r;
-        if (int r = ec_alloc(c, &member_off, n_c + 1, &res, true)) return r;
+        if (int r = res.alloc(c, &c_sample, n_c)) return r;
+        if (int r = res.alloc(c, &c_psize, n_c)) return r;
+        if (int r = res.alloc(c, &c_emit, n_c)) return r;
+        if (int r = res.alloc(c, &c_count, n_c)) return r;
+        if (int r = res.alloc(c, &c_last, n_c)) return r;
+        if (int r = res.alloc(c, &member_off, n_c + 1, true)) return r;
         if (n_c > 0) {
             j.c_sample = c_sample; j.c_psize = c_psize; j.c_emit = c_emit; j.c_count = c_count; j.c_last = c_last;
             j.n_cnvs = n_c;
@@ -333,17 +285,17 @@ int gd_emcnv_finish(gd_ctx* c, uint64_t* n_cnvs, uint64_t* n_members)
             HIPCHK(c, hipGetLastError());
             if (int r = ec_scan(c, s, c_count, n_c, 0, member_off, member_off + n_c)) return r;
             if (int r = ec_fetch(c, member_off + n_c, &n_m)) return r;
-            if (int r = ec_alloc(c, &o_row, n_m, &res)) return r;
-            if (int r = ec_alloc(c, &o_depth, n_m, &res)) return r;
-            if (int r = ec_alloc(c, &o_cn, n_m, &res)) return r;
-            if (int r = ec_alloc(c, &o_fc, n_m, &res)) return r;
+            if (int r = res.alloc(c, &o_row, n_m)) return r;
+            if (int r = res.alloc(c, &o_depth, n_m)) return r;
+            if (int r = res.alloc(c, &o_cn, n_m)) return r;
+            if (int r = res.alloc(c, &o_fc, n_m)) return r;
             j.member_off = member_off;
             j.o_row = o_row; j.o_depth = o_depth; j.o_cn = o_cn; j.o_fc = o_fc;
             hipLaunchKernelGGL(gd::gd_emcnv_members_kernel, dim3(ec_cover(n_c, gd::EMCNV_WAVES)), wg, 0, c->stream, j);
             HIPCHK(c, hipGetLastError());
         }
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        res.v.clear();
+        res.release();
         s.c_sample = c_sample; s.c_psize = c_psize; s.c_emit = c_emit; s.c_count = c_count; s.c_last = c_last;
         s.member_off = member_off; s.o_row = o_row; s.o_depth = o_depth; s.o_cn = o_cn; s.o_fc = o_fc;
         s.n_cnvs = n_c; s.n_members = n_m;

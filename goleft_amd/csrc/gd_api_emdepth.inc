@@ -4,21 +4,6 @@
 
 namespace {
 
-// the device buffers of one call, freed when it returns
-struct EmBufs {
-    void* in = nullptr;
-    float* scale = nullptr;
-    double* lambda = nullptr;
-    uint8_t* iters = nullptr;
-    uint8_t* cn = nullptr;
-    float* log2fc = nullptr;
-    ~EmBufs()
-    {
-        for (void* p : {in, (void*)scale, (void*)lambda, (void*)iters, (void*)cn, (void*)log2fc})
-            if (p) (void)hipFree(p);
-    }
-};
-
 static int em_check_n(gd_ctx* c, int n_samples)
 {
     if (n_samples == 2)
@@ -26,6 +11,13 @@ static int em_check_n(gd_ctx* c, int n_samples)
     if (n_samples < 1 || n_samples > gd::EM_MAX_N)
         return fail(c, GD_E_RANGE, "emdepth: 1 or 3 .. %d samples, not %d", gd::EM_MAX_N, n_samples);
     return GD_OK;
+}
+
+// (the largest array of a call: nine centres a row in float64, or a value a sample)
+static int em_check_fit(gd_ctx* c, const char* who, size_t n_rows, int n_samples)
+{
+    if (gdm::fits(n_rows, (size_t)n_samples, gd::EM_CENTRES)) return GD_OK;
+    return fail(c, GD_E_RANGE, "%s: %zu rows of %d samples do not fit an allocation", who, n_rows, n_samples);
 }
 
 // the kernel on rows already on the device (float32 when !cells, int64 otherwise); every output is a device pointer or
@@ -57,19 +49,22 @@ static int em_launch(gd_ctx* c, bool cells, const void* d_in, const float* d_sca
 
 // d_in: the rows on the device (float32 when !cells, int64 otherwise); d_scale: device or nullptr
 static int em_run(gd_ctx* c, bool cells, const void* d_in, const float* d_scale, size_t n_rows, int n_samples,
-                  double* lambda, uint8_t* iters, uint8_t* cn, float* log2fc, EmBufs& b)
+                  double* lambda, uint8_t* iters, uint8_t* cn, float* log2fc)
 {
     const size_t N = (size_t)n_samples, cellsN = n_rows * N;
-    if (lambda) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.lambda), n_rows * gd::EM_CENTRES * sizeof(double)));
-    if (iters) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.iters), n_rows));
-    if (cn) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.cn), cellsN));
-    if (log2fc) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.log2fc), cellsN * sizeof(float)));
-    if (int r = em_launch(c, cells, d_in, d_scale, n_rows, n_samples, b.lambda, b.iters, b.cn, b.log2fc, &c->em_secs[1])) return r;
+    DevBuf b_lambda, b_iters, b_cn, b_fc;
+    if (lambda) if (int r = b_lambda.alloc(c, n_rows * gd::EM_CENTRES * sizeof(double))) return r;
+    if (iters) if (int r = b_iters.alloc(c, n_rows)) return r;
+    if (cn) if (int r = b_cn.alloc(c, cellsN)) return r;
+    if (log2fc) if (int r = b_fc.alloc(c, cellsN * sizeof(float))) return r;
+    if (int r = em_launch(c, cells, d_in, d_scale, n_rows, n_samples, b_lambda.as<double>(), b_iters.as<uint8_t>(),
+                          b_cn.as<uint8_t>(), b_fc.as<float>(), &c->em_secs[1]))
+        return r;
     const double t1 = ing_now();
-    if (lambda) HIPCHK(c, hipMemcpyAsync(lambda, b.lambda, n_rows * gd::EM_CENTRES * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (iters) HIPCHK(c, hipMemcpyAsync(iters, b.iters, n_rows, hipMemcpyDeviceToHost, c->stream));
-    if (cn) HIPCHK(c, hipMemcpyAsync(cn, b.cn, cellsN, hipMemcpyDeviceToHost, c->stream));
-    if (log2fc) HIPCHK(c, hipMemcpyAsync(log2fc, b.log2fc, cellsN * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (lambda) HIPCHK(c, hipMemcpyAsync(lambda, b_lambda.p, n_rows * gd::EM_CENTRES * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (iters) HIPCHK(c, hipMemcpyAsync(iters, b_iters.p, n_rows, hipMemcpyDeviceToHost, c->stream));
+    if (cn) HIPCHK(c, hipMemcpyAsync(cn, b_cn.p, cellsN, hipMemcpyDeviceToHost, c->stream));
+    if (log2fc) HIPCHK(c, hipMemcpyAsync(log2fc, b_fc.p, cellsN * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->em_secs[2] = ing_now() - t1;
     return GD_OK;
@@ -84,21 +79,18 @@ int gd_emdepth(gd_ctx* c, const float* depths, size_t n_rows, int n_samples, dou
     if (int r = em_check_n(c, n_samples)) return r;
     if (n_rows == 0) return GD_OK;
     if (!depths) return GD_E_INVALID;
-    const size_t N = (size_t)n_samples;
-    if (n_rows > (SIZE_MAX / sizeof(double)) / (N > gd::EM_CENTRES ? N : gd::EM_CENTRES))
-        return fail(c, GD_E_RANGE, "emdepth: %zu rows of %d samples do not fit an allocation", n_rows, n_samples);
-    for (size_t i = 0; i < n_rows * N; ++i)
-        if (!(depths[i] >= 0.0f) || !std::isfinite(depths[i]))
-            return fail(c, GD_E_INVALID, "emdepth: the depth of row %zu, sample %zu is not a finite number >= 0", i / N, i % N);
+    if (int r = em_check_fit(c, "emdepth", n_rows, n_samples)) return r;
+    if (int r = mat_check(c, "emdepth", depths, n_rows, n_samples)) return r;
     if (int r = set_device(c)) return r;
     c->em_secs[0] = c->em_secs[1] = c->em_secs[2] = 0;
-    EmBufs b;
+    const size_t bytes = n_rows * (size_t)n_samples * sizeof(float);
+    DevBuf in;
     const double t0 = ing_now();
-    HIPCHK(c, hipMalloc(&b.in, n_rows * N * sizeof(float)));
-    HIPCHK(c, hipMemcpyAsync(b.in, depths, n_rows * N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (int r = in.alloc(c, bytes)) return r;
+    HIPCHK(c, hipMemcpyAsync(in.p, depths, bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->em_secs[0] = ing_now() - t0;
-    return em_run(c, false, b.in, nullptr, n_rows, n_samples, lambda, iters, cn, log2fc, b);
+    return em_run(c, false, in.p, nullptr, n_rows, n_samples, lambda, iters, cn, log2fc);
 }
 
 int gd_emdepth_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, int n_samples, const float* scale, double* lambda,
@@ -106,26 +98,21 @@ int gd_emdepth_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, int n_sam
 {
     if (!c) return GD_E_INVALID;
     if (int r = em_check_n(c, n_samples)) return r;
-    const size_t N = (size_t)n_samples;
-    if (scale)
-        for (size_t s = 0; s < N; ++s)
-            if (!(scale[s] >= 0.0f) || !std::isfinite(scale[s]))
-                return fail(c, GD_E_INVALID, "emdepth: the scale of sample %zu is not a finite number >= 0", s);
+    if (scale) if (int r = mat_check_scale(c, "emdepth", scale, n_samples)) return r;
     if (n_rows == 0) return GD_OK;
     if (!d_cells) return GD_E_INVALID;
-    if (n_rows > (SIZE_MAX / sizeof(double)) / (N > gd::EM_CENTRES ? N : gd::EM_CENTRES))
-        return fail(c, GD_E_RANGE, "emdepth: %zu rows of %d samples do not fit an allocation", n_rows, n_samples);
+    if (int r = em_check_fit(c, "emdepth", n_rows, n_samples)) return r;
     if (int r = set_device(c)) return r;
     c->em_secs[0] = c->em_secs[1] = c->em_secs[2] = 0;
-    EmBufs b;
+    DevBuf d_scale;
     if (scale) {
         const double t0 = ing_now();
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.scale), N * sizeof(float)));
-        HIPCHK(c, hipMemcpyAsync(b.scale, scale, N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        if (int r = d_scale.alloc(c, (size_t)n_samples * sizeof(float))) return r;
+        HIPCHK(c, hipMemcpyAsync(d_scale.p, scale, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->em_secs[0] = ing_now() - t0;
     }
-    return em_run(c, true, d_cells, b.scale, n_rows, n_samples, lambda, iters, cn, log2fc, b);
+    return em_run(c, true, d_cells, d_scale.as<float>(), n_rows, n_samples, lambda, iters, cn, log2fc);
 }
 
 // gd_emdepth for a float32 matrix that is in HBM already: gd_devmat.hpp's check in place of the host's, no upload
@@ -136,14 +123,11 @@ int gd_emdepth_device(gd_ctx* c, const float* d_depths, size_t n_rows, int n_sam
     if (int r = em_check_n(c, n_samples)) return r;
     if (n_rows == 0) return GD_OK;
     if (!d_depths) return GD_E_INVALID;
-    const size_t N = (size_t)n_samples;
-    if (n_rows > (SIZE_MAX / sizeof(double)) / (N > gd::EM_CENTRES ? N : gd::EM_CENTRES))
-        return fail(c, GD_E_RANGE, "emdepth: %zu rows of %d samples do not fit an allocation", n_rows, n_samples);
+    if (int r = em_check_fit(c, "emdepth", n_rows, n_samples)) return r;
     if (int r = set_device(c)) return r;
     if (int r = dm_check(c, "emdepth", d_depths, n_rows, n_samples)) return r;
     c->em_secs[0] = c->em_secs[1] = c->em_secs[2] = 0;
-    EmBufs b;
-    return em_run(c, false, d_depths, nullptr, n_rows, n_samples, lambda, iters, cn, log2fc, b);
+    return em_run(c, false, d_depths, nullptr, n_rows, n_samples, lambda, iters, cn, log2fc);
 }
 
 int gd_emdepth_timing(gd_ctx* c, double* out, size_t n)

@@ -29,18 +29,6 @@ static void is_drop(gd_ctx* c)
     c->isp = nullptr;
 }
 
-// the device copies of one batch, freed when the call returns
-struct IsBatch {
-    int64_t *sizes = nullptr, *tile_off = nullptr;
-    int32_t* tile_cnt = nullptr;
-    ~IsBatch()
-    {
-        if (sizes) (void)hipFree(sizes);
-        if (tile_off) (void)hipFree(tile_off);
-        if (tile_cnt) (void)hipFree(tile_cnt);
-    }
-};
-
 constexpr int32_t kIsMaxTiles = 1 << 24;       // per reference (a .bai ends at 2^29 bases: 32 768 tiles)
 
 }  // namespace
@@ -115,18 +103,18 @@ int gd_indexsplit_add(gd_ctx* c, int32_t n_samples, const int64_t* sample_off, c
         if (sizes[i] < 0) return fail(c, GD_E_INVALID, "indexsplit: negative tile size at %lld", (long long)i);
     if (T == 0 || s.n_cells == 0) return GD_OK;
     const double t0 = ing_now();
-    IsBatch b;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.sizes), (size_t)T * sizeof(int64_t)));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.tile_off), N * R * sizeof(int64_t)));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&b.tile_cnt), N * R * sizeof(int32_t)));
-    HIPCHK(c, hipMemcpyAsync(b.sizes, sizes, (size_t)T * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b.tile_off, tile_off, N * R * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b.tile_cnt, tile_cnt, N * R * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    DevBuf d_sizes, d_tile_off, d_tile_cnt;              // the device copies of the batch
+    if (int r = d_sizes.alloc(c, (size_t)T * sizeof(int64_t))) return r;
+    if (int r = d_tile_off.alloc(c, N * R * sizeof(int64_t))) return r;
+    if (int r = d_tile_cnt.alloc(c, N * R * sizeof(int32_t))) return r;
+    HIPCHK(c, hipMemcpyAsync(d_sizes.p, sizes, (size_t)T * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_tile_off.p, tile_off, N * R * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_tile_cnt.p, tile_cnt, N * R * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const double t1 = ing_now();
     gd::IsJob j{};
     j.n_samples = n_samples; j.n_refs = s.R;
-    j.sizes = b.sizes; j.tile_off = b.tile_off; j.tile_cnt = b.tile_cnt;
+    j.sizes = d_sizes.as<int64_t>(); j.tile_off = d_tile_off.as<int64_t>(); j.tile_cnt = d_tile_cnt.as<int32_t>();
     j.longest = s.d_longest; j.cell_off = s.d_cell_off; j.sums = s.d_sums;
     const unsigned gx = (unsigned)std::min<int64_t>(((int64_t)s.most + gd::IS_WG - 1) / gd::IS_WG, 1024);
     const unsigned gy = (unsigned)std::min<size_t>(R, 65535);

@@ -12,17 +12,13 @@ int gd_inflate_bgzf(gd_ctx* c, const uint8_t* data, size_t n_bytes, size_t n_mem
     for (size_t m = 0; m < n_members; ++m)
         if (in_off[m] + in_len[m] > n_bytes || out_off[m] + out_len[m] > out_bytes)
             return fail(c, GD_E_RANGE, "BGZF member %zu outside the given buffers", m);
-    uint8_t *d_in = nullptr, *d_out = nullptr, *d_tab = nullptr;
+    DevBuf b_in, b_out, b_tab;
     const size_t tab_bytes = n_members * (2 * sizeof(uint64_t) + 4 * sizeof(uint32_t));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_in), n_bytes + gd::INF_SLACK);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_out), out_bytes + gd::INF_SLACK);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_tab), tab_bytes);
-    if (e != hipSuccess) {
-        if (d_in) (void)hipFree(d_in);
-        if (d_out) (void)hipFree(d_out);
-        return fail(c, GD_E_NOMEM, "device allocation for BGZF inflate failed");
-    }
-    uint64_t* t_in_off = reinterpret_cast<uint64_t*>(d_tab);
+    if (int r = b_in.alloc(c, n_bytes + gd::INF_SLACK)) return r;
+    if (int r = b_out.alloc(c, out_bytes + gd::INF_SLACK)) return r;
+    if (int r = b_tab.alloc(c, tab_bytes)) return r;
+    uint8_t *d_in = b_in.as<uint8_t>(), *d_out = b_out.as<uint8_t>();
+    uint64_t* t_in_off = b_tab.as<uint64_t>();
     uint64_t* t_out_off = t_in_off + n_members;
     uint32_t* t_in_len = reinterpret_cast<uint32_t*>(t_out_off + n_members);
     uint32_t* t_out_len = t_in_len + n_members;
@@ -48,7 +44,6 @@ int gd_inflate_bgzf(gd_ctx* c, const uint8_t* data, size_t n_bytes, size_t n_mem
         float ms = 0;
         if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) c->kernel_ms[GD_K_INFLATE] = ms;
     }
-    (void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(d_tab);
     for (hipError_t x : {e1, e2, e3, e4, e5, e6, e7, e8})
         if (x != hipSuccess) return fail(c, GD_E_HIP, "BGZF inflate kernel failed: %s", hipGetErrorString(x));
     return GD_OK;

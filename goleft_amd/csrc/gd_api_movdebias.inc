@@ -1,24 +1,11 @@
 // gd_api_movdebias.inc -- dcnv's GeneralDebiaser, a moving median over the rows in covariate order (part of gd_api.hip,
 // inside extern "C"; DESIGN.md section 3.15).  The argsort of the covariate (debiaser.go:56-76; ties by row) is host work
-// inside the call, the windows and the division are gd_movdebias.hpp's kernel.  gd_moving_debias_cells is the form for the
+// inside the call (gd_matcheck.hpp), the windows and the division are gd_movdebias.hpp's kernel.  gd_moving_debias_cells is the form for the
 // int64 cells gd_depthwed_device leaves: gd_devmat.hpp's conversion into a buffer of the call's own (a window reads rows
 // other workgroups divide, so the division cannot run in place), then the same kernel into the caller's device matrix.
 // Nothing is kept between calls but the timings.
 
 namespace {
-
-// the device buffers of one call, freed when it returns
-struct MdBufs {
-    void* cells = nullptr;
-    void* order = nullptr;
-    void* out = nullptr;
-    void* med = nullptr;
-    ~MdBufs()
-    {
-        for (void* p : {cells, order, out, med})
-            if (p) (void)hipFree(p);
-    }
-};
 
 // what both forms check before anything else, in gd_moving_debias's order
 static int md_check(gd_ctx* c, size_t n_rows, int n_samples, bool pointers, const double* vals, int window)
@@ -44,42 +31,36 @@ static int md_run(gd_ctx* c, const float* depths, const int64_t* d_from, float* 
 {
     const size_t N = (size_t)n_samples;
     const double t0 = ing_now();
-    std::vector<uint32_t> order(n_rows);
-    for (size_t r = 0; r < n_rows; ++r) order[r] = (uint32_t)r;
-    std::sort(order.begin(), order.end(), [vals](uint32_t a, uint32_t b) { return vals[a] < vals[b] || (vals[a] == vals[b] && a < b); });
+    const std::vector<uint32_t> order = gdm::argsort(vals, n_rows);
     if (int r = set_device(c)) return r;
     for (double& s : c->md_secs) s = 0;
     c->md_secs[0] = ing_now() - t0;
 
-    MdBufs b;
-    DmWord negative;
+    DevBuf d_cells, d_order, d_out, d_med, negative;
     const size_t cells = n_rows * N;
     const double t1 = ing_now();
-    HIPCHK(c, hipMalloc(&b.cells, cells * sizeof(float)));
-    HIPCHK(c, hipMalloc(&b.order, n_rows * sizeof(uint32_t)));
-    if (!d_resident) HIPCHK(c, hipMalloc(&b.out, cells * sizeof(float)));
-    if (med) HIPCHK(c, hipMalloc(&b.med, cells * sizeof(double)));
-    if (!d_resident) HIPCHK(c, hipMemcpyAsync(b.cells, depths, cells * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b.order, order.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (int r = d_cells.alloc(c, cells * sizeof(float))) return r;
+    if (int r = d_order.alloc(c, n_rows * sizeof(uint32_t))) return r;
+    if (!d_resident) if (int r = d_out.alloc(c, cells * sizeof(float))) return r;
+    if (med) if (int r = d_med.alloc(c, cells * sizeof(double))) return r;
+    if (!d_resident) HIPCHK(c, hipMemcpyAsync(d_cells.p, depths, cells * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_order.p, order.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->md_secs[1] = ing_now() - t1;
 
     gd::MdJob j{};
-    j.cells = static_cast<const uint32_t*>(b.cells);
+    j.cells = d_cells.as<const uint32_t>();
     j.n_rows = (int64_t)n_rows; j.n = n_samples; j.window = window;
     j.segment = c->md_segment > 0 ? c->md_segment : window <= gd::MD_CAP_MID ? gd::MD_SEG_SMALL : gd::MD_SEG_BIG;
-    j.order = static_cast<const uint32_t*>(b.order);
-    j.out = d_resident ? d_resident : static_cast<float*>(b.out); j.med = static_cast<double*>(b.med);
+    j.order = d_order.as<const uint32_t>();
+    j.out = d_resident ? d_resident : d_out.as<float>(); j.med = d_med.as<double>();
     const dim3 grid((unsigned)(((int64_t)n_rows + j.segment - 1) / j.segment), (unsigned)((N + gd::MD_COLS - 1) / gd::MD_COLS));
     const dim3 wg(gd::MD_COLS);
     const double t2 = ing_now();
     if (d_resident) {
         // The conversion, and its verdict before anything else runs: a negative cell leaves the caller's matrix alone.
-        if (int r = dm_from_cells(c, d_from, static_cast<float*>(b.cells), n_rows, n_samples, negative)) return r;
-        uint32_t flag = 0;
-        HIPCHK(c, hipMemcpyAsync(&flag, negative.p, sizeof flag, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (flag) return fail(c, GD_E_INVALID, "moving debias: a cell of the device matrix is negative");
+        if (int r = dm_from_cells(c, d_from, d_cells.as<float>(), n_rows, n_samples, negative)) return r;
+        if (int r = dm_refuse_negative(c, "moving debias", negative)) return r;
     }
     if (window <= gd::MD_CAP_SMALL) hipLaunchKernelGGL(gd::gd_movdebias_kernel<gd::MD_CAP_SMALL>, grid, wg, 0, c->stream, j);
     else if (window <= gd::MD_CAP_MID) hipLaunchKernelGGL(gd::gd_movdebias_kernel<gd::MD_CAP_MID>, grid, wg, 0, c->stream, j);
@@ -89,8 +70,8 @@ static int md_run(gd_ctx* c, const float* depths, const int64_t* d_from, float* 
     c->md_secs[2] = ing_now() - t2;
 
     const double t3 = ing_now();
-    if (out) HIPCHK(c, hipMemcpyAsync(out, b.out, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (med) HIPCHK(c, hipMemcpyAsync(med, b.med, cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (out) HIPCHK(c, hipMemcpyAsync(out, d_out.p, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (med) HIPCHK(c, hipMemcpyAsync(med, d_med.p, cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->md_secs[3] = ing_now() - t3;
     return GD_OK;
@@ -103,10 +84,7 @@ int gd_moving_debias(gd_ctx* c, const float* depths, size_t n_rows, int n_sample
 {
     if (!c) return GD_E_INVALID;
     if (int r = md_check(c, n_rows, n_samples, depths && out, vals, window)) return r;
-    const size_t N = (size_t)n_samples;
-    for (size_t i = 0; i < n_rows * N; ++i)
-        if (!(depths[i] >= 0.0f) || !std::isfinite(depths[i]))
-            return fail(c, GD_E_INVALID, "moving debias: the depth of row %zu, sample %zu is not a finite number >= 0", i / N, i % N);
+    if (int r = mat_check(c, "moving debias", depths, n_rows, n_samples)) return r;
     return md_run(c, depths, nullptr, nullptr, n_rows, n_samples, vals, window, out, med);
 }
 
@@ -116,7 +94,7 @@ int gd_moving_debias_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, int
     if (!c) return GD_E_INVALID;
     if (int r = md_check(c, n_rows, n_samples, d_cells && d_out, vals, window)) return r;
     const size_t cells = n_rows * (size_t)n_samples;
-    if (dm_overlap(d_cells, cells * sizeof(int64_t), d_out, cells * sizeof(float)))
+    if (gdm::overlap(d_cells, cells * sizeof(int64_t), d_out, cells * sizeof(float)))
         return fail(c, GD_E_INVALID, "moving debias: the quotients would overlap the cells they are made of");
     return md_run(c, nullptr, d_cells, d_out, n_rows, n_samples, vals, window, nullptr, nullptr);
 }

@@ -74,18 +74,14 @@ int gd_region_windows(gd_ctx* c, int32_t tid, int64_t start, int64_t end, int64_
     if (cap < k || !sums) return fail(c, GD_E_CAPACITY, "need room for %zu windows", k);
     if (h.length <= 0) { for (size_t i = 0; i < k; ++i) { sums[i] = 0; if (mins) mins[i] = 0; } return GD_OK; }
     if (!c->d_perbase) return fail(c, GD_E_STATE, "the per-base vector was not kept (gd_set_outputs)");
-    int64_t* d_s = nullptr;
-    int32_t* d_m = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d_s), k * sizeof(int64_t)));
-    if (hipMalloc(reinterpret_cast<void**>(&d_m), k * sizeof(int32_t)) != hipSuccess) { (void)hipFree(d_s); return fail(c, GD_E_NOMEM, "hipMalloc"); }
+    DevBuf d_s, d_m;
+    if (int r = d_s.alloc(c, k * sizeof(int64_t))) return r;
+    if (int r = d_m.alloc(c, k * sizeof(int32_t))) return r;
     hipLaunchKernelGGL(gd::gd_region_windows_kernel, dim3((unsigned)k), dim3(256), 0, c->stream,
-                       c->d_perbase + h.base_off, h.length, start, end, (int32_t)W, first, d_s, d_m);
-    hipError_t e1 = hipMemcpyAsync(sums, d_s, k * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-    hipError_t e2 = mins ? hipMemcpyAsync(mins, d_m, k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-    hipError_t e3 = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_s);
-    (void)hipFree(d_m);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(c, GD_E_HIP, "region window reduction failed");
+                       c->d_perbase + h.base_off, h.length, start, end, (int32_t)W, first, d_s.as<int64_t>(), d_m.as<int32_t>());
+    HIPCHK(c, hipMemcpyAsync(sums, d_s.p, k * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (mins) HIPCHK(c, hipMemcpyAsync(mins, d_m.p, k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return GD_OK;
 }
 
@@ -106,24 +102,21 @@ int gd_region_callable(gd_ctx* c, int32_t tid, int64_t start, int64_t end, gd_ru
     if (!c->d_perbase) return fail(c, GD_E_STATE, "the per-base vector was not kept (gd_set_outputs)");
     size_t bcap = std::max<size_t>(cap, 1024);
     for (;;) {
-        int2* d_b = nullptr;
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d_b), bcap * sizeof(int2)));
+        DevBuf d_b;                              // (a round that found too little room gives its buffer back before the next)
+        if (int r = d_b.alloc(c, bcap * sizeof(int2))) return r;
         (void)hipMemsetAsync(c->d_region_cursor, 0, sizeof(uint32_t), c->stream);
         int64_t len = end - start;
         unsigned blocks = (unsigned)std::min<int64_t>((len + 255) / 256, 4096);
         hipLaunchKernelGGL(gd::gd_region_bounds_kernel, dim3(blocks), dim3(256), 0, c->stream,
                            c->d_perbase + h.base_off, h.length, start, end, c->params.min_cov,
-                           c->params.max_mean_depth, d_b, (uint32_t)std::min<size_t>(bcap, 0xffffffffu),
+                           c->params.max_mean_depth, d_b.as<int2>(), (uint32_t)std::min<size_t>(bcap, 0xffffffffu),
                            c->d_region_cursor);
         uint32_t cnt = 0;
-        hipError_t e1 = hipMemcpyAsync(&cnt, c->d_region_cursor, sizeof cnt, hipMemcpyDeviceToHost, c->stream);
-        hipError_t e2 = hipStreamSynchronize(c->stream);
-        if (e1 != hipSuccess || e2 != hipSuccess) { (void)hipFree(d_b); return fail(c, GD_E_HIP, "region class reduction failed"); }
-        if (cnt > bcap) { (void)hipFree(d_b); bcap = cnt; continue; }
+        HIPCHK(c, hipMemcpyAsync(&cnt, c->d_region_cursor, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (cnt > bcap) { bcap = cnt; continue; }
         std::vector<int2> b(cnt);
-        hipError_t e3 = cnt ? hipMemcpy(b.data(), d_b, cnt * sizeof(int2), hipMemcpyDeviceToHost) : hipSuccess;
-        (void)hipFree(d_b);
-        if (e3 != hipSuccess) return fail(c, GD_E_HIP, "region class copy failed");
+        if (cnt) HIPCHK(c, hipMemcpy(b.data(), d_b.p, cnt * sizeof(int2), hipMemcpyDeviceToHost));
         std::sort(b.begin(), b.end(), [](const int2& a, const int2& z) { return a.x < z.x; });
         *n = cnt;
         if (cap < cnt || !out) return fail(c, GD_E_CAPACITY, "need room for %u runs", cnt);
@@ -193,7 +186,7 @@ int gd_regions(gd_ctx* c, size_t n_regions, const int32_t* tid, const int64_t* s
             const size_t o_cr = o_wr + ((n_dw * 4 + 15) & ~(size_t)15), o_s = o_cr + ((n_ch * 4 + 15) & ~(size_t)15);
             const size_t o_m = o_s + n_dw * 8, o_b = (o_m + n_dw * 4 + 15) & ~(size_t)15, o_c = o_b + bcap * sizeof(int4);
             DevBuf d;
-            if (d.alloc(o_c + 16) != hipSuccess) return fail(c, GD_E_NOMEM, "device allocation for the region batch failed");
+            if (int r = d.alloc(c, o_c + 16)) return r;
             uint8_t* base = d.as<uint8_t>();
             gd::RegionTab* d_tab = reinterpret_cast<gd::RegionTab*>(base + o_tab);
             uint32_t* d_wr = reinterpret_cast<uint32_t*>(base + o_wr);

@@ -334,23 +334,62 @@ int in_flight(gd_ctx* c)
                         __FILE__, __LINE__);                                           \
     } while (0)
 
+// One device buffer of one call, freed when the call returns however it returns: the only owner of per-call device
+// memory in the ABI (states that live across calls have destructors of their own).  Never allocated: as() is null.
+struct DevBuf {
+    void* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int alloc(gd_ctx* c, size_t bytes)
+    {
+        HIPCHK(c, hipMalloc(&p, bytes ? bytes : 1));
+        return GD_OK;
+    }
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+    void* release() { void* q = p; p = nullptr; return q; }       // the buffer is the caller's from here on
+};
+
+// Its companion for a call whose number of buffers is only known as it runs: all freed on return, unless release() has
+// handed them to a state that keeps them.
+struct DevList {
+    std::vector<void*> v;
+    DevList() = default;
+    DevList(const DevList&) = delete;
+    DevList& operator=(const DevList&) = delete;
+    ~DevList() { for (void* p : v) (void)hipFree(p); }
+    // *out = count elements (at least one), zeroed on the context's stream when asked for
+    template <typename T>
+    int alloc(gd_ctx* c, T** out, size_t count, bool zero = false)
+    {
+        const size_t bytes = (count ? count : 1) * sizeof(T);
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(out), bytes));
+        v.push_back(*out);
+        if (zero) HIPCHK(c, hipMemsetAsync(*out, 0, bytes, c->stream));
+        return GD_OK;
+    }
+    void release() { v.clear(); }
+};
+
+// Room for `need` elements in a device array the context keeps (grow-only, by half at least); with keep, the first `used`
+// stay.  Waits for both of the context's streams before the old block goes.
 template <typename Tp>
 int ensure_dev(gd_ctx* c, Tp** p, size_t* cap, size_t need, bool keep = false, size_t used = 0)
 {
     if (need <= *cap && *p) return GD_OK;
     size_t ncap = std::max(need, *cap + *cap / 2);
     if (ncap == 0) ncap = 1;
-    Tp* np = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&np), ncap * sizeof(Tp)));
+    DevBuf nb;                                   // (freed again when the copy or a synchronisation fails)
+    if (int r = nb.alloc(c, ncap * sizeof(Tp))) return r;
     if (*p) {
         if (keep && used)
-            HIPCHK(c, hipMemcpyAsync(np, *p, used * sizeof(Tp), hipMemcpyDeviceToDevice,
-                                     c->copy_stream));
+            HIPCHK(c, hipMemcpyAsync(nb.p, *p, used * sizeof(Tp), hipMemcpyDeviceToDevice, c->copy_stream));
         HIPCHK(c, hipStreamSynchronize(c->copy_stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipFree(*p));
     }
-    *p = np;
+    *p = static_cast<Tp*>(nb.release());
     *cap = ncap;
     return GD_OK;
 }
@@ -736,14 +775,6 @@ int ck_tids(gd_ctx* c, const std::vector<int32_t>& tids)
     }
     return flush();
 }
-
-// RAII for the scratch device buffers of gd_ingest_bgzf
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-    template <typename T> T* as() const { return static_cast<T*>(p); }
-};
 
 }  // namespace
 

@@ -297,6 +297,16 @@ class DepthEngine:
                                                C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    @staticmethod
+    def _scale_arg(scale, n_samples: int):
+        """The optional per-sample scale as the C ABI takes it: (the float32 array, which must outlive the call; its address),
+        or (None, None)."""
+        if scale is None:
+            return None, None
+        s = np.ascontiguousarray(scale, np.float32)
+        assert s.shape == (n_samples,)
+        return s, s.ctypes.data
+
     def _emdepth_outputs(self, rows: int, n: int):
         return (np.empty((rows, 9), np.float64), np.empty(rows, np.uint8), np.empty((rows, n), np.uint8),
                 np.empty((rows, n), np.float32))
@@ -316,13 +326,9 @@ class DepthEngine:
         """The same for int64 cells in HBM (depthwed_device's pointer): the depth of a cell is float32(cell), times
         scale[sample] in float32 when a scale is given.  Returns what emdepth returns."""
         lam, it, cn, fc = self._emdepth_outputs(rows, n_samples)
-        s = None
-        if scale is not None:
-            s = np.ascontiguousarray(scale, np.float32)
-            assert s.shape == (n_samples,)
-        self._chk(self._lib.gd_emdepth_cells(self._ctx, C.c_void_p(dptr), rows, n_samples,
-                                             s.ctypes.data if s is not None else None, lam.ctypes.data, it.ctypes.data,
-                                             cn.ctypes.data, fc.ctypes.data))
+        s, s_ptr = self._scale_arg(scale, n_samples)
+        self._chk(self._lib.gd_emdepth_cells(self._ctx, C.c_void_p(dptr), rows, n_samples, s_ptr, lam.ctypes.data,
+                                             it.ctypes.data, cn.ctypes.data, fc.ctypes.data))
         return lam, it, cn, fc
 
     def emdepth_timing(self):
@@ -430,6 +436,18 @@ class DepthEngine:
         self._chk(self._lib.gd_emcnv_end(self._ctx))
         return out
 
+    def _emcnv_run(self, rows: int, n_samples: int, starts, ends, block_rows, cn, add):
+        """gd_emcnv_begin, one add(r0, n_rows, starts, ends, cn) -- the gd_emcnv_add* call of rows r0 .. r0 + n_rows, the
+        last three as addresses, cn's None without a cn matrix -- per block of block_rows rows, then the result."""
+        st, en = self._emcnv_positions(starts, ends, rows)
+        self._chk(self._lib.gd_emcnv_begin(self._ctx, n_samples))
+        step = rows if not block_rows else int(block_rows)
+        for r0 in range(0, rows, max(step, 1)):
+            r1 = min(rows, r0 + step)
+            self._chk(add(r0, r1 - r0, st[r0:r1].ctypes.data, en[r0:r1].ctypes.data,
+                          cn[r0:r1].ctypes.data if cn is not None else None))
+        return self._emcnv_result(cn)
+
     def emdepth_cnvs(self, depths, starts, ends, block_rows=None):
         """emdepth.Cache over a [rows][samples] float32 matrix whose rows span start[r] .. end[r] (uint32), in input
         order: the CNV calls in (emit_row, sample) order.  A dict of sample, psize, emit_row (uint32 [cnvs]), member_off
@@ -439,34 +457,17 @@ class DepthEngine:
         d = np.ascontiguousarray(depths, np.float32)
         assert d.ndim == 2
         rows, n = d.shape
-        st, en = self._emcnv_positions(starts, ends, rows)
-        cn = np.empty((rows, n), np.uint8)
-        self._chk(self._lib.gd_emcnv_begin(self._ctx, n))
-        step = rows if not block_rows else int(block_rows)
-        for r0 in range(0, rows, max(step, 1)):
-            r1 = min(rows, r0 + step)
-            self._chk(self._lib.gd_emcnv_add(self._ctx, d[r0:r1].ctypes.data, r1 - r0, st[r0:r1].ctypes.data,
-                                             en[r0:r1].ctypes.data, cn[r0:r1].ctypes.data))
-        return self._emcnv_result(cn)
+        return self._emcnv_run(rows, n, starts, ends, block_rows, np.empty((rows, n), np.uint8),
+                               lambda r0, k, st, en, cn: self._lib.gd_emcnv_add(self._ctx, d[r0:r0 + k].ctypes.data, k, st, en, cn))
 
     def emdepth_cnvs_cells(self, dptr: int, rows: int, n_samples: int, starts, ends, scale=None, block_rows=None,
                            site_cn=False):
         """The same for int64 cells in HBM (depthwed_device's pointer), scaled as emdepth_cells does.  The per-site copy
         numbers are read back only when site_cn is set (they are the one output of rows x samples bytes)."""
-        st, en = self._emcnv_positions(starts, ends, rows)
-        s = None
-        if scale is not None:
-            s = np.ascontiguousarray(scale, np.float32)
-            assert s.shape == (n_samples,)
-        cn = np.empty((rows, n_samples), np.uint8) if site_cn else None
-        self._chk(self._lib.gd_emcnv_begin(self._ctx, n_samples))
-        step = rows if not block_rows else int(block_rows)
-        for r0 in range(0, rows, max(step, 1)):
-            r1 = min(rows, r0 + step)
-            self._chk(self._lib.gd_emcnv_add_cells(self._ctx, C.c_void_p(dptr + r0 * n_samples * 8), r1 - r0,
-                                                   s.ctypes.data if s is not None else None, st[r0:r1].ctypes.data,
-                                                   en[r0:r1].ctypes.data, cn[r0:r1].ctypes.data if site_cn else None))
-        return self._emcnv_result(cn)
+        s, s_ptr = self._scale_arg(scale, n_samples)
+        return self._emcnv_run(rows, n_samples, starts, ends, block_rows, np.empty((rows, n_samples), np.uint8) if site_cn else None,
+                               lambda r0, k, st, en, cn: self._lib.gd_emcnv_add_cells(
+                                   self._ctx, C.c_void_p(dptr + r0 * n_samples * 8), k, s_ptr, st, en, cn))
 
     # ---- the matrix stays in HBM (DESIGN.md section 3.14): dptr / out_ptr are device addresses ----
     def device_alloc(self, nbytes: int) -> int:
@@ -525,16 +526,9 @@ class DepthEngine:
     def emdepth_cnvs_device(self, dptr: int, rows: int, n_samples: int, starts, ends, block_rows=None, site_cn=False):
         """emdepth_cnvs for a device float32 [rows][n_samples] matrix (each block checked on the device first); site_cn
         and block_rows as in emdepth_cnvs_cells."""
-        st, en = self._emcnv_positions(starts, ends, rows)
-        cn = np.empty((rows, n_samples), np.uint8) if site_cn else None
-        self._chk(self._lib.gd_emcnv_begin(self._ctx, n_samples))
-        step = rows if not block_rows else int(block_rows)
-        for r0 in range(0, rows, max(step, 1)):
-            r1 = min(rows, r0 + step)
-            self._chk(self._lib.gd_emcnv_add_device(self._ctx, C.c_void_p(dptr + r0 * n_samples * 4), r1 - r0,
-                                                    st[r0:r1].ctypes.data, en[r0:r1].ctypes.data,
-                                                    cn[r0:r1].ctypes.data if site_cn else None))
-        return self._emcnv_result(cn)
+        return self._emcnv_run(rows, n_samples, starts, ends, block_rows, np.empty((rows, n_samples), np.uint8) if site_cn else None,
+                               lambda r0, k, st, en, cn: self._lib.gd_emcnv_add_device(
+                                   self._ctx, C.c_void_p(dptr + r0 * n_samples * 4), k, st, en, cn))
 
     def emcnv_timing(self):
         """Seconds since the last gd_emcnv_begin: (upload, emdepth kernel, CNV kernels, read-back)."""
