@@ -5,12 +5,13 @@
 // timing.  The rest of the ABI is in the gd_api_*.inc files included at the end, in this order: records (pinned
 // staging ring + copy stream, records host -> HBM, HBM-resident per-contig record streams), compute (route, launch
 // sequencing, look-back), results (read-back), aux, ingest, covstats, indexcov, indexsplit, crai, devmat, emdepth, emcnv,
-// colselect, chunkdebias, movdebias, comm.
+// colselect, chunkdebias, movdebias, svddebias, comm.
 // Replaces gargs' process.Runner + the samtools child + the callback's parse loop of `goleft depth`
 // (depth/depth.go:392-394, :45, :282-325).
 #include "../../include/goleft_depth.h"
 #include "gd_kernels.hpp"
 #include "gd_matcheck.hpp"
+#include "gd_eigh.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -421,6 +422,7 @@ int gd_kernel_ms(gd_ctx* c, int id, float* ms)
 #include "gd_api_colselect.inc"
 #include "gd_api_chunkdebias.inc"
 #include "gd_api_movdebias.inc"
+#include "gd_api_svddebias.inc"
 #include "gd_api_comm.inc"
 
 }  // extern "C"

@@ -268,6 +268,7 @@ struct gd_ctx {
                                                                // the median kernel alone when GOLEFT_CHUNKDEBIAS_SPLIT is set (gd_api_chunkdebias.inc)
     double md_secs[4] = {0, 0, 0, 0};                          // gd_moving_debias*: sort, upload, kernel, read-back of the last call (gd_api_movdebias.inc)
     int64_t md_segment = 0;                                    // GD_OPT_MOVDEBIAS_SEGMENT: sorted rows a workgroup owns (0: by the window)
+    double sv_secs[5] = {0, 0, 0, 0, 0};                       // gd_svd_debias*: upload, statistics + Gram, eigenpairs (host), projection, read-back of the last call (gd_api_svddebias.inc)
     double em_secs[3] = {0, 0, 0};                             // gd_emdepth*: upload, kernel, read-back of the last call (gd_api_emdepth.inc)
     uint8_t* h_walk = nullptr; size_t cap_walk = 0;            // gd_ingest_decode, gd_covstats_decode: per-segment tables of the record walk (page-locked host memory
                                                                // the walk kernels read and write over the link: no copy command)

@@ -35,6 +35,18 @@
 // flag debiases in-process and then normalises, in the reference's order (dcnv.go:331-337): the quotients are near 1 and
 // EMDepth stops on absolute thresholds, so they go back to depth scale -- the level is --level or the middle sample median
 // of the matrix AS READ, the factors T / med'[s] over the medians of the debiased matrix (this project's definition).
+//
+//   goleft-depth debias --svd PCT [--zscore] matrix.bed[.gz]
+//   goleft-depth emdepth --svd PCT [GC flags] [--level L] [--cnvs FILE] matrix.bed[.gz]
+//
+// `debias --svd` removes the bias nobody has a covariate for: dcnv's SVD debiaser (debiaser.go:173-200; gd_svd_debias,
+// DESIGN.md section 3.16) zeroes the leading singular values of the matrix whose share of the spectrum exceeds PCT (the
+// reference's MinVariancePct), at most 15; --zscore flanks it with the reference's z-score scaler (scalers.go:24-56) --
+// without it the first component is the mean depth and cells may come out negative.  One stderr line carries the removed
+// shares as the reference logs them.  Not with a covariate or its windows: chain the debiasers by a pipe.  `emdepth --svd`
+// runs it in-process, always z-scored (emdepth refuses negative cells), after the GC debias when there is one and before
+// --normalize, which it implies: the output is what `debias --svd PCT --zscore | emdepth --normalize` writes.  The spectrum
+// needs every row, so this step is never tiled by GOLEFT_EMDEPTH_ROWS.
 #include <zlib.h>
 
 #include <algorithm>
@@ -59,6 +71,8 @@ struct EArgs {
     bool normalize = false, has_level = false, has_window = false, has_moving = false;
     double level = 0, window = 0.01;
     int moving = 0;                              // --moving / --gc-moving: the GeneralDebiaser's window, in rows
+    bool has_svd = false, zscore = false;        // --svd PCT [--zscore]: the SVD debiaser's MinVariancePct, its scaler
+    double svd = 0;
     bool gc() const { return !gc_values.empty() || !gc_fasta.empty(); }
 };
 
@@ -74,6 +88,7 @@ void usage_scales(FILE* f)
 void usage_debias(FILE* f)
 {
     fputs("usage: debias (--gc-values FILE | --fasta REF.fa) [--window W | --moving ROWS] MATRIX\n"
+          "       debias --svd PCT [--zscore] MATRIX\n"
           "  MATRIX  a depthwed matrix (#chrom start end samples... and its rows), plain or gzipped\n"
           "  writes the matrix with every cell divided by its sample's median over the rows of similar covariate (dcnv's\n"
           "  ChunkDebiaser): the rows in covariate order are cut where a value exceeds the chunk's first by more than W\n"
@@ -81,13 +96,18 @@ void usage_debias(FILE* f)
           "  --fasta  take the GC fraction of [max(start, 250) - 250, end) of REF.fa (needs REF.fa.fai) instead\n"
           "  --window  W, a finite number > 0 (default 0.01)\n"
           "  --moving  divide by a moving median over ROWS rows in covariate order instead (dcnv's GeneralDebiaser; dcnv runs\n"
-          "            it with 9): an odd number, 1 .. 255.  Not with --window\n", f);
+          "            it with 9): an odd number, 1 .. 255.  Not with --window\n"
+          "  --svd  instead of a covariate: zero the leading singular values of the matrix whose share of the spectrum exceeds\n"
+          "         PCT per cent (a finite number >= 0), at most 15 (dcnv's SVD debiaser); 2 .. 1024 samples.  The removed shares\n"
+          "         go to stderr.  Not with the flags above: chain the debiasers by a pipe\n"
+          "  --zscore  with --svd: z-score every row first and carry it back after (max(0, z sd + mean)); without it the first\n"
+          "            component is the mean depth and cells may come out negative\n", f);
 }
 
 void usage(FILE* f)
 {
     fputs("usage: emdepth [--scales FILE | --normalize [--level L] | (--gc-values FILE | --gc-fasta REF.fa) [--gc-window W | --gc-moving ROWS] [--level L]]\n"
-          "               [--cnvs FILE] MATRIX\n"
+          "               [--svd PCT] [--cnvs FILE] MATRIX\n"
           "  MATRIX  a depthwed matrix (#chrom start end samples... and its rows), plain or gzipped, already normalised\n"
           "  --scales  a file of one factor per line, in column order: every depth is multiplied by its sample's factor\n"
           "  --normalize  compute those factors here, as `scales` does: each sample's 0.65 quantile of its non-zero depths\n"
@@ -95,6 +115,7 @@ void usage(FILE* f)
           "  --gc-values, --gc-fasta, --gc-window, --gc-moving  first remove the bias of a per-row covariate as `debias` does (its\n"
           "               --gc-values, --fasta, --window, --moving), then --normalize: to --level, or to the middle one of the\n"
           "               sample quantiles of the matrix as read\n"
+          "  --svd  after the GC debias, if any: `debias --svd PCT --zscore`, then --normalize (to --level or the middle sample quantile)\n"
           "  --cnvs  write the CNV calls of every sample (emdepth.Cache) to FILE: sample, index, psize, sites, positions, cn, depth, log2fc\n", f);
 }
 
@@ -119,6 +140,7 @@ int parse_args(int argc, const char* const* argv, EArgs* a, int cmd)
         if (arg == "-h" || arg == "--help") { usage(stdout); return 1; }
         if (arg == "--") { for (++i; i < argc; ++i) pos.push_back(argv[i]); break; }
         if (arg == "--normalize" && cmd == CMD_EMDEPTH) { a->normalize = true; continue; }
+        if (arg == "--zscore" && cmd == CMD_DEBIAS) { a->zscore = true; continue; }
         if (arg.size() > 1 && arg[0] == '-') {
             std::string key = arg, val;
             bool has_val = false;
@@ -126,8 +148,8 @@ int parse_args(int argc, const char* const* argv, EArgs* a, int cmd)
             if (eq != std::string::npos) { key = arg.substr(0, eq); val = arg.substr(eq + 1); has_val = true; }
             const bool gc_key = key == "--gc-values" || key == fasta_key || key == window_key || key == moving_key;
             const bool known = cmd == CMD_SCALES ? key == "--level"
-                             : cmd == CMD_DEBIAS ? gc_key
-                                                 : key == "--level" || key == "--scales" || key == "--cnvs" || gc_key;
+                             : cmd == CMD_DEBIAS ? gc_key || key == "--svd"
+                                                 : key == "--level" || key == "--scales" || key == "--cnvs" || gc_key || key == "--svd";
             if (!known) {
                 fprintf(stderr, "error: unknown argument %s\n", arg.c_str());
                 usage(stderr);
@@ -148,6 +170,17 @@ int parse_args(int argc, const char* const* argv, EArgs* a, int cmd)
                 }
                 a->moving = (int)v;
                 a->has_moving = true;
+                continue;
+            }
+            if (key == "--svd") {
+                char* end = nullptr;
+                a->svd = strtod(val.c_str(), &end);
+                if (end != val.c_str() + val.size() || !std::isfinite(a->svd) || !(a->svd >= 0)) {
+                    fprintf(stderr, "error: --svd must be a finite share in per cent >= 0, not '%s'\n", val.c_str());
+                    usage(stderr);
+                    return -1;
+                }
+                a->has_svd = true;
                 continue;
             }
             if (key == "--level" || key == window_key) {
@@ -175,7 +208,22 @@ int parse_args(int argc, const char* const* argv, EArgs* a, int cmd)
         usage(stderr);
         return -1;
     }
-    if (cmd == CMD_DEBIAS && !a->gc()) {
+    if (cmd == CMD_DEBIAS && a->has_svd && (a->gc() || a->has_window || a->has_moving)) {
+        fprintf(stderr, "error: --svd takes no covariate and no window: run the two debiasers one after the other, by a pipe\n");
+        usage(stderr);
+        return -2;                               // (exit code 1: the flags are each valid)
+    }
+    if (a->zscore && !a->has_svd) {
+        fprintf(stderr, "error: --zscore is the scaler of --svd: it needs --svd PCT\n");
+        usage(stderr);
+        return -1;
+    }
+    if (a->has_svd && !a->scales.empty()) {
+        fprintf(stderr, "error: --svd normalises after the debiasing, as --normalize does: --scales cannot be given with it\n");
+        usage(stderr);
+        return -1;
+    }
+    if (cmd == CMD_DEBIAS && !a->gc() && !a->has_svd) {
         fprintf(stderr, "error: the covariate is required: --gc-values FILE or --fasta REF.fa\n");
         usage(stderr);
         return -1;
@@ -200,7 +248,7 @@ int parse_args(int argc, const char* const* argv, EArgs* a, int cmd)
         usage(stderr);
         return -2;                               // (exit code 1: the two flags are each valid)
     }
-    if (a->gc() && cmd == CMD_EMDEPTH) a->normalize = true;
+    if ((a->gc() || a->has_svd) && cmd == CMD_EMDEPTH) a->normalize = true;
     if (a->has_level && !a->normalize && cmd == CMD_EMDEPTH) {
         fprintf(stderr, "error: --level sets the level --normalize carries the samples to: it needs --normalize\n");
         usage(stderr);
@@ -660,6 +708,37 @@ int debias_matrix(const char* prog, gd_ctx* ctx, const EArgs& a, Matrix* m, std:
     return 0;
 }
 
+// gd_svd_debias over the whole matrix: m's depths become the result.  The stderr line is the reference's log line
+// (debiaser.go:186-192: the shares of the removed singular values, %.2f), then their number.  secs: gd_svd_debias_timing's
+// five values, then n.
+int svd_matrix(const char* prog, gd_ctx* ctx, const EArgs& a, bool zscore, Matrix* m, double* secs)
+{
+    const size_t N = m->n, rows = m->where.size();
+    if (rows == 0) { fprintf(stderr, "%s: %s has no rows\n", prog, a.input.c_str()); return 1; }
+    std::vector<float> out(rows * N);
+    std::vector<double> s(std::min(rows, N));
+    int n = 0;
+    const int rc = gd_svd_debias(ctx, m->depths.data(), rows, (int)N, a.svd, zscore ? 1 : 0, out.data(), s.data(), &n);
+    if (rc != GD_OK) { fprintf(stderr, "%s: gd_svd_debias: %s (%s)\n", prog, gd_strerror(rc), gd_last_error(ctx)); return 1; }
+    (void)gd_svd_debias_timing(ctx, secs, 5);
+    secs[5] = (double)n;
+    double sum = 0;
+    for (double v : s) sum += v;
+    std::string line = "variance:";
+    char buf[64];
+    for (int k = 0; k < n; ++k) { snprintf(buf, sizeof buf, " %.2f", 100.0 * s[(size_t)k] / sum); line += buf; }
+    fprintf(stderr, "%s; n = %d\n", line.c_str(), n);
+    m->depths.swap(out);
+    return 0;
+}
+
+void print_svd_timing(size_t rows, size_t N, const double* secs)
+{
+    fprintf(stderr, "{\"rows\": %zu, \"samples\": %zu, \"svd_upload_s\": %.4f, \"svd_gram_s\": %.4f, \"svd_eigen_s\": %.4f, "
+                    "\"svd_project_s\": %.4f, \"svd_readback_s\": %.4f, \"svd_removed\": %d}\n",
+            rows, N, secs[0], secs[1], secs[2], secs[3], secs[4], (int)secs[5]);
+}
+
 void print_debias_timing(size_t rows, size_t N, const double* secs)
 {
     fprintf(stderr, "{\"rows\": %zu, \"samples\": %zu, \"debias_sort_s\": %.4f, \"debias_upload_s\": %.4f, \"debias_kernels_s\": %.4f, "
@@ -675,7 +754,7 @@ int run_debias(const EArgs& a, FILE* out)
     if (int rc = open_device("debias", &ctx)) return rc;
     std::vector<double> vals;
     double secs[7] = {0, 0, 0, 0, 0, 0, 0};
-    const int rc = debias_matrix("debias", ctx, a, &m, &vals, secs);
+    const int rc = a.has_svd ? svd_matrix("debias", ctx, a, a.zscore, &m, secs) : debias_matrix("debias", ctx, a, &m, &vals, secs);
     gd_destroy(ctx);
     if (rc) return rc;
     const size_t N = m.n, rows = m.where.size();
@@ -690,7 +769,7 @@ int run_debias(const EArgs& a, FILE* out)
         o += '\n';
     }
     if (fwrite(o.data(), 1, o.size(), out) != o.size() || fflush(out) != 0) { fprintf(stderr, "debias: error writing the rows\n"); return 1; }
-    if (getenv("GOLEFT_EMDEPTH_TIMING")) print_debias_timing(rows, N, secs);
+    if (getenv("GOLEFT_EMDEPTH_TIMING")) a.has_svd ? print_svd_timing(rows, N, secs) : print_debias_timing(rows, N, secs);
     return 0;
 }
 
@@ -734,7 +813,7 @@ int run(const EArgs& a, FILE* out)
     }
     gd_ctx* ctx = nullptr;
     if (int rc = open_device("emdepth", &ctx)) return rc;
-    double med_secs[4] = {0, 0, 0, 0}, gc_secs[7] = {0, 0, 0, 0, 0, 0, 0};
+    double med_secs[4] = {0, 0, 0, 0}, gc_secs[7] = {0, 0, 0, 0, 0, 0, 0}, svd_secs[6] = {0, 0, 0, 0, 0, 0};
     EArgs norm = a;                              // what the normalisation after a debiasing is asked for
     if (a.gc()) {
         // debias, then normalise (dcnv.go:331-337).  The quotients are near 1; the level that carries them back to depth
@@ -750,6 +829,8 @@ int run(const EArgs& a, FILE* out)
         if (rc == 0) rc = debias_matrix("emdepth", ctx, a, &m, &vals, gc_secs);
         if (rc) { gd_destroy(ctx); return rc; }
     }
+    if (a.has_svd)                               // always z-scored: the rows below take no negative cell
+        if (int rc = svd_matrix("emdepth", ctx, a, true, &m, svd_secs)) { gd_destroy(ctx); return rc; }
     if (a.normalize) {
         // the matrix goes up once for the medians and again, scaled, in its blocks
         std::vector<float> scale, med;
@@ -806,6 +887,7 @@ int run(const EArgs& a, FILE* out)
         t_cnv_write = now_s() - t0;
     }
     if (timing && a.gc()) print_debias_timing(rows, N, gc_secs);
+    if (timing && a.has_svd) print_svd_timing(rows, N, svd_secs);
     if (timing && a.normalize)
         fprintf(stderr, "{\"rows\": %zu, \"samples\": %zu, \"medians_upload_s\": %.4f, \"medians_kernels_s\": %.4f, "
                         "\"medians_readback_s\": %.4f, \"medians_passes\": %d}\n",

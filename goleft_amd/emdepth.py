@@ -1,6 +1,6 @@
 """`emdepth`, `scales` and `debias` entry points: copy numbers per site of a depthwed matrix, goleft's emdepth.EMDepth run
-on the device, the per-sample factors that normalise such a matrix first, and dcnv's ChunkDebiaser or GeneralDebiaser,
-which free it of GC bias before that (the matrix reading, the blocks of rows, the output
+on the device, the per-sample factors that normalise such a matrix first, dcnv's ChunkDebiaser or GeneralDebiaser,
+which free it of GC bias before that, and its SVD debiaser for the bias without a covariate (the matrix reading, the blocks of rows, the output
 rows and the exit codes live in the C++ host twin)."""
 from __future__ import annotations
 
@@ -21,7 +21,8 @@ def Main(argv, out_path=None) -> int:
     """argv: the arguments after the program name, e.g. ["--scales", "scales.txt", "matrix.bed.gz"] or
     ["--normalize", "--level", "30", "--cnvs", "cnvs.tsv", "matrix.bed"] or ["--gc-values", "gc.txt", "matrix.bed"]: a
     depthwed matrix (`#chrom start end samples...` and its rows), plain or gzipped, already normalised unless --normalize
-    or a GC flag (--gc-values FILE | --gc-fasta REF.fa, [--gc-window W | --gc-moving ROWS]: debias as Debias does, then normalise) is given.
+    or a GC flag (--gc-values FILE | --gc-fasta REF.fa, [--gc-window W | --gc-moving ROWS]: debias as Debias does, then normalise) is given;
+    ["--svd", "2"] runs `debias --svd 2 --zscore` after that and before the normalisation.
     The rows go to out_path (stdout when None); returns the exit code."""
     lib = _hostlib.load()
     n, arr = _argv(b"emdepth", argv)
@@ -40,7 +41,9 @@ def Debias(argv, out_path=None) -> int:
     """`goleft-depth debias`: argv e.g. ["--gc-values", "gc.txt", "--window", "0.02", "matrix.bed.gz"] or ["--fasta",
     "ref.fa", "matrix.bed"].  The matrix with every cell divided by its sample's median over the rows of similar covariate
     (dcnv's ChunkDebiaser; with ["--moving", "9"] in place of --window by the moving median of dcnv's GeneralDebiaser) goes
-    to out_path (stdout when None); returns the exit code."""
+    to out_path (stdout when None); returns the exit code.  ["--svd", "2", "--zscore", "matrix.bed"] takes no covariate:
+    dcnv's SVD debiaser zeroes the leading singular values whose share of the spectrum exceeds 2 per cent, at most 15, between
+    the z-score scaler's two halves; the removed shares go to stderr."""
     lib = _hostlib.load()
     n, arr = _argv(b"debias", argv)
     return int(lib.gdh_debias_run(n, arr, out_path.encode() if out_path else None))
@@ -79,11 +82,14 @@ def _factors(med, nonzero, T):
 
 
 def cohort_cnvs(eng, dptr, rows, n_samples, starts, ends, vals=None, window=None, level=None, block_rows=None,
-                site_cn=False, moving=None):
+                site_cn=False, moving=None, svd=None):
     """From DepthEngine.depthwed_device's int64 cells (dptr, rows) to CNV calls without the matrix leaving HBM: the
     resident twin of `goleft-depth emdepth --normalize --cnvs` (vals None) and of `emdepth --gc-values --cnvs` (vals: the
     covariate of every row, window: --gc-window, 0.01 when None; or moving: --gc-moving, the odd window of dcnv's
-    GeneralDebiaser in place of the ChunkDebiaser -- giving both is a ValueError).  level: --level; None is the middle sample median of the matrix as
+    GeneralDebiaser in place of the ChunkDebiaser -- giving both is a ValueError).  svd: --svd, the share in per cent above
+    which dcnv's SVD debiaser zeroes a leading singular value, always z-scored, after the GC debias when vals is given and
+    before the normalisation; with svd and without vals the level None is the middle sample median of the debiased matrix,
+    as `debias --svd PCT --zscore | emdepth --normalize` has it.  level: --level; None is the middle sample median of the matrix as
     read.  Returns (factors float32 [samples], level, what DepthEngine.emdepth_cnvs* returns); the per-site copy numbers
     are read back only when site_cn is set, everything else that comes back is O(samples + calls).
 
@@ -98,22 +104,30 @@ def cohort_cnvs(eng, dptr, rows, n_samples, starts, ends, vals=None, window=None
     if moving is not None and vals is None:
         raise ValueError("cohort_cnvs: moving needs the covariate of every row")
     T = None if level is None else float(level)
-    if T is None or vals is None:
+    if (T is None or vals is None) and not (svd is not None and vals is None):
         med, nz = eng.sample_medians_cells(dptr, rows, n_samples)
         # (float)median: the rounding is monotone, so this is the median of the float32 matrix the command line reads
         med = med.astype(np.float32)
         if T is None:
             T = _factors(med, nz, None)
-    if vals is None:
+    if vals is None and svd is None:
         f = _factors(med, nz, T)
         return f, T, eng.emdepth_cnvs_cells(dptr, rows, n_samples, starts, ends, scale=f, block_rows=block_rows, site_cn=site_cn)
     out = eng.device_alloc(max(rows * n_samples * 4, 1))
     try:
-        if moving is not None:
-            eng.moving_debias_cells(dptr, rows, n_samples, vals, moving, out)
+        if vals is None:
+            eng.svd_debias_cells(dptr, rows, n_samples, svd, True, out)
         else:
-            eng.chunk_debias_cells(dptr, rows, n_samples, vals, 0.01 if window is None else window, out)
-        f = _factors(*eng.sample_medians_device(out, rows, n_samples), T)
+            if moving is not None:
+                eng.moving_debias_cells(dptr, rows, n_samples, vals, moving, out)
+            else:
+                eng.chunk_debias_cells(dptr, rows, n_samples, vals, 0.01 if window is None else window, out)
+            if svd is not None:
+                eng.svd_debias_device(out, rows, n_samples, svd, True, out)
+        med, nz = eng.sample_medians_device(out, rows, n_samples)
+        if vals is None and level is None:
+            T = _factors(med, nz, None)
+        f = _factors(med, nz, T)
         eng.scale_device(out, rows, n_samples, f)
         return f, T, eng.emdepth_cnvs_device(out, rows, n_samples, starts, ends, block_rows=block_rows, site_cn=site_cn)
     finally:

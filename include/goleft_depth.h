@@ -39,7 +39,7 @@ extern "C" {
 
 /* GD_ABI_VERSION changes when an existing entry point or structure changes; GD_ABI_REVISION counts the releases that only
  * ADDED entry points since then (revision 1: gd_indexcov_*; 2: gd_indexsplit_*; 3: gd_crai_sizes).  A caller built against (15, r) runs on any (15, r' >= r).
- * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, gd_sample_medians*, gd_chunk_debias*, gd_device_scale, the *_device entries and gd_moving_debias*, were added without a revision; look them up by symbol.
+ * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, gd_sample_medians*, gd_chunk_debias*, gd_device_scale, the *_device entries, gd_moving_debias* and gd_svd_debias*, were added without a revision; look them up by symbol.
  * Why indexcov did not become version 16: nothing that existed changed, so callers of ABI 15 need not be turned away, and
  * tests/test_host_cpu.py holds gd_abi_version() to 15 until something does change. */
 #define GD_ABI_VERSION 15
@@ -801,6 +801,38 @@ int gd_moving_debias(gd_ctx* ctx, const float* depths, size_t n_rows, int n_samp
 int gd_moving_debias_cells(gd_ctx* ctx, const int64_t* d_cells, size_t n_rows, int n_samples, const double* vals /* [n_rows] */,
                            int window, float* d_out /* DEVICE [n_rows][n_samples] */);
 int gd_moving_debias_timing(gd_ctx* ctx, double* out, size_t n);
+/* ---- SVD debias: dcnv's SVD debiaser flanked by its z-score scaler ----
+ * Added without a revision; look them up by symbol.  depths is [n_rows][n_samples] float32, every cell finite and >= 0,
+ * taken to float64.  With zscore every row i gets m_i = sum / N and sd_i, the sample standard deviation (N - 1, two-pass),
+ * and z_ij = (a_ij - m_i) / sd_i -- 0 for the whole row when sd_i == 0 (this library's choice: the reference divides by 0
+ * there and its factorisation panics); without, Z = A.  s is the singular values of Z, descending, min(n_rows, n_samples) of
+ * them, from the eigenvalues of the float64 Gram matrix Z^T Z the device sums (s = sqrt(max(w, 0)): values below about
+ * 1e-8 of s[0] are not resolved).  n counts the leading values with 100 s[n] / sum(s) > min_variance_pct, at most
+ * min(15, n_rows, n_samples) (the reference stops at 15 and reads past the end of fewer; an all-zero Z gives n = 0).
+ * Z' = Z - (Z V_n) V_n^T with V_n the first n right singular vectors -- the reference's U Sigma' V^T -- and
+ * out = (float)z', or (float)max(0, z' sd_i + m_i) with zscore (ZScore.UnScale): one rounding to float32.  s (or NULL) gets
+ * the spectrum, n_removed (or NULL) n.  Two calls on the same input give the same bytes, and the three forms give the same
+ * bytes for the same float32 matrix.  2 <= n_samples <= 1024 (the eigenpairs are O(n_samples^3) host work inside the call:
+ * about a second at 1024), 1 <= n_rows <= 2^31 - 1, min_variance_pct finite and >= 0: GD_E_RANGE otherwise; a cell that is
+ * not finite and >= 0: GD_E_INVALID, gd_last_error naming its row and sample.  All refusals leave the context usable.
+ * While it runs the call holds 32 KB per 1024 rows and pair of 64-sample tiles on the device.
+ *   gd_svd_debias_cells    the same for d_cells, DEVICE int64 [n_rows][n_samples] as gd_depthwed_device leaves them: d_out,
+ *                          a caller-owned DEVICE float32 matrix of the same shape, receives what gd_svd_debias gives for
+ *                          (float)cell.  d_out overlapping d_cells is GD_E_INVALID before anything runs; a negative cell is
+ *                          GD_E_INVALID with d_out unspecified.
+ *   gd_svd_debias_device   the same for a DEVICE float32 matrix, checked on the device first; d_out may be d_depths itself
+ *                          (every row is read before it is written), any other overlap is GD_E_INVALID.
+ *   gd_svd_debias_timing   (measurement only) of the last call: seconds of upload (cells: conversion and check; device:
+ *                          check), row statistics + Gram matrix and its read-back, eigenpairs on the host, projection,
+ *                          read-back.  Fills min(n, 5) values. */
+int gd_svd_debias(gd_ctx* ctx, const float* depths, size_t n_rows, int n_samples, double min_variance_pct, int zscore,
+                  float* out /* [n_rows][n_samples] */, double* s /* [min(n_rows, n_samples)] or NULL */,
+                  int* n_removed /* or NULL */);
+int gd_svd_debias_cells(gd_ctx* ctx, const int64_t* d_cells, size_t n_rows, int n_samples, double min_variance_pct, int zscore,
+                        float* d_out /* DEVICE [n_rows][n_samples] */, double* s, int* n_removed);
+int gd_svd_debias_device(gd_ctx* ctx, const float* d_depths, size_t n_rows, int n_samples, double min_variance_pct, int zscore,
+                         float* d_out /* DEVICE [n_rows][n_samples]; may equal d_depths */, double* s, int* n_removed);
+int gd_svd_debias_timing(gd_ctx* ctx, double* out, size_t n);
 int gd_ingest_abort(gd_ctx* ctx);
 /* Page-locked host memory for the byte range handed to gd_ingest_bgzf (read the file
  * straight into it: the H2D copy then runs at PCIe speed instead of through a bounce
