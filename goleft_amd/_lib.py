@@ -145,6 +145,9 @@ SYMBOLS = {
     "gd_svd_debias_cells": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_double, C.c_int, _P, _P, _P]),
     "gd_svd_debias_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_double, C.c_int, _P, _P, _P]),
     "gd_svd_debias_timing": (C.c_int, [_P, _P, C.c_size_t]),
+    "gd_svd_debias_scaled": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_double, C.c_int, _P, _P, _P, _P]),
+    "gd_svd_debias_scaled_cells": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_double, C.c_int, _P, _P, _P, _P]),
+    "gd_svd_debias_scaled_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_double, C.c_int, _P, _P, _P, _P]),
     "gd_device_scale": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P]),
     "gd_sample_medians_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P]),
     "gd_emdepth_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P, _P, _P]),

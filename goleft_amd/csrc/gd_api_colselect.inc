@@ -14,9 +14,11 @@ static int cs_check(gd_ctx* c, size_t n_rows, int n_samples)
 }
 
 // d_in: the matrix on the device (float32 when !cells, int64 otherwise).  prefix_out: host [n_samples], the answers as
-// keys (a float's bits or the cell); nonzero_out: host [n_samples] or nullptr.
+// keys (a float's bits or the cell); nonzero_out: host [n_samples] or nullptr.  mid (float32 only): the rank is rows / 2
+// over all cells, the centre of dcnv's Log2 scaler, in place of SampleMedians'; d_prefix_out: device [n_samples] or nullptr,
+// the keys once more, for the kernels that follow on the stream.
 static int cs_run(gd_ctx* c, bool cells, const void* d_in, size_t n_rows, int n_samples, uint64_t* prefix_out,
-                  uint64_t* nonzero_out)
+                  uint64_t* nonzero_out, bool mid = false, uint64_t* d_prefix_out = nullptr)
 {
     const size_t N = (size_t)n_samples;
     DevBuf counts, zeros, prefix, rem, rank, nonzero, flags;
@@ -53,7 +55,8 @@ static int cs_run(gd_ctx* c, bool cells, const void* d_in, size_t n_rows, int n_
         passes = (int)seen[0];                  // the longest answer, in bytes
     } else {
         hipLaunchKernelGGL((gd::gd_colselect_hist_kernel<float, true>), grid, wg, 0, c->stream, j);
-        hipLaunchKernelGGL((gd::gd_colselect_pick_kernel<gd::CS_PICK_FLOAT_FIRST>), pgrid, pwg, 0, c->stream, j);
+        if (mid) hipLaunchKernelGGL(gd::gd_colmid_pick_kernel, pgrid, pwg, 0, c->stream, j);
+        else hipLaunchKernelGGL((gd::gd_colselect_pick_kernel<gd::CS_PICK_FLOAT_FIRST>), pgrid, pwg, 0, c->stream, j);
     }
     for (int p = 0; p < passes; ++p) {
         if (cells) hipLaunchKernelGGL((gd::gd_colselect_hist_kernel<int64_t, false>), grid, wg, 0, c->stream, j);
@@ -61,6 +64,7 @@ static int cs_run(gd_ctx* c, bool cells, const void* d_in, size_t n_rows, int n_
         hipLaunchKernelGGL((gd::gd_colselect_pick_kernel<gd::CS_PICK_DIGIT>), pgrid, pwg, 0, c->stream, j);
     }
     HIPCHK(c, hipGetLastError());
+    if (d_prefix_out) HIPCHK(c, hipMemcpyAsync(d_prefix_out, prefix.p, N * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->sm_secs[1] = ing_now() - t0;
     c->sm_passes = 1 + passes;

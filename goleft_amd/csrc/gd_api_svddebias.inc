@@ -3,7 +3,8 @@
 // the samples x samples Gram matrix, the spectrum and the cut are host work inside the call (gd_eigh.hpp).  The three forms
 // run the same kernels on the same float32 bits: the host form on an upload of its own, the cells form on d_out once
 // gd_devmat.hpp's conversion has filled it, the device form from d_depths into d_out (which may be d_depths).  Nothing is
-// kept between calls but the timings.
+// kept between calls but the timings.  The gd_svd_debias_scaled* entries name the scaler (none, z-score, or dcnv's Log2
+// scaler: gd_svdlog2.hpp, DESIGN.md section 3.17) and return the centre cells; the older three forward to them.
 
 namespace {
 
@@ -17,19 +18,35 @@ static int sv_check(gd_ctx* c, size_t n_rows, int n_samples, double pct)
     return GD_OK;
 }
 
-// After the checks: d_src (checked, on the device) to d_dst.  s and n_removed may be null.
-static int sv_run(gd_ctx* c, const float* d_src, float* d_dst, size_t n_rows, int n_samples, double pct, int zscore, double* s,
-                  int* n_removed)
+static int sv_scaler(int zscore) { return zscore ? GD_SVD_SCALER_ZSCORE : GD_SVD_SCALER_NONE; }
+
+static int sv_check_scaler(gd_ctx* c, int scaler)
+{
+    if (scaler != GD_SVD_SCALER_NONE && scaler != GD_SVD_SCALER_ZSCORE && scaler != GD_SVD_SCALER_LOG2)
+        return fail(c, GD_E_RANGE, "svd debias: the scaler is 0 (none), 1 (z-score) or 2 (log2), not %d", scaler);
+    return GD_OK;
+}
+
+// After the checks: d_src (checked, on the device) to d_dst.  s, n_removed and centre_cells may be null; scaler is a
+// GD_SVD_SCALER_*.  With the log2 scaler gd_colselect.hpp's select finds the centre cell of every sample first, and
+// gd_svdlog2.hpp's kernels take the place of the row statistics, the Gram kernel and the projection.
+static int sv_run(gd_ctx* c, const float* d_src, float* d_dst, size_t n_rows, int n_samples, double pct, int scaler, double* s,
+                  int* n_removed, float* centre_cells)
 {
     const size_t N = (size_t)n_samples;
     const int T = (n_samples + gd::SV_TILE - 1) / gd::SV_TILE;
     const size_t pairs = (size_t)T * (size_t)(T + 1) / 2;
     const size_t slabs = (n_rows + gd::SV_SLAB - 1) / gd::SV_SLAB;
     const unsigned row_grid = (unsigned)std::min<size_t>((n_rows + 3) / 4, (size_t)gd::SV_MAX_GRID);
+    const bool zscore = scaler == GD_SVD_SCALER_ZSCORE, log2s = scaler == GD_SVD_SCALER_LOG2;
 
-    DevBuf d_stats, d_part, d_gram, d_vt;
+    DevBuf d_stats, d_part, d_gram, d_vt, d_keys, d_centre;
     const double t1 = ing_now();
     if (zscore) if (int r = d_stats.alloc(c, n_rows * 2 * sizeof(double))) return r;
+    if (log2s) {
+        if (int r = d_keys.alloc(c, N * sizeof(uint64_t))) return r;
+        if (int r = d_centre.alloc(c, N * sizeof(double))) return r;
+    }
     if (int r = d_part.alloc(c, pairs * slabs * (size_t)(gd::SV_TILE * gd::SV_TILE) * sizeof(double))) return r;
     if (int r = d_gram.alloc(c, N * N * sizeof(double))) return r;
     if (int r = d_vt.alloc(c, (size_t)gd::SV_MAX_K * N * sizeof(double))) return r;
@@ -38,8 +55,25 @@ static int sv_run(gd_ctx* c, const float* d_src, float* d_dst, size_t n_rows, in
     j.cells = d_src; j.out = d_dst; j.n_rows = (int64_t)n_rows; j.n = n_samples; j.zscore = zscore ? 1 : 0;
     j.stats = d_stats.as<double>(); j.part = d_part.as<double>(); j.gram = d_gram.as<double>(); j.vt = d_vt.as<const double>();
     j.slabs = (int32_t)slabs;
-    if (zscore) hipLaunchKernelGGL(gd::gd_svd_rowstats_kernel, dim3(row_grid), dim3(gd::SV_WG), 0, c->stream, j);
-    hipLaunchKernelGGL(gd::gd_svd_gram_kernel, dim3((unsigned)slabs, (unsigned)pairs), dim3(gd::SV_WG), 0, c->stream, j);
+    gd::SlJob l{};
+    l.cells = d_src; l.out = d_dst; l.n_rows = (int64_t)n_rows; l.n = n_samples; l.slabs = (int32_t)slabs;
+    l.keys = d_keys.as<const uint64_t>(); l.centre = d_centre.as<double>(); l.part = d_part.as<double>(); l.vt = d_vt.as<const double>();
+    std::vector<uint64_t> keys(log2s ? N : 0);
+    const dim3 ggrid((unsigned)slabs, (unsigned)pairs), gwg(gd::SV_WG);
+    if (log2s) {
+        // the select is gd_sample_medians' with another rank; the seconds of the last gd_sample_medians* call stay its own
+        double sm[3] = {c->sm_secs[0], c->sm_secs[1], c->sm_secs[2]};
+        const int sm_passes = c->sm_passes;
+        const int r = cs_run(c, false, d_src, n_rows, n_samples, keys.data(), nullptr, true, d_keys.as<uint64_t>());
+        std::copy(sm, sm + 3, c->sm_secs);
+        c->sm_passes = sm_passes;
+        if (r) return r;
+        hipLaunchKernelGGL(gd::gd_svl_centre_kernel, dim3((unsigned)((N + gd::SV_WG - 1) / gd::SV_WG)), gwg, 0, c->stream, l);
+        hipLaunchKernelGGL(gd::gd_svl_gram_kernel, ggrid, gwg, 0, c->stream, l);
+    } else {
+        if (zscore) hipLaunchKernelGGL(gd::gd_svd_rowstats_kernel, dim3(row_grid), gwg, 0, c->stream, j);
+        hipLaunchKernelGGL(gd::gd_svd_gram_kernel, ggrid, gwg, 0, c->stream, j);
+    }
     hipLaunchKernelGGL(gd::gd_svd_gram_sum_kernel, dim3(gd::SV_TILE * gd::SV_TILE / gd::SV_WG, (unsigned)pairs), dim3(gd::SV_WG), 0,
                        c->stream, j);
     HIPCHK(c, hipGetLastError());
@@ -67,10 +101,16 @@ static int sv_run(gd_ctx* c, const float* d_src, float* d_dst, size_t n_rows, in
 
     const double t3 = ing_now();
     if (n) HIPCHK(c, hipMemcpyAsync(d_vt.p, vt.data(), n * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    j.n_removed = (int32_t)n;
+    j.n_removed = l.n_removed = (int32_t)n;
     const int nv = (n_samples + 63) / 64;
     const dim3 pgrid(row_grid), pwg(gd::SV_WG);
-    if (nv <= 1) hipLaunchKernelGGL(gd::gd_svd_project_kernel<1>, pgrid, pwg, 0, c->stream, j);
+    if (log2s) {
+        if (nv <= 1) hipLaunchKernelGGL(gd::gd_svl_project_kernel<1>, pgrid, pwg, 0, c->stream, l);
+        else if (nv <= 2) hipLaunchKernelGGL(gd::gd_svl_project_kernel<2>, pgrid, pwg, 0, c->stream, l);
+        else if (nv <= 4) hipLaunchKernelGGL(gd::gd_svl_project_kernel<4>, pgrid, pwg, 0, c->stream, l);
+        else if (nv <= 8) hipLaunchKernelGGL(gd::gd_svl_project_kernel<8>, pgrid, pwg, 0, c->stream, l);
+        else hipLaunchKernelGGL(gd::gd_svl_project_kernel<16>, pgrid, pwg, 0, c->stream, l);
+    } else if (nv <= 1) hipLaunchKernelGGL(gd::gd_svd_project_kernel<1>, pgrid, pwg, 0, c->stream, j);
     else if (nv <= 2) hipLaunchKernelGGL(gd::gd_svd_project_kernel<2>, pgrid, pwg, 0, c->stream, j);
     else if (nv <= 4) hipLaunchKernelGGL(gd::gd_svd_project_kernel<4>, pgrid, pwg, 0, c->stream, j);
     else if (nv <= 8) hipLaunchKernelGGL(gd::gd_svd_project_kernel<8>, pgrid, pwg, 0, c->stream, j);
@@ -80,16 +120,18 @@ static int sv_run(gd_ctx* c, const float* d_src, float* d_dst, size_t n_rows, in
     c->sv_secs[3] = ing_now() - t3;
     if (s) std::copy(sv.begin(), sv.end(), s);
     if (n_removed) *n_removed = (int)n;
+    if (log2s && centre_cells) mat_keys_to_float(keys, centre_cells);
     return GD_OK;
 }
 
 }  // namespace
 
-int gd_svd_debias(gd_ctx* c, const float* depths, size_t n_rows, int n_samples, double min_variance_pct, int zscore, float* out,
-                  double* s, int* n_removed)
+int gd_svd_debias_scaled(gd_ctx* c, const float* depths, size_t n_rows, int n_samples, double min_variance_pct, int scaler,
+                         float* out, double* s, int* n_removed, float* centre_cells)
 {
     if (!c) return GD_E_INVALID;
     if (int r = sv_check(c, n_rows, n_samples, min_variance_pct)) return r;
+    if (int r = sv_check_scaler(c, scaler)) return r;
     if (!depths || !out) return GD_E_INVALID;
     if (int r = mat_check(c, "svd debias", depths, n_rows, n_samples)) return r;
     if (int r = set_device(c)) return r;
@@ -101,7 +143,8 @@ int gd_svd_debias(gd_ctx* c, const float* depths, size_t n_rows, int n_samples, 
     HIPCHK(c, hipMemcpyAsync(d.p, depths, bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->sv_secs[0] = ing_now() - t0;
-    if (int r = sv_run(c, d.as<const float>(), d.as<float>(), n_rows, n_samples, min_variance_pct, zscore, s, n_removed)) return r;
+    if (int r = sv_run(c, d.as<const float>(), d.as<float>(), n_rows, n_samples, min_variance_pct, scaler, s, n_removed, centre_cells))
+        return r;
     const double t4 = ing_now();
     HIPCHK(c, hipMemcpyAsync(out, d.p, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -109,11 +152,18 @@ int gd_svd_debias(gd_ctx* c, const float* depths, size_t n_rows, int n_samples, 
     return GD_OK;
 }
 
-int gd_svd_debias_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, int n_samples, double min_variance_pct, int zscore,
-                        float* d_out, double* s, int* n_removed)
+int gd_svd_debias(gd_ctx* c, const float* depths, size_t n_rows, int n_samples, double min_variance_pct, int zscore, float* out,
+                  double* s, int* n_removed)
+{
+    return gd_svd_debias_scaled(c, depths, n_rows, n_samples, min_variance_pct, sv_scaler(zscore), out, s, n_removed, nullptr);
+}
+
+int gd_svd_debias_scaled_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, int n_samples, double min_variance_pct, int scaler,
+                               float* d_out, double* s, int* n_removed, float* centre_cells)
 {
     if (!c) return GD_E_INVALID;
     if (int r = sv_check(c, n_rows, n_samples, min_variance_pct)) return r;
+    if (int r = sv_check_scaler(c, scaler)) return r;
     if (!d_cells || !d_out) return GD_E_INVALID;
     const size_t cells = n_rows * (size_t)n_samples;
     if (gdm::overlap(d_cells, cells * sizeof(int64_t), d_out, cells * sizeof(float)))
@@ -126,14 +176,21 @@ int gd_svd_debias_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, int n_
     if (int r = dm_from_cells(c, d_cells, d_out, n_rows, n_samples, negative)) return r;
     if (int r = dm_check(c, "svd debias", d_out, n_rows, n_samples)) return r;
     c->sv_secs[0] = ing_now() - t0;
-    return sv_run(c, d_out, d_out, n_rows, n_samples, min_variance_pct, zscore, s, n_removed);
+    return sv_run(c, d_out, d_out, n_rows, n_samples, min_variance_pct, scaler, s, n_removed, centre_cells);
 }
 
-int gd_svd_debias_device(gd_ctx* c, const float* d_depths, size_t n_rows, int n_samples, double min_variance_pct, int zscore,
-                         float* d_out, double* s, int* n_removed)
+int gd_svd_debias_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, int n_samples, double min_variance_pct, int zscore,
+                        float* d_out, double* s, int* n_removed)
+{
+    return gd_svd_debias_scaled_cells(c, d_cells, n_rows, n_samples, min_variance_pct, sv_scaler(zscore), d_out, s, n_removed, nullptr);
+}
+
+int gd_svd_debias_scaled_device(gd_ctx* c, const float* d_depths, size_t n_rows, int n_samples, double min_variance_pct, int scaler,
+                                float* d_out, double* s, int* n_removed, float* centre_cells)
 {
     if (!c) return GD_E_INVALID;
     if (int r = sv_check(c, n_rows, n_samples, min_variance_pct)) return r;
+    if (int r = sv_check_scaler(c, scaler)) return r;
     if (!d_depths || !d_out) return GD_E_INVALID;
     const size_t bytes = n_rows * (size_t)n_samples * sizeof(float);
     if (d_out != d_depths && gdm::overlap(d_depths, bytes, d_out, bytes))
@@ -143,7 +200,13 @@ int gd_svd_debias_device(gd_ctx* c, const float* d_depths, size_t n_rows, int n_
     const double t0 = ing_now();
     if (int r = dm_check(c, "svd debias", d_depths, n_rows, n_samples)) return r;
     c->sv_secs[0] = ing_now() - t0;
-    return sv_run(c, d_depths, d_out, n_rows, n_samples, min_variance_pct, zscore, s, n_removed);
+    return sv_run(c, d_depths, d_out, n_rows, n_samples, min_variance_pct, scaler, s, n_removed, centre_cells);
+}
+
+int gd_svd_debias_device(gd_ctx* c, const float* d_depths, size_t n_rows, int n_samples, double min_variance_pct, int zscore,
+                         float* d_out, double* s, int* n_removed)
+{
+    return gd_svd_debias_scaled_device(c, d_depths, n_rows, n_samples, min_variance_pct, sv_scaler(zscore), d_out, s, n_removed, nullptr);
 }
 
 int gd_svd_debias_timing(gd_ctx* c, double* out, size_t n)

@@ -15,6 +15,7 @@
 //                                        [samples][256] table with one atomic each.
 //   gd_colselect_pick_kernel<MODE>       one wavefront a column: the bin the rank falls in, the rank left inside it,
 //                                        the prefix one digit longer; the counters are left zero for the next pass.
+//   gd_colmid_pick_kernel                the float first pick with another rank: rows / 2 over all cells, zeros included.
 //
 // T = float: the keys are the bit patterns (non-negative floats order as their bits do; -0.0 is mapped to 0), four passes;
 // the first also counts the exact zeros, in a register.  T = int64_t: the first pass is a histogram of the cell's LENGTH
@@ -45,7 +46,7 @@ constexpr int CS_MAX_N = 4096;
 constexpr int CS_PICK_WAVES = 4;                 // columns of a pick workgroup
 constexpr double CS_QUANTILE = 0.65;             // dcnv.go:121
 
-enum { CS_PICK_FLOAT_FIRST = 0, CS_PICK_LENGTH = 1, CS_PICK_DIGIT = 2 };
+enum { CS_PICK_FLOAT_FIRST = 0, CS_PICK_LENGTH = 1, CS_PICK_DIGIT = 2, CS_PICK_FLOAT_MID = 3 };
 
 struct CsJob {
     const void* cells;                           // [n_rows][n] float or int64_t
@@ -150,7 +151,7 @@ __device__ __forceinline__ uint32_t cs_rank(uint64_t k, uint64_t n)
 }
 
 template <int MODE>
-__global__ __launch_bounds__(CS_PICK_WAVES * 64) void gd_colselect_pick_kernel(CsJob j)
+__device__ __forceinline__ void cs_pick(const CsJob& j)
 {
     const int lane = threadIdx.x & 63;
     const int col = (int)blockIdx.x * CS_PICK_WAVES + (int)(threadIdx.x >> 6);
@@ -178,7 +179,7 @@ __global__ __launch_bounds__(CS_PICK_WAVES * 64) void gd_colselect_pick_kernel(C
     if constexpr (MODE != CS_PICK_DIGIT) {
         const uint64_t rows = (uint64_t)j.n_rows;
         uint64_t k;
-        if constexpr (MODE == CS_PICK_FLOAT_FIRST) {
+        if constexpr (MODE == CS_PICK_FLOAT_FIRST || MODE == CS_PICK_FLOAT_MID) {
             k = j.zeros[col];
         } else {
             k = __shfl(c.x, 0, 64);                                // length 0
@@ -191,7 +192,7 @@ __global__ __launch_bounds__(CS_PICK_WAVES * 64) void gd_colselect_pick_kernel(C
             if (lane == 0) { j.prefix[col] = 0; j.rem[col] = 0; j.rank[col] = 0; }
             return;
         }
-        rank = cs_rank(k, nz);
+        rank = MODE == CS_PICK_FLOAT_MID ? (uint32_t)(rows / 2) : cs_rank(k, nz);
         rem = 4;
     }
     const uint32_t excl = incl - own;
@@ -215,6 +216,19 @@ __global__ __launch_bounds__(CS_PICK_WAVES * 64) void gd_colselect_pick_kernel(C
         j.rem[col] = rem - 1;
         j.rank[col] = left;
     }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(CS_PICK_WAVES * 64) void gd_colselect_pick_kernel(CsJob j)
+{
+    cs_pick<MODE>(j);
+}
+
+// the first pick of a float matrix with the rank rows / 2 over ALL cells, zeros included: the upper median dcnv's Log2
+// scaler centres a sample on (gd_svdlog2.hpp).  A kernel of its own, so that the three instances above stay what they were.
+__global__ __launch_bounds__(CS_PICK_WAVES * 64) void gd_colmid_pick_kernel(CsJob j)
+{
+    cs_pick<CS_PICK_FLOAT_MID>(j);
 }
 
 }  // namespace gd

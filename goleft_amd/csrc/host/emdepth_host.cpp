@@ -47,6 +47,15 @@
 // runs it in-process, always z-scored (emdepth refuses negative cells), after the GC debias when there is one and before
 // --normalize, which it implies: the output is what `debias --svd PCT --zscore | emdepth --normalize` writes.  The spectrum
 // needs every row, so this step is never tiled by GOLEFT_EMDEPTH_ROWS.
+//
+//   goleft-depth debias --svd PCT --log2 matrix.bed[.gz]
+//   goleft-depth emdepth --svd PCT --log2 [GC flags] [--level L] [--cnvs FILE] matrix.bed[.gz]
+//
+// --log2 flanks the SVD debiaser with the reference's Log2 scaler instead (scalers.go:134-164):
+// log2(1 + depth), every sample centred on its median over the rows, and back by max(0, 2^x - 1) -- the "- 1" and the clamp
+// are this project's, the reference's UnScale returns depth + 1.  In log space a multiplicative bias is additive, and a site
+// where a few samples carry a CNV is not flattened before the cut sees it, as the z-score flattens it.  Not with --zscore.
+// `emdepth --svd PCT --log2` is `debias --svd PCT --log2 | emdepth --normalize`.
 #include <zlib.h>
 
 #include <algorithm>
@@ -72,6 +81,7 @@ struct EArgs {
     double level = 0, window = 0.01;
     int moving = 0;                              // --moving / --gc-moving: the GeneralDebiaser's window, in rows
     bool has_svd = false, zscore = false;        // --svd PCT [--zscore]: the SVD debiaser's MinVariancePct, its scaler
+    bool log2 = false;                           // --log2: the Log2 scaler in the z-score's place
     double svd = 0;
     bool gc() const { return !gc_values.empty() || !gc_fasta.empty(); }
 };
@@ -88,7 +98,7 @@ void usage_scales(FILE* f)
 void usage_debias(FILE* f)
 {
     fputs("usage: debias (--gc-values FILE | --fasta REF.fa) [--window W | --moving ROWS] MATRIX\n"
-          "       debias --svd PCT [--zscore] MATRIX\n"
+          "       debias --svd PCT [--zscore | --log2] MATRIX\n"
           "  MATRIX  a depthwed matrix (#chrom start end samples... and its rows), plain or gzipped\n"
           "  writes the matrix with every cell divided by its sample's median over the rows of similar covariate (dcnv's\n"
           "  ChunkDebiaser): the rows in covariate order are cut where a value exceeds the chunk's first by more than W\n"
@@ -101,13 +111,15 @@ void usage_debias(FILE* f)
           "         PCT per cent (a finite number >= 0), at most 15 (dcnv's SVD debiaser); 2 .. 1024 samples.  The removed shares\n"
           "         go to stderr.  Not with the flags above: chain the debiasers by a pipe\n"
           "  --zscore  with --svd: z-score every row first and carry it back after (max(0, z sd + mean)); without it the first\n"
-          "            component is the mean depth and cells may come out negative\n", f);
+          "            component is the mean depth and cells may come out negative\n"
+          "  --log2  with --svd, not with --zscore: take log2(1 + depth) and centre every sample on its median over the rows\n"
+          "          first (dcnv's Log2 scaler), and carry the result back after (max(0, 2^x - 1))\n", f);
 }
 
 void usage(FILE* f)
 {
     fputs("usage: emdepth [--scales FILE | --normalize [--level L] | (--gc-values FILE | --gc-fasta REF.fa) [--gc-window W | --gc-moving ROWS] [--level L]]\n"
-          "               [--svd PCT] [--cnvs FILE] MATRIX\n"
+          "               [--svd PCT [--log2]] [--cnvs FILE] MATRIX\n"
           "  MATRIX  a depthwed matrix (#chrom start end samples... and its rows), plain or gzipped, already normalised\n"
           "  --scales  a file of one factor per line, in column order: every depth is multiplied by its sample's factor\n"
           "  --normalize  compute those factors here, as `scales` does: each sample's 0.65 quantile of its non-zero depths\n"
@@ -116,6 +128,7 @@ void usage(FILE* f)
           "               --gc-values, --fasta, --window, --moving), then --normalize: to --level, or to the middle one of the\n"
           "               sample quantiles of the matrix as read\n"
           "  --svd  after the GC debias, if any: `debias --svd PCT --zscore`, then --normalize (to --level or the middle sample quantile)\n"
+          "  --log2  with --svd: `debias --svd PCT --log2` in place of --zscore\n"
           "  --cnvs  write the CNV calls of every sample (emdepth.Cache) to FILE: sample, index, psize, sites, positions, cn, depth, log2fc\n", f);
 }
 
@@ -141,6 +154,7 @@ int parse_args(int argc, const char* const* argv, EArgs* a, int cmd)
         if (arg == "--") { for (++i; i < argc; ++i) pos.push_back(argv[i]); break; }
         if (arg == "--normalize" && cmd == CMD_EMDEPTH) { a->normalize = true; continue; }
         if (arg == "--zscore" && cmd == CMD_DEBIAS) { a->zscore = true; continue; }
+        if (arg == "--log2" && cmd != CMD_SCALES) { a->log2 = true; continue; }
         if (arg.size() > 1 && arg[0] == '-') {
             std::string key = arg, val;
             bool has_val = false;
@@ -215,6 +229,16 @@ int parse_args(int argc, const char* const* argv, EArgs* a, int cmd)
     }
     if (a->zscore && !a->has_svd) {
         fprintf(stderr, "error: --zscore is the scaler of --svd: it needs --svd PCT\n");
+        usage(stderr);
+        return -1;
+    }
+    if (a->log2 && !a->has_svd) {
+        fprintf(stderr, "error: --log2 is a scaler of --svd: it needs --svd PCT\n");
+        usage(stderr);
+        return -1;
+    }
+    if (a->log2 && a->zscore) {
+        fprintf(stderr, "error: --log2 and --zscore both name the scaler of --svd: give one of them\n");
         usage(stderr);
         return -1;
     }
@@ -708,18 +732,21 @@ int debias_matrix(const char* prog, gd_ctx* ctx, const EArgs& a, Matrix* m, std:
     return 0;
 }
 
-// gd_svd_debias over the whole matrix: m's depths become the result.  The stderr line is the reference's log line
+// the scaler the flags name; `none` where they name none
+int svd_scaler(const EArgs& a, int none) { return a.log2 ? GD_SVD_SCALER_LOG2 : a.zscore ? GD_SVD_SCALER_ZSCORE : none; }
+
+// gd_svd_debias_scaled over the whole matrix (scaler: a GD_SVD_SCALER_*): m's depths become the result.  The stderr line is the reference's log line
 // (debiaser.go:186-192: the shares of the removed singular values, %.2f), then their number.  secs: gd_svd_debias_timing's
 // five values, then n.
-int svd_matrix(const char* prog, gd_ctx* ctx, const EArgs& a, bool zscore, Matrix* m, double* secs)
+int svd_matrix(const char* prog, gd_ctx* ctx, const EArgs& a, int scaler, Matrix* m, double* secs)
 {
     const size_t N = m->n, rows = m->where.size();
     if (rows == 0) { fprintf(stderr, "%s: %s has no rows\n", prog, a.input.c_str()); return 1; }
     std::vector<float> out(rows * N);
     std::vector<double> s(std::min(rows, N));
     int n = 0;
-    const int rc = gd_svd_debias(ctx, m->depths.data(), rows, (int)N, a.svd, zscore ? 1 : 0, out.data(), s.data(), &n);
-    if (rc != GD_OK) { fprintf(stderr, "%s: gd_svd_debias: %s (%s)\n", prog, gd_strerror(rc), gd_last_error(ctx)); return 1; }
+    const int rc = gd_svd_debias_scaled(ctx, m->depths.data(), rows, (int)N, a.svd, scaler, out.data(), s.data(), &n, nullptr);
+    if (rc != GD_OK) { fprintf(stderr, "%s: gd_svd_debias_scaled: %s (%s)\n", prog, gd_strerror(rc), gd_last_error(ctx)); return 1; }
     (void)gd_svd_debias_timing(ctx, secs, 5);
     secs[5] = (double)n;
     double sum = 0;
@@ -754,7 +781,7 @@ int run_debias(const EArgs& a, FILE* out)
     if (int rc = open_device("debias", &ctx)) return rc;
     std::vector<double> vals;
     double secs[7] = {0, 0, 0, 0, 0, 0, 0};
-    const int rc = a.has_svd ? svd_matrix("debias", ctx, a, a.zscore, &m, secs) : debias_matrix("debias", ctx, a, &m, &vals, secs);
+    const int rc = a.has_svd ? svd_matrix("debias", ctx, a, svd_scaler(a, GD_SVD_SCALER_NONE), &m, secs) : debias_matrix("debias", ctx, a, &m, &vals, secs);
     gd_destroy(ctx);
     if (rc) return rc;
     const size_t N = m.n, rows = m.where.size();
@@ -829,8 +856,8 @@ int run(const EArgs& a, FILE* out)
         if (rc == 0) rc = debias_matrix("emdepth", ctx, a, &m, &vals, gc_secs);
         if (rc) { gd_destroy(ctx); return rc; }
     }
-    if (a.has_svd)                               // always z-scored: the rows below take no negative cell
-        if (int rc = svd_matrix("emdepth", ctx, a, true, &m, svd_secs)) { gd_destroy(ctx); return rc; }
+    if (a.has_svd)                               // always scaled: the rows below take no negative cell
+        if (int rc = svd_matrix("emdepth", ctx, a, svd_scaler(a, GD_SVD_SCALER_ZSCORE), &m, svd_secs)) { gd_destroy(ctx); return rc; }
     if (a.normalize) {
         // the matrix goes up once for the medians and again, scaled, in its blocks
         std::vector<float> scale, med;

@@ -22,7 +22,8 @@ def Main(argv, out_path=None) -> int:
     ["--normalize", "--level", "30", "--cnvs", "cnvs.tsv", "matrix.bed"] or ["--gc-values", "gc.txt", "matrix.bed"]: a
     depthwed matrix (`#chrom start end samples...` and its rows), plain or gzipped, already normalised unless --normalize
     or a GC flag (--gc-values FILE | --gc-fasta REF.fa, [--gc-window W | --gc-moving ROWS]: debias as Debias does, then normalise) is given;
-    ["--svd", "2"] runs `debias --svd 2 --zscore` after that and before the normalisation.
+    ["--svd", "2"] runs `debias --svd 2 --zscore` after that and before the normalisation, ["--svd", "2", "--log2"] runs
+    `debias --svd 2 --log2` there.
     The rows go to out_path (stdout when None); returns the exit code."""
     lib = _hostlib.load()
     n, arr = _argv(b"emdepth", argv)
@@ -43,7 +44,8 @@ def Debias(argv, out_path=None) -> int:
     (dcnv's ChunkDebiaser; with ["--moving", "9"] in place of --window by the moving median of dcnv's GeneralDebiaser) goes
     to out_path (stdout when None); returns the exit code.  ["--svd", "2", "--zscore", "matrix.bed"] takes no covariate:
     dcnv's SVD debiaser zeroes the leading singular values whose share of the spectrum exceeds 2 per cent, at most 15, between
-    the z-score scaler's two halves; the removed shares go to stderr."""
+    the z-score scaler's two halves; the removed shares go to stderr.  ["--svd", "2", "--log2", "matrix.bed"] puts dcnv's
+    Log2 scaler in the z-score's place: log2(1 + depth) centred per sample, and back by max(0, 2^x - 1)."""
     lib = _hostlib.load()
     n, arr = _argv(b"debias", argv)
     return int(lib.gdh_debias_run(n, arr, out_path.encode() if out_path else None))
@@ -82,12 +84,13 @@ def _factors(med, nonzero, T):
 
 
 def cohort_cnvs(eng, dptr, rows, n_samples, starts, ends, vals=None, window=None, level=None, block_rows=None,
-                site_cn=False, moving=None, svd=None):
+                site_cn=False, moving=None, svd=None, svd_scaler="zscore"):
     """From DepthEngine.depthwed_device's int64 cells (dptr, rows) to CNV calls without the matrix leaving HBM: the
     resident twin of `goleft-depth emdepth --normalize --cnvs` (vals None) and of `emdepth --gc-values --cnvs` (vals: the
     covariate of every row, window: --gc-window, 0.01 when None; or moving: --gc-moving, the odd window of dcnv's
     GeneralDebiaser in place of the ChunkDebiaser -- giving both is a ValueError).  svd: --svd, the share in per cent above
-    which dcnv's SVD debiaser zeroes a leading singular value, always z-scored, after the GC debias when vals is given and
+    which dcnv's SVD debiaser zeroes a leading singular value, z-scored (svd_scaler "zscore") or between the halves of
+    dcnv's Log2 scaler (svd_scaler "log2": --log2; anything else is a ValueError), after the GC debias when vals is given and
     before the normalisation; with svd and without vals the level None is the middle sample median of the debiased matrix,
     as `debias --svd PCT --zscore | emdepth --normalize` has it.  level: --level; None is the middle sample median of the matrix as
     read.  Returns (factors float32 [samples], level, what DepthEngine.emdepth_cnvs* returns); the per-site copy numbers
@@ -101,6 +104,8 @@ def cohort_cnvs(eng, dptr, rows, n_samples, starts, ends, vals=None, window=None
         raise ValueError("cohort_cnvs: the level must be a finite number > 0")
     if moving is not None and window is not None:
         raise ValueError("cohort_cnvs: window (the ChunkDebiaser) and moving (the GeneralDebiaser) exclude each other")
+    if svd_scaler not in ("zscore", "log2"):
+        raise ValueError("cohort_cnvs: svd_scaler is 'zscore' or 'log2'")
     if moving is not None and vals is None:
         raise ValueError("cohort_cnvs: moving needs the covariate of every row")
     T = None if level is None else float(level)
@@ -116,14 +121,14 @@ def cohort_cnvs(eng, dptr, rows, n_samples, starts, ends, vals=None, window=None
     out = eng.device_alloc(max(rows * n_samples * 4, 1))
     try:
         if vals is None:
-            eng.svd_debias_cells(dptr, rows, n_samples, svd, True, out)
+            eng.svd_debias_cells(dptr, rows, n_samples, svd, True, out, scaler=svd_scaler)
         else:
             if moving is not None:
                 eng.moving_debias_cells(dptr, rows, n_samples, vals, moving, out)
             else:
                 eng.chunk_debias_cells(dptr, rows, n_samples, vals, 0.01 if window is None else window, out)
             if svd is not None:
-                eng.svd_debias_device(out, rows, n_samples, svd, True, out)
+                eng.svd_debias_device(out, rows, n_samples, svd, True, out, scaler=svd_scaler)
         med, nz = eng.sample_medians_device(out, rows, n_samples)
         if vals is None and level is None:
             T = _factors(med, nz, None)

@@ -417,39 +417,50 @@ class DepthEngine:
         self._chk(self._lib.gd_moving_debias_timing(self._ctx, t, 4))
         return t[0], t[1], t[2], t[3]
 
-    def svd_debias(self, depths, pct, zscore=False):
+    SVD_SCALERS = {"none": 0, "zscore": 1, "log2": 2}
+
+    def _svd_scaler(self, zscore, scaler):
+        """GD_SVD_SCALER_* of a scaler given by name or number; None: as zscore says"""
+        if scaler is None:
+            return int(bool(zscore))
+        return self.SVD_SCALERS[scaler] if isinstance(scaler, str) else int(scaler)
+
+    def svd_debias(self, depths, pct, zscore=False, scaler=None):
         """dcnv's SVD debiaser on a [rows][samples] float32 matrix (finite, >= 0; 2 .. 1024 samples, at least one row): the
         leading singular values whose share 100 s[k] / sum(s) exceeds pct (finite, >= 0) are zeroed, at most
         min(15, rows, samples) of them, and the matrix is multiplied back together; with zscore every row is z-scored first
-        (a row without spread becomes zeros) and carried back after, max(0, z sd + mean).  Returns (out float32
-        [rows, samples], s float64 [min(rows, samples)], n removed)."""
+        (a row without spread becomes zeros) and carried back after, max(0, z sd + mean).  scaler: None (as zscore says),
+        "none", "zscore" or "log2" -- dcnv's Log2 scaler: log2(1 + depth), every sample centred on its upper median over
+        all rows, and back by max(0, 2^x - 1).  Returns (out float32 [rows, samples], s float64 [min(rows, samples)],
+        n removed)."""
         d = np.ascontiguousarray(depths, np.float32)
         assert d.ndim == 2
         rows, n = d.shape
         out, s, k = np.empty((rows, n), np.float32), np.empty(max(min(rows, n), 1), np.float64), C.c_int()
-        self._chk(self._lib.gd_svd_debias(self._ctx, d.ctypes.data if d.size else None, rows, n, float(pct), int(bool(zscore)),
-                                          out.ctypes.data, s.ctypes.data, C.byref(k)))
+        self._chk(self._lib.gd_svd_debias_scaled(self._ctx, d.ctypes.data if d.size else None, rows, n, float(pct),
+                                                 self._svd_scaler(zscore, scaler), out.ctypes.data, s.ctypes.data, C.byref(k),
+                                                 None))
         return out, s[:min(rows, n)], k.value
 
-    def _svd_resident(self, fn, src: int, rows: int, n_samples: int, pct, zscore, out_ptr: int):
+    def _svd_resident(self, fn, src: int, rows: int, n_samples: int, pct, zscore, out_ptr: int, scaler):
         s, k = np.empty(max(min(rows, n_samples), 1), np.float64), C.c_int()
-        self._chk(fn(self._ctx, C.c_void_p(src), rows, n_samples, float(pct), int(bool(zscore)), C.c_void_p(out_ptr),
-                     s.ctypes.data, C.byref(k)))
+        self._chk(fn(self._ctx, C.c_void_p(src), rows, n_samples, float(pct), self._svd_scaler(zscore, scaler),
+                     C.c_void_p(out_ptr), s.ctypes.data, C.byref(k), None))
         return s[:min(rows, n_samples)], k.value
 
-    def svd_debias_cells(self, dptr: int, rows: int, n_samples: int, pct, zscore, out_ptr: int):
+    def svd_debias_cells(self, dptr: int, rows: int, n_samples: int, pct, zscore, out_ptr: int, scaler=None):
         """svd_debias for int64 cells in HBM (depthwed_device's pointer): the result for float32(cell) goes to the device
         float32 [rows][n_samples] matrix at out_ptr, which must not overlap the cells.  Returns (s, n removed)."""
-        return self._svd_resident(self._lib.gd_svd_debias_cells, dptr, rows, n_samples, pct, zscore, out_ptr)
+        return self._svd_resident(self._lib.gd_svd_debias_scaled_cells, dptr, rows, n_samples, pct, zscore, out_ptr, scaler)
 
-    def svd_debias_device(self, dptr: int, rows: int, n_samples: int, pct, zscore, out_ptr: int):
+    def svd_debias_device(self, dptr: int, rows: int, n_samples: int, pct, zscore, out_ptr: int, scaler=None):
         """svd_debias for a device float32 [rows][n_samples] matrix (checked on the device first) into the one at out_ptr,
         which may be dptr itself.  Returns (s, n removed)."""
-        return self._svd_resident(self._lib.gd_svd_debias_device, dptr, rows, n_samples, pct, zscore, out_ptr)
+        return self._svd_resident(self._lib.gd_svd_debias_scaled_device, dptr, rows, n_samples, pct, zscore, out_ptr, scaler)
 
     def svd_debias_timing(self):
-        """Of the last svd_debias call: (upload, row statistics + Gram matrix, eigenpairs on the host, projection,
-        read-back) seconds."""
+        """Of the last svd_debias call: (upload, row statistics or sample centres + Gram matrix, eigenpairs on the host,
+        projection, read-back) seconds."""
         t = (C.c_double * 5)()
         self._chk(self._lib.gd_svd_debias_timing(self._ctx, t, 5))
         return tuple(t)

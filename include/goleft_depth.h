@@ -39,7 +39,7 @@ extern "C" {
 
 /* GD_ABI_VERSION changes when an existing entry point or structure changes; GD_ABI_REVISION counts the releases that only
  * ADDED entry points since then (revision 1: gd_indexcov_*; 2: gd_indexsplit_*; 3: gd_crai_sizes).  A caller built against (15, r) runs on any (15, r' >= r).
- * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, gd_sample_medians*, gd_chunk_debias*, gd_device_scale, the *_device entries, gd_moving_debias* and gd_svd_debias*, were added without a revision; look them up by symbol.
+ * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, gd_sample_medians*, gd_chunk_debias*, gd_device_scale, the *_device entries, gd_moving_debias*, gd_svd_debias* and gd_svd_debias_scaled*, were added without a revision; look them up by symbol.
  * Why indexcov did not become version 16: nothing that existed changed, so callers of ABI 15 need not be turned away, and
  * tests/test_host_cpu.py holds gd_abi_version() to 15 until something does change. */
 #define GD_ABI_VERSION 15
@@ -833,6 +833,26 @@ int gd_svd_debias_cells(gd_ctx* ctx, const int64_t* d_cells, size_t n_rows, int 
 int gd_svd_debias_device(gd_ctx* ctx, const float* d_depths, size_t n_rows, int n_samples, double min_variance_pct, int zscore,
                          float* d_out /* DEVICE [n_rows][n_samples]; may equal d_depths */, double* s, int* n_removed);
 int gd_svd_debias_timing(gd_ctx* ctx, double* out, size_t n);
+/* The same three with the scaler named: GD_SVD_SCALER_NONE and GD_SVD_SCALER_ZSCORE run what zscore 0 and 1 run above, any
+ * other value but the three is GD_E_RANGE (the zscore argument above takes every non-zero value as 1, hence the new entries).
+ * GD_SVD_SCALER_LOG2 is dcnv's Log2 scaler (dcnv/scalers/scalers.go:134-164 of the reference):
+ * l_ij = log2(1 + a_ij); every SAMPLE is centred on c_j = sorted(l_.j)[n_rows / 2], its upper median over all rows, zeros
+ * included (= log2(1 + m_j), m_j the cell of that rank); the spectrum, the cut and the projection above on z = l - c;
+ * out_ij = (float)max(0, 2^(z'_ij + c_j) - 1).  The "- 1" and the clamp are this project's: the reference's UnScale returns
+ * 2^x, depth + 1 after a round trip, which its own TestLog2RoundTrip refuses; a zero cell may leave the projection below 0.
+ * centre_cells (or NULL; host, [n_samples]) gets m_j, and is untouched unless the scaler is log2.  Sizes, refusals, the
+ * equal bytes from call to call and from form to form, d_out == d_depths and the timing slots are as above; the selection of
+ * the centres counts into the second slot of gd_svd_debias_timing.  A refused call leaves its outputs untouched. */
+enum { GD_SVD_SCALER_NONE = 0, GD_SVD_SCALER_ZSCORE = 1, GD_SVD_SCALER_LOG2 = 2 };
+int gd_svd_debias_scaled(gd_ctx* ctx, const float* depths, size_t n_rows, int n_samples, double min_variance_pct, int scaler,
+                         float* out /* [n_rows][n_samples] */, double* s /* [min(n_rows, n_samples)] or NULL */,
+                         int* n_removed /* or NULL */, float* centre_cells /* [n_samples] or NULL */);
+int gd_svd_debias_scaled_cells(gd_ctx* ctx, const int64_t* d_cells, size_t n_rows, int n_samples, double min_variance_pct,
+                               int scaler, float* d_out /* DEVICE [n_rows][n_samples] */, double* s, int* n_removed,
+                               float* centre_cells);
+int gd_svd_debias_scaled_device(gd_ctx* ctx, const float* d_depths, size_t n_rows, int n_samples, double min_variance_pct,
+                                int scaler, float* d_out /* DEVICE [n_rows][n_samples]; may equal d_depths */, double* s,
+                                int* n_removed, float* centre_cells);
 int gd_ingest_abort(gd_ctx* ctx);
 /* Page-locked host memory for the byte range handed to gd_ingest_bgzf (read the file
  * straight into it: the H2D copy then runs at PCIe speed instead of through a bounce
