@@ -1,5 +1,6 @@
 // gd_api_svddebias.inc -- dcnv's SVD debiaser and its z-score scaler (part of gd_api.hip, inside extern "C"; DESIGN.md
-// section 3.16).  The row statistics, the Gram matrix and the projection are gd_svddebias.hpp's kernels; the eigenpairs of
+// section 3.16).  The row statistics, the Gram matrix and the projection are gd_svddebias.hpp's kernels, the last two
+// instantiated with the scaler's policy; the eigenpairs of
 // the samples x samples Gram matrix, the spectrum and the cut are host work inside the call (gd_eigh.hpp).  The three forms
 // run the same kernels on the same float32 bits: the host form on an upload of its own, the cells form on d_out once
 // gd_devmat.hpp's conversion has filled it, the device form from d_depths into d_out (which may be d_depths).  Nothing is
@@ -27,9 +28,23 @@ static int sv_check_scaler(gd_ctx* c, int scaler)
     return GD_OK;
 }
 
+// the projection of scaler policy P, with a row's z in NV = 1, 2, 4, 8 or 16 registers a lane (a template has C++ linkage)
+extern "C++" template <class P>
+void sv_project(gd_ctx* c, const gd::SvJob& j, unsigned row_grid)
+{
+    const int nv = (j.n + 63) / 64;
+    const dim3 pgrid(row_grid), pwg(gd::SV_WG);
+    if (nv <= 1) hipLaunchKernelGGL((gd::gd_svd_project_kernel<P, 1>), pgrid, pwg, 0, c->stream, j);
+    else if (nv <= 2) hipLaunchKernelGGL((gd::gd_svd_project_kernel<P, 2>), pgrid, pwg, 0, c->stream, j);
+    else if (nv <= 4) hipLaunchKernelGGL((gd::gd_svd_project_kernel<P, 4>), pgrid, pwg, 0, c->stream, j);
+    else if (nv <= 8) hipLaunchKernelGGL((gd::gd_svd_project_kernel<P, 8>), pgrid, pwg, 0, c->stream, j);
+    else hipLaunchKernelGGL((gd::gd_svd_project_kernel<P, 16>), pgrid, pwg, 0, c->stream, j);
+}
+
 // After the checks: d_src (checked, on the device) to d_dst.  s, n_removed and centre_cells may be null; scaler is a
-// GD_SVD_SCALER_*.  With the log2 scaler gd_colselect.hpp's select finds the centre cell of every sample first, and
-// gd_svdlog2.hpp's kernels take the place of the row statistics, the Gram kernel and the projection.
+// GD_SVD_SCALER_*.  With the log2 scaler gd_colselect.hpp's select finds the centre cell of every sample first,
+// gd_svdlog2.hpp's centre kernel takes the place of the row statistics, and the Gram kernel and the projection are
+// instantiated with its policy.
 static int sv_run(gd_ctx* c, const float* d_src, float* d_dst, size_t n_rows, int n_samples, double pct, int scaler, double* s,
                   int* n_removed, float* centre_cells)
 {
@@ -54,10 +69,7 @@ static int sv_run(gd_ctx* c, const float* d_src, float* d_dst, size_t n_rows, in
     gd::SvJob j{};
     j.cells = d_src; j.out = d_dst; j.n_rows = (int64_t)n_rows; j.n = n_samples; j.zscore = zscore ? 1 : 0;
     j.stats = d_stats.as<double>(); j.part = d_part.as<double>(); j.gram = d_gram.as<double>(); j.vt = d_vt.as<const double>();
-    j.slabs = (int32_t)slabs;
-    gd::SlJob l{};
-    l.cells = d_src; l.out = d_dst; l.n_rows = (int64_t)n_rows; l.n = n_samples; l.slabs = (int32_t)slabs;
-    l.keys = d_keys.as<const uint64_t>(); l.centre = d_centre.as<double>(); l.part = d_part.as<double>(); l.vt = d_vt.as<const double>();
+    j.slabs = (int32_t)slabs; j.keys = d_keys.as<const uint64_t>(); j.centre = d_centre.as<double>();
     std::vector<uint64_t> keys(log2s ? N : 0);
     const dim3 ggrid((unsigned)slabs, (unsigned)pairs), gwg(gd::SV_WG);
     if (log2s) {
@@ -68,11 +80,11 @@ static int sv_run(gd_ctx* c, const float* d_src, float* d_dst, size_t n_rows, in
         std::copy(sm, sm + 3, c->sm_secs);
         c->sm_passes = sm_passes;
         if (r) return r;
-        hipLaunchKernelGGL(gd::gd_svl_centre_kernel, dim3((unsigned)((N + gd::SV_WG - 1) / gd::SV_WG)), gwg, 0, c->stream, l);
-        hipLaunchKernelGGL(gd::gd_svl_gram_kernel, ggrid, gwg, 0, c->stream, l);
+        hipLaunchKernelGGL(gd::gd_svl_centre_kernel, dim3((unsigned)((N + gd::SV_WG - 1) / gd::SV_WG)), gwg, 0, c->stream, j);
+        hipLaunchKernelGGL(gd::gd_svd_gram_kernel<gd::SvLog2>, ggrid, gwg, 0, c->stream, j);
     } else {
         if (zscore) hipLaunchKernelGGL(gd::gd_svd_rowstats_kernel, dim3(row_grid), gwg, 0, c->stream, j);
-        hipLaunchKernelGGL(gd::gd_svd_gram_kernel, ggrid, gwg, 0, c->stream, j);
+        hipLaunchKernelGGL(gd::gd_svd_gram_kernel<gd::SvLinear>, ggrid, gwg, 0, c->stream, j);
     }
     hipLaunchKernelGGL(gd::gd_svd_gram_sum_kernel, dim3(gd::SV_TILE * gd::SV_TILE / gd::SV_WG, (unsigned)pairs), dim3(gd::SV_WG), 0,
                        c->stream, j);
@@ -101,20 +113,9 @@ static int sv_run(gd_ctx* c, const float* d_src, float* d_dst, size_t n_rows, in
 
     const double t3 = ing_now();
     if (n) HIPCHK(c, hipMemcpyAsync(d_vt.p, vt.data(), n * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    j.n_removed = l.n_removed = (int32_t)n;
-    const int nv = (n_samples + 63) / 64;
-    const dim3 pgrid(row_grid), pwg(gd::SV_WG);
-    if (log2s) {
-        if (nv <= 1) hipLaunchKernelGGL(gd::gd_svl_project_kernel<1>, pgrid, pwg, 0, c->stream, l);
-        else if (nv <= 2) hipLaunchKernelGGL(gd::gd_svl_project_kernel<2>, pgrid, pwg, 0, c->stream, l);
-        else if (nv <= 4) hipLaunchKernelGGL(gd::gd_svl_project_kernel<4>, pgrid, pwg, 0, c->stream, l);
-        else if (nv <= 8) hipLaunchKernelGGL(gd::gd_svl_project_kernel<8>, pgrid, pwg, 0, c->stream, l);
-        else hipLaunchKernelGGL(gd::gd_svl_project_kernel<16>, pgrid, pwg, 0, c->stream, l);
-    } else if (nv <= 1) hipLaunchKernelGGL(gd::gd_svd_project_kernel<1>, pgrid, pwg, 0, c->stream, j);
-    else if (nv <= 2) hipLaunchKernelGGL(gd::gd_svd_project_kernel<2>, pgrid, pwg, 0, c->stream, j);
-    else if (nv <= 4) hipLaunchKernelGGL(gd::gd_svd_project_kernel<4>, pgrid, pwg, 0, c->stream, j);
-    else if (nv <= 8) hipLaunchKernelGGL(gd::gd_svd_project_kernel<8>, pgrid, pwg, 0, c->stream, j);
-    else hipLaunchKernelGGL(gd::gd_svd_project_kernel<16>, pgrid, pwg, 0, c->stream, j);
+    j.n_removed = (int32_t)n;
+    if (log2s) sv_project<gd::SvLog2>(c, j, row_grid);
+    else sv_project<gd::SvLinear>(c, j, row_grid);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->sv_secs[3] = ing_now() - t3;

@@ -5,10 +5,17 @@
 // z = (a - m_row) / sd_row (0 for a row whose sd is 0; z = a without the z-score) is formed in float64 where it is used,
 // by the one expression sv_z() in both passes.
 //
+// The Gram kernel and the projection are templates over a scaler policy P, which supplies what the scalers differ in and
+// nothing else: Row, a row's state, and row() that loads it; Col, a column's state, and col(); z() from a cell; back() from
+// z' to a float32 depth (row() and col() load nothing where their last argument is false: a row past the slab, a column
+// past N).  SvLinear below is "none" and the z-score, told apart by the job's zscore field when the kernel
+// runs; SvLog2 is gd_svdlog2.hpp's.  Tiles, slabs, chunks, LDS and the order of additions are the same for every scaler
+// because there is one text of them.
+//
 //   gd_svd_rowstats_kernel    a wave per row: m = sum / N, sd = sqrt(sum (a - m)^2 / (N - 1)), two passes in float64
 //                             (lane l sums columns l, l + 64, ...; the lanes meet in an xor butterfly, which leaves the
 //                             same bits in every lane) into stats[row][2].
-//   gd_svd_gram_kernel        a workgroup of 256 threads owns a (slab of SV_SLAB rows, pair of 64-column tiles ti <= tj):
+//   gd_svd_gram_kernel<P>     a workgroup of 256 threads owns a (slab of SV_SLAB rows, pair of 64-column tiles ti <= tj):
 //                             only the upper triangle of tiles is computed.  SV_CHUNK rows at a time, the z of both
 //                             tiles' columns go to LDS as float64 (2 x 16 x 64 x 8 bytes = 16 KB; a thread converts the
 //                             two cells of one row and column, 256-byte rows of loads), and every thread adds the
@@ -18,11 +25,12 @@
 //                             memory gave the same bits in 1.65 times the time)
 //   gd_svd_gram_sum_kernel    G[i][j] = G[j][i] = the partials of (i, j), i <= j, summed IN SLAB ORDER: no float atomics,
 //                             so two calls give the same bytes, and G is symmetric to the bit.
-//   gd_svd_project_kernel<NV> a wave per row, the row's z in NV = ceil(N / 64) registers a lane (1, 2, 4, 8 or 16):
+//   gd_svd_project_kernel<P, NV>
+//                             a wave per row, the row's z in NV = ceil(N / 64) registers a lane (1, 2, 4, 8 or 16):
 //                             c_k = sum_j z_j V[j][k] by the same butterfly for each of the n removed vectors,
-//                             z' = z - sum_k c_k V[j][k], then out = (float)z', or (float)max(0, z' sd + m) with the
-//                             z-score.  A lane reads its own columns before it writes them: out may be the input.  V is
-//                             read as vt[k][j] straight from global memory -- n x N float64, 24 KB at 200 samples and
+//                             z' = z - sum_k c_k V[j][k], then out = P::back(z'): (float)z', or (float)max(0, z' sd + m)
+//                             with the z-score.  A column's state is loaded where it is used, not held.  A lane reads
+//                             its own columns before it writes them: out may be the input.  V is read as vt[k][j] straight from global memory -- n x N float64, 24 KB at 200 samples and
 //                             n = 15, at most 120 KB: every wave of the device reads the same lines, so they stay in the
 //                             vector L1 / L2.  A copy in LDS would need 120 KB at the limits, one workgroup a CU, and a
 //                             staging pass per workgroup; the loads it would save are L1 hits behind the row's own
@@ -57,6 +65,8 @@ struct SvJob {
     const double* vt;                            // [n_removed][n]
     int32_t n_removed;
     int32_t slabs;
+    const uint64_t* keys;                        // [n] the select's answers: a float's bits in the low word (log2 only)
+    double* centre;                              // [n] log2(1 + m_j) (log2 only)
 };
 
 // the same bits in every lane: at each step both partners add the same two values
@@ -69,6 +79,32 @@ __device__ __forceinline__ double sv_wave_sum(double v)
 
 __device__ __forceinline__ double sv_inv(double sd) { return sd > 0.0 ? 1.0 / sd : 0.0; }
 __device__ __forceinline__ double sv_z(float a, double m, double inv) { return ((double)a - m) * inv; }
+
+// "none" and the z-score: a row's mean and sd from stats (0 and 1 without the z-score), nothing for a column
+struct SvLinear {
+    struct Row { double m = 0.0, sd = 1.0, inv = 1.0; };
+    struct Col {};
+    static __device__ __forceinline__ Row row(const SvJob& j, int64_t row, bool ok)
+    {
+        Row r;
+        if (j.zscore && ok) {
+            r.m = j.stats[2 * (size_t)row];
+            r.sd = j.stats[2 * (size_t)row + 1];
+            r.inv = sv_inv(r.sd);
+        }
+        return r;
+    }
+    static __device__ __forceinline__ Col col(const SvJob&, int, bool) { return Col{}; }
+    static __device__ __forceinline__ double z(float a, const Row& r, const Col&) { return sv_z(a, r.m, r.inv); }
+    static __device__ __forceinline__ float back(const SvJob& j, double zp, const Row& r, const Col&)
+    {
+        if (j.zscore) {
+            zp = zp * r.sd + r.m;
+            zp = zp > 0.0 ? zp : 0.0;
+        }
+        return (float)zp;
+    }
+};
 
 __global__ __launch_bounds__(SV_WG) void gd_svd_rowstats_kernel(SvJob j)
 {
@@ -95,6 +131,7 @@ __global__ __launch_bounds__(SV_WG) void gd_svd_rowstats_kernel(SvJob j)
 }
 
 // blockIdx.x the slab, blockIdx.y the pair of tiles: pairs are numbered row by row of the upper triangle
+template <class P>
 __global__ __launch_bounds__(SV_WG) void gd_svd_gram_kernel(SvJob j)
 {
     __shared__ double za[SV_CHUNK][SV_TILE], zb[SV_CHUNK][SV_TILE];
@@ -109,6 +146,7 @@ __global__ __launch_bounds__(SV_WG) void gd_svd_gram_kernel(SvJob j)
     const int ty = tid >> 4, tx = tid & 15;                  // the thread's 4 x 4 of the block: rows 4 ty .., columns 4 tx ..
     const int lr = tid >> 6, lc = tid & 63;                  // as a loader: row lr of every four, column lc of both tiles
     const int ca = ti * SV_TILE + lc, cb = tj * SV_TILE + lc;
+    const typename P::Col cola = P::col(j, ca, ca < n), colb = P::col(j, cb, cb < n);
     double acc[4][4];
 #pragma unroll
     for (int x = 0; x < 4; ++x)
@@ -121,14 +159,10 @@ __global__ __launch_bounds__(SV_WG) void gd_svd_gram_kernel(SvJob j)
         for (int u = 0; u < SV_CHUNK / 4; ++u) {
             const int64_t row = r + 4 * u + lr;
             const bool ok = row < r1;
-            double m = 0.0, inv = 1.0;
-            if (j.zscore && ok) {
-                m = j.stats[2 * (size_t)row];
-                inv = sv_inv(j.stats[2 * (size_t)row + 1]);
-            }
+            const typename P::Row rs = P::row(j, row, ok);
             const float* src = j.cells + (size_t)(ok ? row : r0) * (size_t)n;
-            za[4 * u + lr][lc] = ok && ca < n ? sv_z(src[ca], m, inv) : 0.0;
-            zb[4 * u + lr][lc] = ok && cb < n ? sv_z(src[cb], m, inv) : 0.0;
+            za[4 * u + lr][lc] = ok && ca < n ? P::z(src[ca], rs, cola) : 0.0;
+            zb[4 * u + lr][lc] = ok && cb < n ? P::z(src[cb], rs, colb) : 0.0;
         }
         __syncthreads();
 #pragma unroll
@@ -172,7 +206,7 @@ __global__ __launch_bounds__(SV_WG) void gd_svd_gram_sum_kernel(SvJob j)
     j.gram[(size_t)gj * (size_t)n + (size_t)gi] = g;
 }
 
-template <int NV>
+template <class P, int NV>
 __global__ __launch_bounds__(SV_WG) void gd_svd_project_kernel(SvJob j)
 {
     const int lane = threadIdx.x & 63;
@@ -181,17 +215,12 @@ __global__ __launch_bounds__(SV_WG) void gd_svd_project_kernel(SvJob j)
     const int K = j.n_removed;
     for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < j.n_rows; row += (int64_t)gridDim.x * 4) {
         const float* a = j.cells + (size_t)row * (size_t)n;
-        double m = 0.0, sd = 1.0, inv = 1.0;
-        if (j.zscore) {
-            m = j.stats[2 * (size_t)row];
-            sd = j.stats[2 * (size_t)row + 1];
-            inv = sv_inv(sd);
-        }
+        const typename P::Row rs = P::row(j, row, true);
         double z[NV], dz[NV];
 #pragma unroll
         for (int u = 0; u < NV; ++u) {
             const int c = lane + 64 * u;
-            z[u] = c < n ? sv_z(a[c], m, inv) : 0.0;
+            z[u] = c < n ? P::z(a[c], rs, P::col(j, c, true)) : 0.0;
             dz[u] = 0.0;
         }
         for (int k = 0; k < K; ++k) {
@@ -212,12 +241,7 @@ __global__ __launch_bounds__(SV_WG) void gd_svd_project_kernel(SvJob j)
 #pragma unroll
         for (int u = 0; u < NV; ++u) {
             const int c = lane + 64 * u;
-            double r = z[u] - dz[u];
-            if (j.zscore) {
-                r = r * sd + m;
-                r = r > 0.0 ? r : 0.0;
-            }
-            if (c < n) o[c] = (float)r;
+            if (c < n) o[c] = P::back(j, z[u] - dz[u], rs, P::col(j, c, true));
         }
     }
 }

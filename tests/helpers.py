@@ -1,6 +1,11 @@
 """Shared helpers for the tests (test infrastructure; may use oracle/)."""
+import functools
 import json
 import os
+import re
+import shutil
+import subprocess
+import tempfile
 
 import numpy as np
 
@@ -8,6 +13,33 @@ from oracle import pyoracle as po
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+HIPCC = next((p for p in ("/opt/rocm/bin/hipcc", shutil.which("hipcc") or "") if p and os.path.exists(p)), None)
+
+
+@functools.lru_cache(maxsize=None)
+def api_asm():
+    """goleft_amd/csrc/gd_api.hip as hipcc compiles it for gfx950, as assembly text.  The resource tests all read this one
+    compile: it runs once a process."""
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "api.s")
+        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
+                               "-I", os.path.join(ROOT, "include"), "-o", path,
+                               os.path.join(ROOT, "goleft_amd", "csrc", "gd_api.hip")], stderr=subprocess.DEVNULL)
+        with open(path) as f:
+            return f.read()
+
+
+def kernel_metadata(asm):
+    """{mangled name: dict(lds, scratch, vgpr, sgpr, spill, sgpr_spill, wg)} from the amdhsa.kernels: list of an assembly
+    text; the dicts are the caller's"""
+    meta = asm[asm.index("amdhsa.kernels:"):]
+    out = {}
+    for k in re.split(r"\n  - \.", meta)[1:]:
+        g = lambda key: re.search(r"\.%s:\s+(\S+)" % key, "." + k).group(1)
+        out[g("name")] = dict(lds=int(g("group_segment_fixed_size")), scratch=int(g("private_segment_fixed_size")),
+                              vgpr=int(g("vgpr_count")), sgpr=int(g("sgpr_count")), spill=int(g("vgpr_spill_count")),
+                              sgpr_spill=int(g("sgpr_spill_count")), wg=int(g("max_flat_workgroup_size")))
+    return out
 
 
 def load_golden_bam(name):

@@ -7,40 +7,21 @@ workgroup.  It is designed for TWO workgroups of 512 threads per CU (136 704 of 
 so at most 128 registers a lane).  The cells a wave has in flight and the 32 bins it scans are unrolled arrays and nothing
 is indexed by a runtime value: no scratch.  The divide kernel is a wave a row, four rows a workgroup, and uses no LDS.
 Metadata only."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
 from tests import helpers as H
 
-HIPCC = next((p for p in ("/opt/rocm/bin/hipcc", shutil.which("hipcc") or "") if p and os.path.exists(p)), None)
 LDS_PER_CU = 160 * 1024
 WORKGROUPS_PER_CU = 2                            # CD_WG_PER_CU
 MEDIAN_WG, DIVIDE_WG = 512, 256                  # CD_WG, CD_DIV_WAVES * 64
 MEDIAN_LDS = (256 * 64 + 8 * 64 + 3 * 64) * 4    # CD_BINS * CD_COLS counters, CD_WAVES * CD_COLS sums, prefix / rank / zeros
 
-pytestmark = pytest.mark.skipif(HIPCC is None, reason="needs hipcc")
+pytestmark = pytest.mark.skipif(H.HIPCC is None, reason="needs hipcc")
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    path = tmp_path_factory.mktemp("isa") / "api.s"
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                           "-I", os.path.join(H.ROOT, "include"), "-o", str(path),
-                           os.path.join(H.ROOT, "goleft_amd", "csrc", "gd_api.hip")], stderr=subprocess.DEVNULL)
-    asm = path.read_text()
-    meta = asm[asm.index("amdhsa.kernels:"):]
-    out = {}
-    for k in re.split(r"\n  - \.", meta)[1:]:
-        g = lambda key: re.search(r"\.%s:\s+(\S+)" % key, "." + k).group(1)
-        if "gd_chunkdebias_" in g("name"):
-            out[g("name")] = dict(lds=int(g("group_segment_fixed_size")), scratch=int(g("private_segment_fixed_size")),
-                                  vgpr=int(g("vgpr_count")), spill=int(g("vgpr_spill_count")),
-                                  wg=int(g("max_flat_workgroup_size")))
-    return out
+def kernels():
+    return {k: r for k, r in H.kernel_metadata(H.api_asm()).items() if "gd_chunkdebias_" in k}
 
 
 def test_two_kernels(kernels):

@@ -1,27 +1,18 @@
 """CPU: the .crai tiling kernels (gd_crai.hpp) as hipcc compiles them for gfx950 -- no scratch and no LDS, the slices handed
 round with v_readlane (the state of a sequence lives in scalar registers), the IEEE double division of the write pass
 with the product in front of it rounded on its own, and 8-byte stores for the fills."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 from tests import helpers as H
 
-HIPCC = next((p for p in ("/opt/rocm/bin/hipcc", shutil.which("hipcc") or "") if p and os.path.exists(p)), None)
-
-pytestmark = pytest.mark.skipif(HIPCC is None, reason="needs hipcc")
+pytestmark = pytest.mark.skipif(H.HIPCC is None, reason="needs hipcc")
 
 
 @pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    path = tmp_path_factory.mktemp("isa") / "api.s"
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                           "-I", os.path.join(H.ROOT, "include"), "-o", str(path),
-                           os.path.join(H.ROOT, "goleft_amd", "csrc", "gd_api.hip")], stderr=subprocess.DEVNULL)
-    return path.read_text()
+def asm():
+    return H.api_asm()
 
 
 def kernel(asm, write):

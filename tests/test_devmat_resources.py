@@ -6,38 +6,22 @@ row, four rows a workgroup, four rows of a wave in flight as an unrolled array: 
 no spills.  Metadata only."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 from tests import helpers as H
 
-HIPCC = next((p for p in ("/opt/rocm/bin/hipcc", shutil.which("hipcc") or "") if p and os.path.exists(p)), None)
 WG = 256                                         # DM_WG = DM_WAVES * 64
 KERNELS = ("gd_devmat_from_cells_kernel", "gd_devmat_check_kernel", "gd_devmat_scale_kernel")
 NEW_SYMBOLS = ("gd_chunk_debias_cells", "gd_device_scale", "gd_sample_medians_device", "gd_emdepth_device",
                "gd_emcnv_add_device")
 
-pytestmark = pytest.mark.skipif(HIPCC is None, reason="needs hipcc")
+pytestmark = pytest.mark.skipif(H.HIPCC is None, reason="needs hipcc")
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    path = tmp_path_factory.mktemp("isa") / "api.s"
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                           "-I", os.path.join(H.ROOT, "include"), "-o", str(path),
-                           os.path.join(H.ROOT, "goleft_amd", "csrc", "gd_api.hip")], stderr=subprocess.DEVNULL)
-    asm = path.read_text()
-    meta = asm[asm.index("amdhsa.kernels:"):]
-    out = {}
-    for k in re.split(r"\n  - \.", meta)[1:]:
-        g = lambda key: re.search(r"\.%s:\s+(\S+)" % key, "." + k).group(1)
-        if "gd_devmat_" in g("name"):
-            out[g("name")] = dict(lds=int(g("group_segment_fixed_size")), scratch=int(g("private_segment_fixed_size")),
-                                  vgpr=int(g("vgpr_count")), spill=int(g("vgpr_spill_count")),
-                                  sgpr_spill=int(g("sgpr_spill_count")), wg=int(g("max_flat_workgroup_size")))
-    return out
+def kernels():
+    return {k: r for k, r in H.kernel_metadata(H.api_asm()).items() if "gd_devmat_" in k}
 
 
 def test_three_kernels(kernels):

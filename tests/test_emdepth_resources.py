@@ -8,41 +8,24 @@ the Poisson term (log, lgamma, exp) inlined into the calls of a row's four regis
 registers -- two waves a SIMD -- and held to 128 by the compiler they spilled; with that term out of line they take
 99 - 114.  So: no scratch (nothing is indexed by a runtime value, nothing spills), at most 128 registers, and LDS
 (none) that lets four workgroups in."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
 from tests import helpers as H
 
-HIPCC = next((p for p in ("/opt/rocm/bin/hipcc", shutil.which("hipcc") or "") if p and os.path.exists(p)), None)
 LDS_PER_CU = 160 * 1024
 WORKGROUPS_PER_CU = 4
 
-pytestmark = pytest.mark.skipif(HIPCC is None, reason="needs hipcc")
+pytestmark = pytest.mark.skipif(H.HIPCC is None, reason="needs hipcc")
 
 
 @pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    path = tmp_path_factory.mktemp("isa") / "api.s"
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                           "-I", os.path.join(H.ROOT, "include"), "-o", str(path),
-                           os.path.join(H.ROOT, "goleft_amd", "csrc", "gd_api.hip")], stderr=subprocess.DEVNULL)
-    return path.read_text()
+def asm():
+    return H.api_asm()
 
 
 @pytest.fixture(scope="module")
 def kernels(asm):
-    meta = asm[asm.index("amdhsa.kernels:"):]
-    out = {}
-    for k in re.split(r"\n  - \.", meta)[1:]:
-        g = lambda key: re.search(r"\.%s:\s+(\S+)" % key, "." + k).group(1)
-        if "gd_emdepth_kernel" in g("name"):
-            out[g("name")] = dict(lds=int(g("group_segment_fixed_size")), scratch=int(g("private_segment_fixed_size")),
-                                  vgpr=int(g("vgpr_count")), wg=int(g("max_flat_workgroup_size")))
-    return out
+    return {k: r for k, r in H.kernel_metadata(asm).items() if "gd_emdepth_kernel" in k}
 
 
 def test_four_instances(kernels):

@@ -1,40 +1,23 @@
 """CPU: the indexcov kernels (gd_indexcov.hpp) as hipcc compiles them for gfx950 -- no scratch in any of them, and the
 Gram kernel is the 8-bit integer matrix instruction."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
 from tests import helpers as H
 
-HIPCC = next((p for p in ("/opt/rocm/bin/hipcc", shutil.which("hipcc") or "") if p and os.path.exists(p)), None)
-
-pytestmark = pytest.mark.skipif(HIPCC is None, reason="needs hipcc")
+pytestmark = pytest.mark.skipif(H.HIPCC is None, reason="needs hipcc")
 
 KERNELS = ("gd_ic_median_kernel", "gd_ic_depth_kernel", "gd_ic_pass_kernel", "gd_ic_cn_kernel", "gd_ic_rowsum_kernel",
            "gd_ic_gram_kernel", "gd_ic_gram_fin_kernel")
 
 
 @pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    path = tmp_path_factory.mktemp("isa") / "api.s"
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                           "-I", os.path.join(H.ROOT, "include"), "-o", str(path),
-                           os.path.join(H.ROOT, "goleft_amd", "csrc", "gd_api.hip")], stderr=subprocess.DEVNULL)
-    return path.read_text()
+def asm():
+    return H.api_asm()
 
 
 @pytest.fixture(scope="module")
 def kernels(asm):
-    meta = asm[asm.index("amdhsa.kernels:"):]
-    out = {}
-    for k in re.split(r"\n  - \.", meta)[1:]:
-        g = lambda key: re.search(r"\.%s:\s+(\S+)" % key, "." + k).group(1)
-        out[g("name")] = dict(lds=int(g("group_segment_fixed_size")), scratch=int(g("private_segment_fixed_size")),
-                              vgpr=int(g("vgpr_count")))
-    return out
+    return H.kernel_metadata(asm)
 
 
 @pytest.mark.parametrize("name", KERNELS)

@@ -1,26 +1,17 @@
 """CPU: the indexsplit kernel (gd_indexsplit.hpp) as hipcc compiles it for gfx950 -- no scratch, the IEEE double
 division, and no fused multiply-add outside that division's own sequence (the quotient is added with its own rounding)."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 from tests import helpers as H
 
-HIPCC = next((p for p in ("/opt/rocm/bin/hipcc", shutil.which("hipcc") or "") if p and os.path.exists(p)), None)
-
-pytestmark = pytest.mark.skipif(HIPCC is None, reason="needs hipcc")
+pytestmark = pytest.mark.skipif(H.HIPCC is None, reason="needs hipcc")
 
 
 @pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    path = tmp_path_factory.mktemp("isa") / "api.s"
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                           "-I", os.path.join(H.ROOT, "include"), "-o", str(path),
-                           os.path.join(H.ROOT, "goleft_amd", "csrc", "gd_api.hip")], stderr=subprocess.DEVNULL)
-    return path.read_text()
+def asm():
+    return H.api_asm()
 
 
 @pytest.fixture(scope="module")

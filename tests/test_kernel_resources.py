@@ -3,35 +3,21 @@ The tile kernels and the long-read kernel are tuned to seven 256-thread workgrou
 vector registers, the streaming sums kernel and the inflate kernel to six; none of them may spill.  A change that costs
 a register too many or a kilobyte of LDS passes every functional test and loses a seventh of the memory-level
 parallelism; here it fails on the CPU box."""
-import os
-import re
-import shutil
 import subprocess
 
 import pytest
 
 from tests import helpers as H
 
-HIPCC = next((p for p in ("/opt/rocm/bin/hipcc", shutil.which("hipcc") or "") if p and os.path.exists(p)), None)
 LDS_PER_CU = 160 * 1024
 
-pytestmark = pytest.mark.skipif(HIPCC is None, reason="needs hipcc")
+pytestmark = pytest.mark.skipif(H.HIPCC is None, reason="needs hipcc")
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    asm = tmp_path_factory.mktemp("isa") / "api.s"
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                           "-I", os.path.join(H.ROOT, "include"), "-o", str(asm),
-                           os.path.join(H.ROOT, "goleft_amd", "csrc", "gd_api.hip")], stderr=subprocess.DEVNULL)
-    text = asm.read_text()
-    meta = text[text.index("amdhsa.kernels:"):]
-    names, out = [], {}
-    for k in re.split(r"\n  - \.", meta)[1:]:
-        g = lambda key: re.search(r"\.%s:\s+(\S+)" % key, "." + k).group(1)
-        names.append(g("name"))
-        out[names[-1]] = dict(lds=int(g("group_segment_fixed_size")), scratch=int(g("private_segment_fixed_size")),
-                              sgpr=int(g("sgpr_count")), vgpr=int(g("vgpr_count")))
+def kernels():
+    out = H.kernel_metadata(H.api_asm())
+    names = list(out)
     dem = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.strip().splitlines()
     return {d: out[n] for d, n in zip(dem, names)}
 

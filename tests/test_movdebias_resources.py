@@ -7,40 +7,23 @@ for CAP 63, 81 600 for CAP 255, two workgroups of which fit a CU's 160 KB.  The 
 to push, their addresses, and the eight slots a push has in flight) are unrolled arrays and the ring is LDS: no scratch;
 at most 128 registers a lane, four waves per SIMD (LDS holds the largest instance to two workgroups a CU whatever it
 uses).  Metadata only."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 from tests import helpers as H
 
-HIPCC = next((p for p in ("/opt/rocm/bin/hipcc", shutil.which("hipcc") or "") if p and os.path.exists(p)), None)
 LDS_PER_CU = 160 * 1024
 CAPS = (15, 63, 255)                             # MD_CAP_SMALL, MD_CAP_MID, MD_CAP_BIG
 WG = 64                                          # MD_COLS: one wave
 MAX_VGPR = 128
 
-pytestmark = pytest.mark.skipif(HIPCC is None, reason="needs hipcc")
+pytestmark = pytest.mark.skipif(H.HIPCC is None, reason="needs hipcc")
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    path = tmp_path_factory.mktemp("isa") / "api.s"
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                           "-I", os.path.join(H.ROOT, "include"), "-o", str(path),
-                           os.path.join(H.ROOT, "goleft_amd", "csrc", "gd_api.hip")], stderr=subprocess.DEVNULL)
-    asm = path.read_text()
-    meta = asm[asm.index("amdhsa.kernels:"):]
-    out = {}
-    for k in re.split(r"\n  - \.", meta)[1:]:
-        g = lambda key: re.search(r"\.%s:\s+(\S+)" % key, "." + k).group(1)
-        if "gd_movdebias_" in g("name"):
-            out[g("name")] = dict(lds=int(g("group_segment_fixed_size")), scratch=int(g("private_segment_fixed_size")),
-                                  vgpr=int(g("vgpr_count")), spill=int(g("vgpr_spill_count")),
-                                  wg=int(g("max_flat_workgroup_size")))
-    return out
+def kernels():
+    return {k: r for k, r in H.kernel_metadata(H.api_asm()).items() if "gd_movdebias_" in k}
 
 
 def cap_of(name):

@@ -1,5 +1,5 @@
-"""CPU: the SVD debias kernels (goleft_amd/csrc/gd_svddebias.hpp) as hipcc compiles them for gfx950, and the symbols the
-library exports for them.  Metadata only.
+"""CPU: the SVD debias kernels (goleft_amd/csrc/gd_svddebias.hpp) as hipcc compiles them for gfx950 with the policy of the
+linear scalers (SvLinear: none and the z-score), and the symbols the library exports for them.  Metadata only.
 
 DESIGN.md section 3.16 claims: no kernel uses scratch; every workgroup is 256 threads, a wave on each SIMD, so a
 workgroup fits a CU as often as a wave's registers fit a SIMD's 512 and its LDS the CU's 160 KB.  The Gram kernel holds two
@@ -7,40 +7,24 @@ workgroup fits a CU as often as a wave's registers fit a SIMD's 512 and its LDS 
 registers a lane: six workgroups a CU.  The other kernels use no LDS.  The projection holds the row, its
 correction and a vector in 3 x NV float64 a lane: at most 64 registers up to NV = 8 (eight workgroups a CU) and at most 128
 at NV = 16 (four)."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 from tests import helpers as H
 
-HIPCC = next((p for p in ("/opt/rocm/bin/hipcc", shutil.which("hipcc") or "") if p and os.path.exists(p)), None)
 VGPR_PER_SIMD = 512
 WAVES_PER_SIMD = 8
 LDS_PER_CU = 160 * 1024
 WG = 256                                         # SV_WG: one wave a SIMD
+PROJECT = "gd_svd_project_kernelINS_8SvLinearELi%sE"        # gd::gd_svd_project_kernel<gd::SvLinear, NV>
 
-pytestmark = pytest.mark.skipif(HIPCC is None, reason="needs hipcc")
+pytestmark = pytest.mark.skipif(H.HIPCC is None, reason="needs hipcc")
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    path = tmp_path_factory.mktemp("isa") / "api.s"
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                           "-I", os.path.join(H.ROOT, "include"), "-o", str(path),
-                           os.path.join(H.ROOT, "goleft_amd", "csrc", "gd_api.hip")], stderr=subprocess.DEVNULL)
-    asm = path.read_text()
-    meta = asm[asm.index("amdhsa.kernels:"):]
-    out = {}
-    for k in re.split(r"\n  - \.", meta)[1:]:
-        g = lambda key: re.search(r"\.%s:\s+(\S+)" % key, "." + k).group(1)
-        if "gd_svd_" in g("name"):
-            out[g("name")] = dict(lds=int(g("group_segment_fixed_size")), scratch=int(g("private_segment_fixed_size")),
-                                  vgpr=int(g("vgpr_count")), spill=int(g("vgpr_spill_count")),
-                                  wg=int(g("max_flat_workgroup_size")))
-    return out
+def kernels():
+    return {k: r for k, r in H.kernel_metadata(H.api_asm()).items() if "gd_svd_" in k and "SvLog2" not in k}
 
 
 def workgroups_per_cu(r):
@@ -60,7 +44,7 @@ def test_the_kernels_are_there(kernels):
     assert len(kernels) == 8, sorted(kernels)
     for part in ("gd_svd_rowstats_kernel", "gd_svd_gram_kernel", "gd_svd_gram_sum_kernel"):
         one(kernels, part)
-    nv = sorted(int(re.search(r"gd_svd_project_kernelILi(\d+)E", k).group(1)) for k in kernels if "project" in k)
+    nv = sorted(int(re.search(PROJECT % r"(\d+)", k).group(1)) for k in kernels if "project" in k)
     assert nv == [1, 2, 4, 8, 16]
 
 
@@ -75,9 +59,9 @@ def test_the_workgroups_a_cu_the_design_claims(kernels):
     gram = one(kernels, "gd_svd_gram_kernel")
     assert gram["vgpr"] <= 80 and gram["lds"] == 16384 and workgroups_per_cu(gram) == 6, gram
     for nv in (1, 2, 4, 8):
-        r = one(kernels, "gd_svd_project_kernelILi%dE" % nv)
+        r = one(kernels, PROJECT % nv)
         assert r["vgpr"] <= 64 and workgroups_per_cu(r) == 8, (nv, r)
-    r = one(kernels, "gd_svd_project_kernelILi16E")
+    r = one(kernels, PROJECT % 16)
     assert r["vgpr"] <= 128 and workgroups_per_cu(r) >= 4, r
     for part in ("gd_svd_rowstats_kernel", "gd_svd_gram_sum_kernel"):
         assert workgroups_per_cu(one(kernels, part)) == 8

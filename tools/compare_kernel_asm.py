@@ -3,9 +3,10 @@
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -I include -o before.s goleft_amd/csrc/gd_api.hip   # at the parent
     ... the same at the branch, -o after.s ...
-    tools/compare_kernel_asm.py before.s after.s [--strip TEXT ...]
+    tools/compare_kernel_asm.py before.s after.s [--strip TEXT ...] [--rename OLD=NEW ...]
 
-Kernels are matched by demangled name (--strip removes what a rename took out of the names, e.g. "4096, 256, "), bodies are
+Kernels are matched by demangled name (--strip removes what a rename took out of the names, e.g. "4096, 256, "; --rename
+replaces OLD by NEW in the names of the first file, in the order given, so that a kernel pairs up with what it became), bodies are
 compared instruction by instruction: comments, directives and basic-block label numbers do not count.  A kernel whose only
 differences are trailing immediates (the offset of a kernel argument or a struct's stride, after a field went) is marked."""
 import re
@@ -13,7 +14,7 @@ import subprocess
 import sys
 
 
-def kernels(path, strip):
+def kernels(path, strip, rename):
     text = open(path).read()
     names = re.findall(r"^\s*\.amdhsa_kernel (\S+)", text, re.M)
     dem = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.split("\n")
@@ -27,13 +28,16 @@ def kernels(path, strip):
                 ins.append(line)
         for s in ["void "] + strip:                  # (a kernel that stops being a template loses its return type)
             d = d.replace(s, "")
+        for old, new in rename:
+            d = d.replace(old, new)
         out[d] = ins
     return out
 
 
 def main():
     strip = [a for i, a in enumerate(sys.argv) if i and sys.argv[i - 1] == "--strip"]
-    a, b = (kernels(p, strip) for p in sys.argv[1:3])
+    rename = [a.split("=", 1) for i, a in enumerate(sys.argv) if i and sys.argv[i - 1] == "--rename"]
+    a, b = kernels(sys.argv[1], strip, rename), kernels(sys.argv[2], strip, [])
     same = [k for k in a if k in b and a[k] == b[k]]
     print("%d kernels before, %d after, %d identical" % (len(a), len(b), len(same)))
     imm = lambda ins: [re.sub(r"(, |offset:)(0x[0-9a-f]+|-?\d+)$", r"\1#", i) for i in ins]   # a trailing immediate operand
