@@ -38,6 +38,8 @@ SYMBOLS = {
     "gdh_scales_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p]),
     "gdh_debias_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_debias_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p]),
+    "gdh_cnveval_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
+    "gdh_cnveval_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p]),
     "gdh_samplename_main":(C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_crai_read": (C.c_int, [C.c_char_p, C.c_size_t, C.c_size_t, _P, _P, _P, _P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                 C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]),

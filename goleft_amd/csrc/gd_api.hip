@@ -5,7 +5,7 @@
 // timing.  The rest of the ABI is in the gd_api_*.inc files included at the end, in this order: records (pinned
 // staging ring + copy stream, records host -> HBM, HBM-resident per-contig record streams), compute (route, launch
 // sequencing, look-back), results (read-back), aux, ingest, covstats, indexcov, indexsplit, crai, devmat, emdepth, emcnv,
-// colselect, chunkdebias, movdebias, svddebias, comm.
+// colselect, chunkdebias, movdebias, svddebias, cnveval, comm.
 // Replaces gargs' process.Runner + the samtools child + the callback's parse loop of `goleft depth`
 // (depth/depth.go:392-394, :45, :282-325).
 #include "../../include/goleft_depth.h"
@@ -423,6 +423,7 @@ int gd_kernel_ms(gd_ctx* c, int id, float* ms)
 #include "gd_api_chunkdebias.inc"
 #include "gd_api_movdebias.inc"
 #include "gd_api_svddebias.inc"
+#include "gd_api_cnveval.inc"
 #include "gd_api_comm.inc"
 
 }  // extern "C"

@@ -269,6 +269,7 @@ struct gd_ctx {
     double md_secs[4] = {0, 0, 0, 0};                          // gd_moving_debias*: sort, upload, kernel, read-back of the last call (gd_api_movdebias.inc)
     int64_t md_segment = 0;                                    // GD_OPT_MOVDEBIAS_SEGMENT: sorted rows a workgroup owns (0: by the window)
     double sv_secs[5] = {0, 0, 0, 0, 0};                       // gd_svd_debias*: upload, statistics + Gram, eigenpairs (host), projection, read-back of the last call (gd_api_svddebias.inc)
+    double ce_secs[4] = {0, 0, 0, 0};                          // gd_cnveval: preparation + upload, kernels, read-back of the last call, and the first kernel's part of the second (gd_api_cnveval.inc)
     double em_secs[3] = {0, 0, 0};                             // gd_emdepth*: upload, kernel, read-back of the last call (gd_api_emdepth.inc)
     uint8_t* h_walk = nullptr; size_t cap_walk = 0;            // gd_ingest_decode, gd_covstats_decode: per-segment tables of the record walk (page-locked host memory
                                                                // the walk kernels read and write over the link: no copy command)

@@ -9,6 +9,7 @@
 //   goleft-depth emdepth [--scales FILE | --normalize [--level L]] [--cnvs FILE] matrix.bed[.gz]   (goleft's emdepth package: copy numbers per site of a depthwed matrix)
 //   goleft-depth scales [--level L] matrix.bed[.gz]                         (the factors emdepth --scales takes: dcnv's sample medians carried to one level)
 //   goleft-depth debias (--gc-values FILE | --fasta ref.fa) [--window W] matrix.bed[.gz]   (dcnv's ChunkDebiaser: the matrix freed of GC bias; emdepth takes the same as --gc-values | --gc-fasta, --gc-window)
+//   goleft-depth cnveval [-m MINOVERLAP] [-s] truth.bed[.gz] test.bed[.gz]   (the reference's cnveval command: precision and recall of a call set, per size class)
 //   goleft-depth samplename [-e] a.bam                                     (goleft samplename: the @RG SM values)
 //   samtools depth -Q q -d D -r REGION in.bam                   (the same program installed under the NAME samtools,
 //                                                                goleft_amd/shim/samtools: an unmodified goleft finds it on PATH)
@@ -88,6 +89,11 @@ int main(int argc, char** argv)
         av.push_back("samplename");
         for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
         return leave(gdh_samplename_main((int)av.size(), av.data()));
+    }
+    if (argc > 1 && strcmp(argv[1], "cnveval") == 0) {
+        av.push_back("cnveval");
+        for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
+        return leave(gdh_cnveval_main((int)av.size(), av.data()));
     }
     av.push_back("goleft depth");
     int first = 1;

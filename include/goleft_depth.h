@@ -39,7 +39,7 @@ extern "C" {
 
 /* GD_ABI_VERSION changes when an existing entry point or structure changes; GD_ABI_REVISION counts the releases that only
  * ADDED entry points since then (revision 1: gd_indexcov_*; 2: gd_indexsplit_*; 3: gd_crai_sizes).  A caller built against (15, r) runs on any (15, r' >= r).
- * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, gd_sample_medians*, gd_chunk_debias*, gd_device_scale, the *_device entries, gd_moving_debias*, gd_svd_debias* and gd_svd_debias_scaled*, were added without a revision; look them up by symbol.
+ * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, gd_sample_medians*, gd_chunk_debias*, gd_device_scale, the *_device entries, gd_moving_debias*, gd_svd_debias* and gd_svd_debias_scaled*, were added without a revision; look them up by symbol.  So were gd_cnveval and gd_cnveval_timing.
  * Why indexcov did not become version 16: nothing that existed changed, so callers of ABI 15 need not be turned away, and
  * tests/test_host_cpu.py holds gd_abi_version() to 15 until something does change. */
 #define GD_ABI_VERSION 15
@@ -853,6 +853,38 @@ int gd_svd_debias_scaled_cells(gd_ctx* ctx, const int64_t* d_cells, size_t n_row
 int gd_svd_debias_scaled_device(gd_ctx* ctx, const float* d_depths, size_t n_rows, int n_samples, double min_variance_pct,
                                 int scaler, float* d_out /* DEVICE [n_rows][n_samples]; may equal d_depths */, double* s,
                                 int* n_removed, float* centre_cells);
+/* ---- cnveval.Evaluate (cnveval/cnveval.go:163-341 of the reference): the calls of every sample
+ * scored against a truth set, on the device.  One host form: the inputs are kilobytes to megabytes.
+ *   samples     ids 0 .. n_samples - 1: the union of the samples of both sets.
+ *   calls       grouped by sample: sample s owns [cnv_off[s], cnv_off[s + 1]) of the four int32 arrays (chromosome rank,
+ *               start, end, copy number), in (chromosome rank, start) order within the sample -- where two calls of a
+ *               sample tie, the order given is the order taken.  A rank is any integer >= 0 that orders the chromosomes
+ *               as the caller wants them ordered (the reference: their names as byte strings), the same in both sets.
+ *   truths      n_truths intervals (rank, start, end, copy number) in any order; truth t names the samples
+ *               t_samples[t_off[t] .. t_off[t + 1]) -- a sample named twice counts twice, as in the reference.
+ *   min_overlap above 0, at most 1.
+ *   stats       host, [n_samples][3][4]: size class (length below 20000, below 100000, the rest) by FP, FN, TP, TN.  A
+ *               sample without calls is not evaluated: its twelve counts are 0.
+ * A call matches a truth on its chromosome when overlap / min(lengths) >= min_overlap (one float64 division; a zero
+ * length matches nothing) and the copy numbers are equal after those above 2 become 3.  The counts are the reference's
+ * to the last one, its quirks included, and two calls give the same bytes.
+ * Everything is checked before anything runs, and a refused call leaves stats untouched: min_overlap, the limits below,
+ * a negative start or rank, end < start or a sample id outside the samples GD_E_RANGE; offsets that do not start at 0 or
+ * decrease GD_E_INVALID; calls of a sample out of order GD_E_UNSORTED -- each with the index in gd_last_error.  No calls
+ * or no truths is valid.
+ * gd_cnveval_timing: seconds of the last call (measurement only): preparation and upload, kernels, read-back, and as a
+ * fourth value the part of the second that the first kernel (the truths that name a sample) took.  Fills min(n, 4) values. */
+#define GD_CNVEVAL_MAX_SAMPLES (1 << 20)
+#define GD_CNVEVAL_MAX_TRUTHS (1 << 24)
+#define GD_CNVEVAL_MAX_CNVS (1 << 26)
+#define GD_CNVEVAL_MAX_ENTRIES (1 << 28)        /* (truth, sample) namings */
+#define GD_CNVEVAL_MAX_MEMBER_WORDS (1 << 28)   /* n_truths * ceil(n_samples / 32): 1 GiB of membership bits */
+int gd_cnveval(gd_ctx* ctx, int32_t n_samples, const int64_t* cnv_off /* [n_samples + 1] */, const int32_t* cnv_chrom,
+               const int32_t* cnv_start, const int32_t* cnv_end, const int32_t* cnv_cn, size_t n_truths,
+               const int32_t* t_chrom, const int32_t* t_start, const int32_t* t_end, const int32_t* t_cn,
+               const int64_t* t_off /* [n_truths + 1] */, const int32_t* t_samples, double min_overlap,
+               int64_t* stats /* [n_samples][3][4] */);
+int gd_cnveval_timing(gd_ctx* ctx, double* out, size_t n);
 int gd_ingest_abort(gd_ctx* ctx);
 /* Page-locked host memory for the byte range handed to gd_ingest_bgzf (read the file
  * straight into it: the H2D copy then runs at PCIe speed instead of through a bounce

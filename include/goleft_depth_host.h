@@ -257,6 +257,19 @@ int gdh_crai_read(const char* path, size_t cap_refs, size_t cap_slices, int64_t*
  * unless there is exactly one.  1 when the file cannot be read, 255 on a usage error.  Opens no device. ---------- */
 int gdh_samplename_main(int argc, const char* const* argv);
 
+/* ---- `cnveval` (cnveval/cmd/cnveval/cnveval.go): precision and recall of a call set against a truth set, per size
+ * class, counted on the device (gd_cnveval).  argv: [-m MINOVERLAP] [-s] truth.bed[.gz] test.bed[.gz]; -m above 0 and at
+ * most 1 (default 0.4); -s keeps only the truth lines that name a sample of the test set.  Lines that start with '#' are
+ * skipped; the others hold chrom, start, end, copy number and comma-separated samples, tab-separated (a test line's sample
+ * is the first of its list).  A short or empty line, a number that is not an integer, a coordinate outside 0 .. 2^31 - 1
+ * and end < start are refused with file and line.  A last line without a newline is dropped as the reference drops it,
+ * with a note on stderr.  Stdout: the reference's four `size-class:` lines, byte for byte (0 / 0 prints NaN); stderr: its
+ * two log lines without the timestamp, and with GOLEFT_CNVEVAL_TIMING=1 the seconds of reading, upload, kernels and
+ * read-back.  Returns the exit code (1 on an error, with nothing written; 255 on a usage error). ---------------------- */
+int gdh_cnveval_main(int argc, const char* const* argv);
+/* Same, writing to out_path (NULL = stdout). */
+int gdh_cnveval_run(int argc, const char* const* argv, const char* out_path);
+
 /* ---- BAM decode (replaces the read side of the samtools child) ---------- */
 /* How `goleft-depth` cuts a BAM into device passes (host/gpu_ingest.hpp; exported for tests):
  * start[r] / has[r] describe the n_refs references of the file (offset of the BGZF member of r's first
