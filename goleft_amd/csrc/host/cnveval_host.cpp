@@ -6,10 +6,7 @@
 // samples ids (the union of both sets), ranks the chromosomes by their names as byte strings (so 10 < 2), sorts every
 // sample's calls by (rank, start) with a stable sort -- calls that tie keep their input order -- and prints the four
 // lines; the counting is gd_cnveval's, on the device.  The reference's x.cpu.pprof is not written.
-#include <zlib.h>
-
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -20,6 +17,7 @@
 
 #include "../../../include/goleft_depth.h"
 #include "../../../include/goleft_depth_host.h"
+#include "cli.hpp"
 
 namespace {
 
@@ -39,42 +37,30 @@ void usage(FILE* f)
 
 int parse_args(int argc, const char* const* argv, CArgs* a)
 {
-    for (int i = 1; i < argc; ++i) {
-        std::string arg = argv[i];
-        if (arg == "-h" || arg == "--help") { usage(stdout); return 1; }
-        if (arg == "--") { for (++i; i < argc; ++i) a->pos.push_back(argv[i]); break; }
-        if (arg.size() > 1 && arg[0] == '-') {
-            std::string key = arg, val;
-            bool has_val = false;
-            const size_t eq = arg.find('=');
-            if (eq != std::string::npos) { key = arg.substr(0, eq); val = arg.substr(eq + 1); has_val = true; }
-            if (key == "-s" || key == "--limitsamples") {
-                if (has_val) { fprintf(stderr, "error: %s takes no value\n", key.c_str()); usage(stderr); return -1; }
-                a->limit_samples = true;
-                continue;
-            }
-            if (key != "-m" && key != "--minoverlap") { fprintf(stderr, "error: unknown argument %s\n", arg.c_str()); usage(stderr); return -1; }
-            if (!has_val) {
-                if (i + 1 >= argc) { fprintf(stderr, "error: missing value for %s\n", key.c_str()); usage(stderr); return -1; }
-                val = argv[++i];
-            }
-            char* end = nullptr;
-            const double v = strtod(val.c_str(), &end);
-            if (val.empty() || *end || !(v > 0 && v <= 1)) {
-                fprintf(stderr, "error: %s %s: minoverlap must be between 0 and 1\n", key.c_str(), val.c_str());
-                usage(stderr);
-                return -1;
-            }
-            a->min_overlap = v;
+    using gdh::cli::Args;
+    Args c(argc, argv, usage);
+    for (;;) {
+        const Args::Kind kind = c.next();
+        if (kind == Args::End) break;
+        if (kind == Args::Help) return 1;
+        if (kind == Args::Positional) { a->pos.push_back(c.arg); continue; }
+        if (c.key == "-s" || c.key == "--limitsamples") {
+            if (c.has_val) return c.fail("%s takes no value", c.key.c_str());
+            a->limit_samples = true;
             continue;
         }
-        a->pos.push_back(arg);
+        if (c.key != "-m" && c.key != "--minoverlap") return c.fail("unknown argument %s", c.arg.c_str());
+        if (!c.value()) return -1;
+        char* end = nullptr;
+        const double v = strtod(c.val.c_str(), &end);
+        if (c.val.empty() || *end || !(v > 0 && v <= 1)) return c.fail("%s %s: minoverlap must be between 0 and 1", c.key.c_str(), c.val.c_str());
+        a->min_overlap = v;
     }
-    if (a->pos.size() != 2) { fprintf(stderr, "error: truth and test are required\n"); usage(stderr); return -1; }
+    if (a->pos.size() != 2) return c.fail("truth and test are required");
     return 0;
 }
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+using gdh::cli::now_s;
 
 struct Line {
     std::string chrom;
@@ -99,30 +85,17 @@ bool parse_int(const std::string& s, long long* out)
 // parseTruth (:65-107) without its filter: every line that ends in a newline and does not start with '#'
 int read_bed(const std::string& path, std::vector<Line>* out)
 {
-    gzFile f = gzopen(path.c_str(), "rb");       // (reads a plain file as it is)
-    if (!f) { fprintf(stderr, "cnveval: cannot open %s\n", path.c_str()); return 1; }
-    struct Close { gzFile f; ~Close() { gzclose(f); } } closer{f};
+    gdh::cli::Lines in;
+    if (!in.open(path)) { fprintf(stderr, "cnveval: cannot open %s\n", path.c_str()); return 1; }
     std::string line;
-    char buf[1 << 16];
-    long long lineno = 0;
-    for (;;) {
-        line.clear();
-        bool any = false, whole = false;
-        while (gzgets(f, buf, sizeof buf)) {
-            any = true;
-            const size_t n = strlen(buf);
-            line.append(buf, n);
-            if (n && buf[n - 1] == '\n') { whole = true; break; }
-        }
-        if (!any) break;
-        ++lineno;
-        if (!whole) {
+    const long long& lineno = in.lineno;
+    while (in.next(&line)) {
+        if (!in.whole) {
             // ReadString returns such a line together with io.EOF, and the reference's loop leaves on io.EOF first
             fprintf(stderr, "cnveval: %s:%lld: the last line has no newline and is not read, as in the reference\n", path.c_str(), lineno);
             break;
         }
-        if (line[0] == '#') continue;
-        while (!line.empty() && (line.back() == '\n' || line.back() == '\r')) line.pop_back();
+        if (line[0] == '#') continue;            // (an empty line has a NUL there)
         if (line.empty()) { fprintf(stderr, "cnveval: %s:%lld: an empty line\n", path.c_str(), lineno); return 1; }
         std::vector<std::string> tok;
         for (size_t b = 0;;) {
@@ -216,29 +189,20 @@ int run(const CArgs& a, FILE* out)
         t_off[t + 1] = (int64_t)t_samples.size();
     }
     const double t_read = now_s() - t_begin;
-    int device = 0;
-    if (const char* e = getenv("GOLEFT_DEVICE")) device = atoi(e);
-    gd_ctx* ctx = nullptr;
-    {
-        const int rc = gd_create(device, &ctx);
-        if (rc != GD_OK) {
-            fprintf(stderr, "cnveval: no usable MI355X device (%s); this build has no CPU path\n", gd_strerror(rc));
-            return 1;
-        }
-    }
+    gdh::cli::Device ctx;
+    if (!ctx.open("cnveval")) return 1;
     std::vector<int64_t> stats(S * 12, 0);
     {
         const int rc = gd_cnveval(ctx, (int32_t)S, cnv_off.data(), c_chrom.data(), c_start.data(), c_end.data(), c_cn.data(), T, t_chrom.data(),
                                   t_start.data(), t_end.data(), t_cn.data(), t_off.data(), t_samples.data(), a.min_overlap, stats.data());
         if (rc != GD_OK) {
             fprintf(stderr, "cnveval: gd_cnveval: %s (%s)\n", gd_strerror(rc), gd_last_error(ctx));
-            gd_destroy(ctx);
             return 1;
         }
     }
     double lib[3] = {0, 0, 0};
     (void)gd_cnveval_timing(ctx, lib, 3);
-    gd_destroy(ctx);
+    ctx.reset();
     // Tabulate (cnveval.go:118-133) and Stat.String (:93-96); '-' overrides '0' in %-04d: left-justified, space-padded
     int64_t tab[4][4] = {};
     for (size_t s = 0; s < S; ++s)
@@ -264,14 +228,7 @@ extern "C" int gdh_cnveval_run(int argc, const char* const* argv, const char* ou
     const int p = parse_args(argc, argv, &a);
     if (p > 0) return 0;
     if (p < 0) return 255;
-    FILE* out = stdout;
-    if (out_path) {
-        out = fopen(out_path, "w");
-        if (!out) { fprintf(stderr, "cnveval: cannot create %s\n", out_path); return 1; }
-    }
-    int r = run(a, out);
-    if (out_path) { if (fclose(out) != 0 && r == 0) r = 1; }
-    return r;
+    return gdh::cli::run_to_output("cnveval", out_path, [&](FILE* out) { return run(a, out); });
 }
 
 extern "C" int gdh_cnveval_main(int argc, const char* const* argv) { return gdh_cnveval_run(argc, argv, nullptr); }

@@ -12,7 +12,6 @@
 #include <zlib.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cinttypes>
 #include <cmath>
 #include <cstdio>
@@ -25,6 +24,7 @@
 #include "../../../include/goleft_depth.h"
 #include "../../../include/goleft_depth_host.h"
 #include "bam_reader.hpp"
+#include "cli.hpp"
 #include "gpu_ingest.hpp"
 #include "sample_names.hpp"
 
@@ -64,33 +64,20 @@ bool go_atoi(const std::string& s, int64_t* out)
 // 1: help printed, 0: parsed, -1: usage error
 int parse_args(int argc, const char* const* argv, CArgs* a)
 {
-    for (int i = 1; i < argc; ++i) {
-        std::string arg = argv[i];
-        if (arg == "-h" || arg == "--help") { usage(stdout); return 1; }
-        if (arg == "--") { for (++i; i < argc; ++i) a->bams.push_back(argv[i]); break; }
-        if (arg.size() > 1 && arg[0] == '-') {
-            std::string key = arg, val;
-            bool has_val = false;
-            const size_t eq = arg.find('=');
-            if (eq != std::string::npos) { key = arg.substr(0, eq); val = arg.substr(eq + 1); has_val = true; }
-            int which = -1;
-            if (key == "-n" || key == "--n") which = 0;
-            else if (key == "-r" || key == "--regions") which = 1;
-            else if (key == "-f" || key == "--fasta") which = 2;
-            if (which < 0) { fprintf(stderr, "error: unknown argument %s\n", arg.c_str()); usage(stderr); return -1; }
-            if (!has_val) {
-                if (i + 1 >= argc) { fprintf(stderr, "error: missing value for %s\n", key.c_str()); usage(stderr); return -1; }
-                val = argv[++i];
-            }
-            if (which == 0) {
-                if (!go_atoi(val, &a->n)) { fprintf(stderr, "error: error processing %s: invalid integer %s\n", key.c_str(), val.c_str()); usage(stderr); return -1; }
-            } else if (which == 1) a->regions = val;
-            else a->fasta = val;
-            continue;
-        }
-        a->bams.push_back(arg);
+    using gdh::cli::Args;
+    Args c(argc, argv, usage);
+    for (;;) {
+        const Args::Kind kind = c.next();
+        if (kind == Args::End) break;
+        if (kind == Args::Help) return 1;
+        if (kind == Args::Positional) { a->bams.push_back(c.arg); continue; }
+        std::string* const text = c.key == "-r" || c.key == "--regions" ? &a->regions : c.key == "-f" || c.key == "--fasta" ? &a->fasta : nullptr;
+        if (!text && c.key != "-n" && c.key != "--n") return c.fail("unknown argument %s", c.arg.c_str());
+        if (!c.value()) return -1;
+        if (text) *text = c.val;
+        else if (!go_atoi(c.val, &a->n)) return c.fail("error processing %s: invalid integer %s", c.key.c_str(), c.val.c_str());
     }
-    if (a->bams.empty()) { fprintf(stderr, "error: bams is required\n"); usage(stderr); return -1; }
+    if (a->bams.empty()) return c.fail("bams is required");
     return 0;
 }
 
@@ -335,7 +322,7 @@ int env_int(const char* name, int64_t dflt)
     return e && *e ? atoi(e) : (int)dflt;
 }
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+using gdh::cli::now_s;
 
 struct Timing { double list = 0, feed = 0, decode = 0, hist = 0, finish = 0; };
 
@@ -481,14 +468,8 @@ int run(const CArgs& a, FILE* out)
         fprintf(stderr, "covstats: %s: CRAM input is not supported (only BAM)\n", a.bams.front().c_str());
         return 1;
     }
-    int device = 0;
-    if (const char* e = getenv("GOLEFT_DEVICE")) device = atoi(e);
-    gd_ctx* ctx = nullptr;
-    const int rc = gd_create(device, &ctx);
-    if (rc != GD_OK) {
-        fprintf(stderr, "covstats: no usable MI355X device (%s); this build has no CPU path\n", gd_strerror(rc));
-        return 1;
-    }
+    gdh::cli::Device ctx;
+    if (!ctx.open("covstats")) return 1;
     Timing tm;
     const double t0 = now_s();
     int r = 0;
@@ -507,7 +488,6 @@ int run(const CArgs& a, FILE* out)
                         "\"lib_walk_scan_hist_s\": %.4f}\n",
                 now_s() - t0, tm.list, tm.feed, tm.decode, tm.hist, tm.finish, lib[0], lib[3], lib[4]);
     }
-    gd_destroy(ctx);
     return r;
 }
 
@@ -515,19 +495,13 @@ int run(const CArgs& a, FILE* out)
 
 extern "C" int gdh_covstats_run(int argc, const char* const* argv, const char* out_path)
 {
-    FILE* out = stdout;
-    if (out_path) {
-        out = fopen(out_path, "w");
-        if (!out) { fprintf(stderr, "covstats: cannot create %s\n", out_path); return 1; }
-    }
-    fputs(kHeader, out);                                     // before the arguments are parsed (:224-226)
-    fflush(out);
-    CArgs a;
-    const int p = parse_args(argc, argv, &a);
-    int r = p > 0 ? 0 : p < 0 ? 255 : run(a, out);
-    if (out_path) { if (fclose(out) != 0 && r == 0) r = 1; }
-    else fflush(stdout);
-    return r;
+    return gdh::cli::run_to_output("covstats", out_path, [&](FILE* out) {
+        fputs(kHeader, out);                                 // before the arguments are parsed (:224-226)
+        fflush(out);
+        CArgs a;
+        const int p = parse_args(argc, argv, &a);
+        return p > 0 ? 0 : p < 0 ? 255 : run(a, out);
+    });
 }
 
 extern "C" int gdh_covstats_main(int argc, const char* const* argv) { return gdh_covstats_run(argc, argv, nullptr); }

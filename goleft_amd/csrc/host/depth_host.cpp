@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "bam_reader.hpp"
+#include "cli.hpp"
 #include "fasta_stats.hpp"
 #include "gpu_ingest.hpp"
 
@@ -74,28 +75,22 @@ int parse_args(int argc, const char* const* argv, DArgs* a)
         {"--q", "-Q", 1}, {"--chrom", "-c", 2}, {"--mincov", nullptr, 1}, {"--stats", "-s", 0},
         {"--reference", "-r", 2}, {"--processes", "-p", 1}, {"--bed", "-b", 2}, {"--prefix", nullptr, 2}};
     std::vector<std::string> positional;
-    for (int i = 1; i < argc; ++i) {
-        std::string arg = argv[i];
-        if (arg == "--help" || arg == "-h") { usage(stdout); return 1; }
-        if (arg.size() < 2 || arg[0] != '-') { positional.push_back(arg); continue; }
-        std::string val;
-        bool has_val = false;
-        size_t eq = arg.find('=');
-        if (eq != std::string::npos) { val = arg.substr(eq + 1); arg = arg.substr(0, eq); has_val = true; }
+    using gdh::cli::Args;
+    Args c(argc, argv, usage, false);            // (no `--`: it is an unknown argument)
+    for (;;) {
+        const Args::Kind kind = c.next();
+        if (kind == Args::End) break;
+        if (kind == Args::Help) return 1;
+        if (kind == Args::Positional) { positional.push_back(c.arg); continue; }
+        const std::string &arg = c.key, &val = c.val;
+        const bool has_val = c.has_val;          // a flag may be written --flag=true
         const Opt* o = nullptr;
-        for (const Opt& c : opts)
-            if (arg == c.lng || (c.sht && arg == c.sht)) o = &c;
-        if (!o) { fprintf(stderr, "error: unknown argument %s\n", arg.c_str()); usage(stderr); return -1; }
-        if (o->kind != 0 && !has_val) {
-            if (i + 1 >= argc) { fprintf(stderr, "error: missing value for %s\n", arg.c_str()); usage(stderr); return -1; }
-            val = argv[++i];
-        }
+        for (const Opt& k : opts)
+            if (arg == k.lng || (k.sht && arg == k.sht)) o = &k;
+        if (!o) return c.fail("unknown argument %s", arg.c_str());
+        if (o->kind != 0 && !c.value()) return -1;
         int iv = 0;
-        if (o->kind == 1 && !parse_int(val.c_str(), &iv)) {
-            fprintf(stderr, "error: error processing %s: invalid integer %s\n", arg.c_str(), val.c_str());
-            usage(stderr);
-            return -1;
-        }
+        if (o->kind == 1 && !parse_int(val.c_str(), &iv)) return c.fail("error processing %s: invalid integer %s", arg.c_str(), val.c_str());
         const std::string n = o->lng;
         if (n == "--windowsize") a->window_size = iv;
         else if (n == "--maxmeandepth") a->max_mean_depth = iv;
@@ -109,10 +104,10 @@ int parse_args(int argc, const char* const* argv, DArgs* a)
         else if (n == "--bed") a->bed = val;
         else if (n == "--prefix") a->prefix = val;
     }
-    if (positional.size() > 1) { fprintf(stderr, "error: too many positional arguments at '%s'\n", positional[1].c_str()); usage(stderr); return -1; }
+    if (positional.size() > 1) return c.fail("too many positional arguments at '%s'", positional[1].c_str());
     if (positional.size() == 1) a->bam = positional[0];
-    if (a->prefix.empty()) { fprintf(stderr, "error: --prefix is required\n"); usage(stderr); return -1; }
-    if (a->bam.empty()) { fprintf(stderr, "error: bam is required\n"); usage(stderr); return -1; }
+    if (a->prefix.empty()) return c.fail("--prefix is required");
+    if (a->bam.empty()) return c.fail("bam is required");
     if (a->window_size < 1) { fprintf(stderr, "error: --windowsize must be >= 1\n"); return -1; }
     return 0;
 }

@@ -56,24 +56,25 @@
 // are this project's, the reference's UnScale returns depth + 1.  In log space a multiplicative bias is additive, and a site
 // where a few samples carry a CNV is not flattened before the cut sees it, as the z-score flattens it.  Not with --zscore.
 // `emdepth --svd PCT --log2` is `debias --svd PCT --log2 | emdepth --normalize`.
-#include <zlib.h>
-
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <string_view>
 #include <vector>
 
 #include "../../../include/goleft_depth.h"
 #include "../../../include/goleft_depth_host.h"
+#include "cli.hpp"
+#include "depth_matrix.hpp"
 #include "fasta_stats.hpp"
 
 namespace {
 
-enum { CMD_EMDEPTH = 0, CMD_SCALES = 1, CMD_DEBIAS = 2 };
+using gdh::Matrix;
+using gdh::cli::now_s;
 
 struct EArgs {
     std::string scales, cnvs, input, gc_values, gc_fasta;
@@ -140,265 +141,106 @@ bool parse_positive(const std::string& val, double* out)
     return end == val.c_str() + val.size() && std::isfinite(*out) && *out > 0;
 }
 
-// cmd: which entry's arguments these are (CMD_*)
-int parse_args(int argc, const char* const* argv, EArgs* a, int cmd)
-{
-    const auto usage = [cmd](FILE* f) { cmd == CMD_SCALES ? usage_scales(f) : cmd == CMD_DEBIAS ? usage_debias(f) : ::usage(f); };
-    const char* const fasta_key = cmd == CMD_DEBIAS ? "--fasta" : "--gc-fasta";
-    const char* const window_key = cmd == CMD_DEBIAS ? "--window" : "--gc-window";
-    const char* const moving_key = cmd == CMD_DEBIAS ? "--moving" : "--gc-moving";
-    std::vector<std::string> pos;
-    for (int i = 1; i < argc; ++i) {
-        std::string arg = argv[i];
-        if (arg == "-h" || arg == "--help") { usage(stdout); return 1; }
-        if (arg == "--") { for (++i; i < argc; ++i) pos.push_back(argv[i]); break; }
-        if (arg == "--normalize" && cmd == CMD_EMDEPTH) { a->normalize = true; continue; }
-        if (arg == "--zscore" && cmd == CMD_DEBIAS) { a->zscore = true; continue; }
-        if (arg == "--log2" && cmd != CMD_SCALES) { a->log2 = true; continue; }
-        if (arg.size() > 1 && arg[0] == '-') {
-            std::string key = arg, val;
-            bool has_val = false;
-            const size_t eq = arg.find('=');
-            if (eq != std::string::npos) { key = arg.substr(0, eq); val = arg.substr(eq + 1); has_val = true; }
-            const bool gc_key = key == "--gc-values" || key == fasta_key || key == window_key || key == moving_key;
-            const bool known = cmd == CMD_SCALES ? key == "--level"
-                             : cmd == CMD_DEBIAS ? gc_key || key == "--svd"
-                                                 : key == "--level" || key == "--scales" || key == "--cnvs" || gc_key || key == "--svd";
-            if (!known) {
-                fprintf(stderr, "error: unknown argument %s\n", arg.c_str());
-                usage(stderr);
-                return -1;
-            }
-            if (!has_val) {
-                if (i + 1 >= argc) { fprintf(stderr, "error: missing value for %s\n", key.c_str()); usage(stderr); return -1; }
-                val = argv[++i];
-            }
-            if (val.empty()) { fprintf(stderr, "error: empty value for %s\n", key.c_str()); usage(stderr); return -1; }
-            if (key == moving_key) {
-                char* end = nullptr;
-                const long v = strtol(val.c_str(), &end, 10);
-                if (end != val.c_str() + val.size() || v < 1 || v > 255 || v % 2 == 0) {
-                    fprintf(stderr, "error: %s must be an odd number of rows, 1 .. 255, not '%s'\n", key.c_str(), val.c_str());
-                    usage(stderr);
-                    return -1;
-                }
-                a->moving = (int)v;
-                a->has_moving = true;
-                continue;
-            }
-            if (key == "--svd") {
-                char* end = nullptr;
-                a->svd = strtod(val.c_str(), &end);
-                if (end != val.c_str() + val.size() || !std::isfinite(a->svd) || !(a->svd >= 0)) {
-                    fprintf(stderr, "error: --svd must be a finite share in per cent >= 0, not '%s'\n", val.c_str());
-                    usage(stderr);
-                    return -1;
-                }
-                a->has_svd = true;
-                continue;
-            }
-            if (key == "--level" || key == window_key) {
-                const bool level = key == "--level";
-                if (!parse_positive(val, level ? &a->level : &a->window)) {
-                    fprintf(stderr, "error: %s must be a finite number > 0, not '%s'\n", key.c_str(), val.c_str());
-                    usage(stderr);
-                    return -1;
-                }
-                (level ? a->has_level : a->has_window) = true;
-                continue;
-            }
-            (key == "--scales" ? a->scales : key == "--cnvs" ? a->cnvs : key == "--gc-values" ? a->gc_values : a->gc_fasta) = val;
-            continue;
-        }
-        pos.push_back(arg);
-    }
-    if (a->normalize && !a->scales.empty()) {
-        fprintf(stderr, "error: --normalize computes the factors that --scales reads: give one of them\n");
-        usage(stderr);
-        return -1;
-    }
-    if (!a->gc_values.empty() && !a->gc_fasta.empty()) {
-        fprintf(stderr, "error: --gc-values and %s both name the covariate: give one of them\n", fasta_key);
-        usage(stderr);
-        return -1;
-    }
-    if (cmd == CMD_DEBIAS && a->has_svd && (a->gc() || a->has_window || a->has_moving)) {
-        fprintf(stderr, "error: --svd takes no covariate and no window: run the two debiasers one after the other, by a pipe\n");
-        usage(stderr);
-        return -2;                               // (exit code 1: the flags are each valid)
-    }
-    if (a->zscore && !a->has_svd) {
-        fprintf(stderr, "error: --zscore is the scaler of --svd: it needs --svd PCT\n");
-        usage(stderr);
-        return -1;
-    }
-    if (a->log2 && !a->has_svd) {
-        fprintf(stderr, "error: --log2 is a scaler of --svd: it needs --svd PCT\n");
-        usage(stderr);
-        return -1;
-    }
-    if (a->log2 && a->zscore) {
-        fprintf(stderr, "error: --log2 and --zscore both name the scaler of --svd: give one of them\n");
-        usage(stderr);
-        return -1;
-    }
-    if (a->has_svd && !a->scales.empty()) {
-        fprintf(stderr, "error: --svd normalises after the debiasing, as --normalize does: --scales cannot be given with it\n");
-        usage(stderr);
-        return -1;
-    }
-    if (cmd == CMD_DEBIAS && !a->gc() && !a->has_svd) {
-        fprintf(stderr, "error: the covariate is required: --gc-values FILE or --fasta REF.fa\n");
-        usage(stderr);
-        return -1;
-    }
-    if (a->gc() && !a->scales.empty()) {
-        fprintf(stderr, "error: the GC flags normalise after the debiasing, as --normalize does: --scales cannot be given with them\n");
-        usage(stderr);
-        return -1;
-    }
-    if (a->has_window && !a->gc()) {
-        fprintf(stderr, "error: %s is the window of the debiasing: it needs --gc-values or %s\n", window_key, fasta_key);
-        usage(stderr);
-        return -1;
-    }
-    if (a->has_moving && !a->gc()) {
-        fprintf(stderr, "error: %s is the window of the debiasing: it needs --gc-values or %s\n", moving_key, fasta_key);
-        usage(stderr);
-        return -1;
-    }
-    if (a->has_moving && a->has_window) {
-        fprintf(stderr, "error: %s and %s choose the debiaser: give one of them\n", window_key, moving_key);
-        usage(stderr);
-        return -2;                               // (exit code 1: the two flags are each valid)
-    }
-    if ((a->gc() || a->has_svd) && cmd == CMD_EMDEPTH) a->normalize = true;
-    if (a->has_level && !a->normalize && cmd == CMD_EMDEPTH) {
-        fprintf(stderr, "error: --level sets the level --normalize carries the samples to: it needs --normalize\n");
-        usage(stderr);
-        return -1;
-    }
-    if (pos.size() != 1) { fprintf(stderr, "error: one matrix is required\n"); usage(stderr); return -1; }
-    a->input = pos[0];
-    return 0;
-}
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-// one line without its newline (and without a carriage return before it); false at the end of the file
-bool read_line(gzFile f, std::string* line)
-{
-    line->clear();
-    char buf[1 << 16];
-    bool any = false;
-    while (gzgets(f, buf, sizeof buf)) {
-        any = true;
-        const size_t n = strlen(buf);
-        line->append(buf, n);
-        if (n && buf[n - 1] == '\n') break;
-    }
-    while (!line->empty() && (line->back() == '\n' || line->back() == '\r')) line->pop_back();
-    return any;
-}
-
-// a finite number >= 0 that is all of [s, e) and still finite as a float32
-bool parse_factor(const char* s, const char* e, float* out)
-{
-    if (s == e) return false;
-    const std::string t(s, e);
-    char* end = nullptr;
-    const double v = strtod(t.c_str(), &end);
-    if (end != t.c_str() + t.size() || !std::isfinite(v) || !(v >= 0)) return false;
-    const float f = (float)v;
-    if (!std::isfinite(f)) return false;
-    *out = f;
-    return true;
-}
-
-struct Matrix {
-    std::string header;
-    size_t n = 0;                                // samples
-    std::vector<std::string> where;              // chrom \t start \t end of each row, as read
-    std::vector<long long> lineno;               // ... and the line it was read from
-    std::vector<float> depths;                   // [rows][n]
+// What a command takes: each flag by the name the command gives it, null where the flag is not its own.
+struct Command {
+    const char* prog;
+    void (*usage)(FILE*);
+    const char *normalize, *zscore, *log2;                                       // flags without a value
+    const char *scales, *cnvs, *level, *svd, *gc_values, *fasta, *window, *moving;
+    bool debiaser_required;                      // debias: a debiaser has to be named, and --svd stands without a covariate
 };
 
-int read_matrix(const std::string& path, Matrix* m)
+const Command kEmdepth = {"emdepth", usage, "--normalize", nullptr, "--log2",
+                          "--scales", "--cnvs", "--level", "--svd", "--gc-values", "--gc-fasta", "--gc-window", "--gc-moving", false};
+const Command kScales = {"scales", usage_scales, nullptr, nullptr, nullptr,
+                         nullptr, nullptr, "--level", nullptr, nullptr, nullptr, nullptr, nullptr, false};
+const Command kDebias = {"debias", usage_debias, nullptr, "--zscore", "--log2",
+                         nullptr, nullptr, nullptr, "--svd", "--gc-values", "--fasta", "--window", "--moving", true};
+
+// 0, 1 after the help, -1 for a usage error, -2 for two valid flags that do not go together (exit code 1)
+int parse_args(const Command& k, int argc, const char* const* argv, EArgs* a)
 {
-    gzFile f = gzopen(path.c_str(), "rb");       // (reads a plain file as it is)
-    if (!f) { fprintf(stderr, "emdepth: cannot open %s\n", path.c_str()); return 1; }
-    struct Close { gzFile f; ~Close() { gzclose(f); } } closer{f};
-    std::string line;
-    long long lineno = 0;
-    bool have_header = false;
-    while (read_line(f, &line)) {
-        ++lineno;
-        if (!have_header) {
-            // dcnv.go:173-175: the first line, '#...' or 'chrom...'; the samples are its fields from the fourth on
-            if (line.empty() || (line[0] != '#' && line.compare(0, 5, "chrom") != 0)) {
-                fprintf(stderr, "emdepth: %s: line 1 is not a '#chrom start end samples...' header\n", path.c_str());
-                return 1;
-            }
-            size_t tabs = 0;
-            for (char ch : line) tabs += ch == '\t';
-            if (tabs < 3) { fprintf(stderr, "emdepth: %s: the header names no samples\n", path.c_str()); return 1; }
-            m->n = tabs - 2;
-            m->header = line;
-            have_header = true;
-            if (m->n == 2) {
-                fprintf(stderr, "emdepth: %s has 2 samples: the reference's median of an even row reads b[N/2 + 1], which two values do not have (1 or 3 .. 4096 samples)\n", path.c_str());
-                return 1;
-            }
-            if (m->n > 4096) { fprintf(stderr, "emdepth: %s has %zu samples: 1 or 3 .. 4096\n", path.c_str(), m->n); return 1; }
+    using gdh::cli::Args;
+    Args c(argc, argv, k.usage);
+    const auto is = [&c](const char* name) { return name && c.key == name; };
+    std::vector<std::string> pos;
+    for (;;) {
+        const Args::Kind kind = c.next();
+        if (kind == Args::End) break;
+        if (kind == Args::Help) return 1;
+        if (kind == Args::Positional) { pos.push_back(c.arg); continue; }
+        if (!c.has_val && (is(k.normalize) || is(k.zscore) || is(k.log2))) {
+            (is(k.normalize) ? a->normalize : is(k.zscore) ? a->zscore : a->log2) = true;
             continue;
         }
-        if (line.empty()) continue;
-        const char* p = line.c_str();
-        const char* const end = p + line.size();
-        size_t field = 0;
-        const char* cells_at = nullptr;
-        const size_t at = m->depths.size();
-        m->depths.resize(at + m->n);
-        for (;;) {
-            const char* q = static_cast<const char*>(memchr(p, '\t', (size_t)(end - p)));
-            const char* fe = q ? q : end;
-            if (field == 3) cells_at = p;
-            if (field >= 3 && field < 3 + m->n && !parse_factor(p, fe, &m->depths[at + field - 3])) {
-                fprintf(stderr, "emdepth: %s: line %lld: column %zu is not a finite depth >= 0: '%.*s'\n", path.c_str(), lineno,
-                        field + 1, (int)(fe - p), p);
-                return 1;
-            }
-            ++field;
-            if (!q) break;
-            p = q + 1;
+        std::string* const text = is(k.scales) ? &a->scales : is(k.cnvs) ? &a->cnvs : is(k.gc_values) ? &a->gc_values : is(k.fasta) ? &a->gc_fasta : nullptr;
+        if (!text && !is(k.level) && !is(k.svd) && !is(k.window) && !is(k.moving)) return c.fail("unknown argument %s", c.arg.c_str());
+        if (!c.value()) return -1;
+        const std::string& val = c.val;
+        if (val.empty()) return c.fail("empty value for %s", c.key.c_str());
+        if (text) {
+            *text = val;
+        } else if (is(k.moving)) {
+            char* end = nullptr;
+            const long v = strtol(val.c_str(), &end, 10);
+            if (end != val.c_str() + val.size() || v < 1 || v > 255 || v % 2 == 0)
+                return c.fail("%s must be an odd number of rows, 1 .. 255, not '%s'", c.key.c_str(), val.c_str());
+            a->moving = (int)v;
+            a->has_moving = true;
+        } else if (is(k.svd)) {
+            char* end = nullptr;
+            a->svd = strtod(val.c_str(), &end);
+            if (end != val.c_str() + val.size() || !std::isfinite(a->svd) || !(a->svd >= 0))
+                return c.fail("--svd must be a finite share in per cent >= 0, not '%s'", val.c_str());
+            a->has_svd = true;
+        } else {
+            const bool level = is(k.level);
+            if (!parse_positive(val, level ? &a->level : &a->window))
+                return c.fail("%s must be a finite number > 0, not '%s'", c.key.c_str(), val.c_str());
+            (level ? a->has_level : a->has_window) = true;
         }
-        if (field != 3 + m->n) {
-            fprintf(stderr, "emdepth: %s: line %lld has %zu columns, the header has %zu\n", path.c_str(), lineno, field, 3 + m->n);
-            return 1;
-        }
-        m->where.emplace_back(line.c_str(), (size_t)(cells_at - 1 - line.c_str()));
-        m->lineno.push_back(lineno);
     }
-    if (!have_header) { fprintf(stderr, "emdepth: %s is empty\n", path.c_str()); return 1; }
+    // (in this order: an argv that trips two of them names the first)
+    if (a->normalize && !a->scales.empty()) return c.fail("--normalize computes the factors that --scales reads: give one of them");
+    if (!a->gc_values.empty() && !a->gc_fasta.empty()) return c.fail("--gc-values and %s both name the covariate: give one of them", k.fasta);
+    if (k.debiaser_required && a->has_svd && (a->gc() || a->has_window || a->has_moving)) {
+        c.fail("--svd takes no covariate and no window: run the two debiasers one after the other, by a pipe");
+        return -2;                               // (the flags are each valid)
+    }
+    if (a->zscore && !a->has_svd) return c.fail("--zscore is the scaler of --svd: it needs --svd PCT");
+    if (a->log2 && !a->has_svd) return c.fail("--log2 is a scaler of --svd: it needs --svd PCT");
+    if (a->log2 && a->zscore) return c.fail("--log2 and --zscore both name the scaler of --svd: give one of them");
+    if (a->has_svd && !a->scales.empty())
+        return c.fail("--svd normalises after the debiasing, as --normalize does: --scales cannot be given with it");
+    if (k.debiaser_required && !a->gc() && !a->has_svd) return c.fail("the covariate is required: --gc-values FILE or --fasta REF.fa");
+    if (a->gc() && !a->scales.empty())
+        return c.fail("the GC flags normalise after the debiasing, as --normalize does: --scales cannot be given with them");
+    if (a->has_window && !a->gc()) return c.fail("%s is the window of the debiasing: it needs --gc-values or %s", k.window, k.fasta);
+    if (a->has_moving && !a->gc()) return c.fail("%s is the window of the debiasing: it needs --gc-values or %s", k.moving, k.fasta);
+    if (a->has_moving && a->has_window) {
+        c.fail("%s and %s choose the debiaser: give one of them", k.window, k.moving);
+        return -2;                               // (the two flags are each valid)
+    }
+    if ((a->gc() || a->has_svd) && k.normalize) a->normalize = true;          // emdepth: a debiaser implies --normalize
+    if (a->has_level && !a->normalize && k.normalize) return c.fail("--level sets the level --normalize carries the samples to: it needs --normalize");
+    if (pos.size() != 1) return c.fail("one matrix is required");
+    a->input = pos[0];
     return 0;
 }
 
 int read_scales(const std::string& path, size_t n, std::vector<float>* out)
 {
-    gzFile f = gzopen(path.c_str(), "rb");
-    if (!f) { fprintf(stderr, "emdepth: cannot open %s\n", path.c_str()); return 1; }
-    struct Close { gzFile f; ~Close() { gzclose(f); } } closer{f};
+    gdh::cli::Lines in;
+    if (!in.open(path)) { fprintf(stderr, "emdepth: cannot open %s\n", path.c_str()); return 1; }
     std::string line;
-    long long lineno = 0;
-    while (read_line(f, &line)) {
-        ++lineno;
+    while (in.next(&line)) {
         size_t a = 0, b = line.size();
         while (a < b && (line[a] == ' ' || line[a] == '\t')) ++a;
         while (b > a && (line[b - 1] == ' ' || line[b - 1] == '\t')) --b;
         if (a == b) continue;
         float v;
-        if (!parse_factor(line.c_str() + a, line.c_str() + b, &v)) {
-            fprintf(stderr, "emdepth: %s: line %lld is not a finite factor >= 0\n", path.c_str(), lineno);
+        if (!gdh::parse_factor(line.c_str() + a, line.c_str() + b, &v)) {
+            fprintf(stderr, "emdepth: %s: line %lld is not a finite factor >= 0\n", path.c_str(), in.lineno);
             return 1;
         }
         out->push_back(v);
@@ -410,14 +252,14 @@ int read_scales(const std::string& path, size_t n, std::vector<float>* out)
     return 0;
 }
 
-// all of [s, e) as a decimal uint32
-bool parse_u32(const char* s, const char* e, uint32_t* out)
+// all of t as a decimal uint32
+bool parse_u32(std::string_view t, uint32_t* out)
 {
-    if (s == e) return false;
+    if (t.empty()) return false;
     uint64_t v = 0;
-    for (; s < e; ++s) {
-        if (*s < '0' || *s > '9') return false;
-        v = v * 10 + (uint64_t)(*s - '0');
+    for (const char ch : t) {
+        if (ch < '0' || ch > '9') return false;
+        v = v * 10 + (uint64_t)(ch - '0');
         if (v > 0xffffffffull) return false;
     }
     *out = (uint32_t)v;
@@ -427,35 +269,17 @@ bool parse_u32(const char* s, const char* e, uint32_t* out)
 // start and end of every row (emdepth.Position holds uint32 values)
 int parse_positions(const std::string& path, const Matrix& m, std::vector<uint32_t>* starts, std::vector<uint32_t>* ends)
 {
-    const size_t rows = m.where.size();
+    const size_t rows = m.rows();
     starts->resize(rows);
     ends->resize(rows);
     for (size_t r = 0; r < rows; ++r) {
-        const std::string& w = m.where[r];
-        const size_t t1 = w.find('\t'), t2 = t1 == std::string::npos ? t1 : w.find('\t', t1 + 1);
-        if (t2 == std::string::npos || !parse_u32(w.c_str() + t1 + 1, w.c_str() + t2, &(*starts)[r]) ||
-            !parse_u32(w.c_str() + t2 + 1, w.c_str() + w.size(), &(*ends)[r])) {
+        if (!parse_u32(m.start(r), &(*starts)[r]) || !parse_u32(m.end(r), &(*ends)[r])) {
             fprintf(stderr, "emdepth: %s: line %lld: --cnvs needs start and end as decimal numbers below 2^32\n", path.c_str(),
                     m.lineno[r]);
             return 1;
         }
     }
     return 0;
-}
-
-// the header's fields from the fourth on
-std::vector<std::string> sample_names(const Matrix& m)
-{
-    std::vector<std::string> names;
-    size_t at = 0;
-    for (int k = 0; k < 3; ++k) at = m.header.find('\t', at) + 1;
-    for (;;) {
-        const size_t q = m.header.find('\t', at);
-        names.push_back(m.header.substr(at, q == std::string::npos ? q : q - at));
-        if (q == std::string::npos) break;
-        at = q + 1;
-    }
-    return names;
 }
 
 // %.2f as Go prints it: the infinities are +Inf and -Inf
@@ -486,14 +310,12 @@ int format_cnvs(gd_ctx* ctx, const Matrix& m, uint64_t n_cnvs, uint64_t n_member
         snprintf(buf, sizeof buf, "\t%u\t%u\t%llu\t", sample[k], psize[k], (unsigned long long)(b - a));
         o += buf;
         for (uint64_t i = a; i < b; ++i) {
-            const std::string& w = m.where[row[i]];
-            const size_t t1 = w.find('\t'), t2 = w.find('\t', t1 + 1);
             if (i > a) o += ',';
-            o.append(w, 0, t1);
+            o.append(m.chrom(row[i]));
             o += ':';
-            o.append(w, t1 + 1, t2 - t1 - 1);
+            o.append(m.start(row[i]));
             o += '-';
-            o.append(w, t2 + 1, std::string::npos);
+            o.append(m.end(row[i]));
         }
         o += '\t';
         for (uint64_t i = a; i < b; ++i) { if (i > a) o += ','; o += (char)('0' + cn[i]); }
@@ -515,18 +337,6 @@ int write_text(const std::string& path, const std::string& o)
     return 0;
 }
 
-int open_device(const char* prog, gd_ctx** ctx)
-{
-    int device = 0;
-    if (const char* e = getenv("GOLEFT_DEVICE")) device = atoi(e);
-    const int rc = gd_create(device, ctx);
-    if (rc != GD_OK) {
-        fprintf(stderr, "%s: no usable MI355X device (%s); this build has no CPU path\n", prog, gd_strerror(rc));
-        return 1;
-    }
-    return 0;
-}
-
 // Every sample's factor: gd_sample_medians over the whole matrix, then N values of host work in float64.  The level T is
 // the middle median, sorted(med)[N / 2] -- the centre the reference's own scalers use (gmean, dcnv/scalers/scalers.go:
 // 126-130) -- or --level.  med and nonzero are left for the caller; secs: upload, kernels, read-back, passes.  level_out
@@ -534,7 +344,7 @@ int open_device(const char* prog, gd_ctx** ctx)
 int sample_scales(const char* prog, gd_ctx* ctx, const EArgs& a, const Matrix& m, std::vector<float>* scale,
                   std::vector<float>* med, std::vector<uint64_t>* nonzero, double* secs, double* level_out = nullptr)
 {
-    const size_t N = m.n, rows = m.where.size();
+    const size_t N = m.n, rows = m.rows();
     if (rows == 0) { fprintf(stderr, "%s: %s has no rows\n", prog, a.input.c_str()); return 1; }
     med->assign(N, 0.0f);
     nonzero->assign(N, 0);
@@ -571,18 +381,24 @@ int sample_scales(const char* prog, gd_ctx* ctx, const EArgs& a, const Matrix& m
     return 0;
 }
 
+void print_medians_timing(size_t rows, size_t N, const double* secs)
+{
+    fprintf(stderr, "{\"rows\": %zu, \"samples\": %zu, \"medians_upload_s\": %.4f, \"medians_kernels_s\": %.4f, "
+                    "\"medians_readback_s\": %.4f, \"medians_passes\": %d}\n",
+            rows, N, secs[0], secs[1], secs[2], (int)secs[3]);
+}
+
 int run_scales(const EArgs& a, FILE* out)
 {
     Matrix m;
     if (int rc = read_matrix(a.input, &m)) return rc;
-    gd_ctx* ctx = nullptr;
-    if (int rc = open_device("scales", &ctx)) return rc;
+    gdh::cli::Device ctx;
+    if (!ctx.open("scales")) return 1;
     std::vector<float> scale, med;
     std::vector<uint64_t> nonzero;
     double secs[4] = {0, 0, 0, 0};
-    const int rc = sample_scales("scales", ctx, a, m, &scale, &med, &nonzero, secs);
-    gd_destroy(ctx);
-    if (rc) return rc;
+    if (int rc = sample_scales("scales", ctx, a, m, &scale, &med, &nonzero, secs)) return rc;
+    ctx.reset();
     const std::vector<std::string> names = sample_names(m);
     std::string o;
     char buf[64];
@@ -592,23 +408,18 @@ int run_scales(const EArgs& a, FILE* out)
         o += buf;
     }
     if (fwrite(o.data(), 1, o.size(), out) != o.size() || fflush(out) != 0) { fprintf(stderr, "scales: error writing the factors\n"); return 1; }
-    if (getenv("GOLEFT_EMDEPTH_TIMING"))
-        fprintf(stderr, "{\"rows\": %zu, \"samples\": %zu, \"medians_upload_s\": %.4f, \"medians_kernels_s\": %.4f, "
-                        "\"medians_readback_s\": %.4f, \"medians_passes\": %d}\n",
-                m.where.size(), m.n, secs[0], secs[1], secs[2], (int)secs[3]);
+    if (getenv("GOLEFT_EMDEPTH_TIMING")) print_medians_timing(m.rows(), m.n, secs);
     return 0;
 }
 
 // --gc-values: one float64 per line, one line per row, in row order
 int read_vals(const char* prog, const std::string& path, size_t rows, std::vector<double>* out)
 {
-    gzFile f = gzopen(path.c_str(), "rb");
-    if (!f) { fprintf(stderr, "%s: cannot open %s\n", prog, path.c_str()); return 1; }
-    struct Close { gzFile f; ~Close() { gzclose(f); } } closer{f};
+    gdh::cli::Lines in;
+    if (!in.open(path)) { fprintf(stderr, "%s: cannot open %s\n", prog, path.c_str()); return 1; }
     std::string line;
-    long long lineno = 0;
-    while (read_line(f, &line)) {
-        ++lineno;
+    const long long& lineno = in.lineno;
+    while (in.next(&line)) {
         size_t a = 0, b = line.size();
         while (a < b && (line[a] == ' ' || line[a] == '\t')) ++a;
         while (b > a && (line[b - 1] == ' ' || line[b - 1] == '\t')) --b;
@@ -632,14 +443,14 @@ int read_vals(const char* prog, const std::string& path, size_t rows, std::vecto
     return 0;
 }
 
-// all of [s, e) as a decimal int64 below 2^62
-bool parse_i64(const char* s, const char* e, int64_t* out)
+// all of t as a decimal int64 below 2^62
+bool parse_i64(std::string_view t, int64_t* out)
 {
-    if (s == e) return false;
+    if (t.empty()) return false;
     int64_t v = 0;
-    for (; s < e; ++s) {
-        if (*s < '0' || *s > '9' || v > ((int64_t)1 << 58)) return false;
-        v = v * 10 + (int64_t)(*s - '0');
+    for (const char ch : t) {
+        if (ch < '0' || ch > '9' || v > ((int64_t)1 << 58)) return false;
+        v = v * 10 + (int64_t)(ch - '0');
     }
     *out = v;
     return true;
@@ -654,23 +465,20 @@ int fasta_vals(const char* prog, gd_ctx* ctx, const std::string& fasta, const st
     gdh::FastaStats fa;
     std::string err;
     if (!fa.open(fasta, &err)) { fprintf(stderr, "%s: %s\n", prog, err.c_str()); return 1; }
-    const size_t rows = m.where.size();
+    const size_t rows = m.rows();
     std::vector<std::string> chroms;             // in order of first appearance
     std::vector<std::vector<size_t>> rows_of;
     std::vector<int64_t> start(rows), end(rows);
     for (size_t r = 0; r < rows; ++r) {
-        const std::string& w = m.where[r];
-        const size_t t1 = w.find('\t'), t2 = t1 == std::string::npos ? t1 : w.find('\t', t1 + 1);
-        if (t2 == std::string::npos || !parse_i64(w.c_str() + t1 + 1, w.c_str() + t2, &start[r]) ||
-            !parse_i64(w.c_str() + t2 + 1, w.c_str() + w.size(), &end[r])) {
+        if (!parse_i64(m.start(r), &start[r]) || !parse_i64(m.end(r), &end[r])) {
             fprintf(stderr, "%s: %s: line %lld: --fasta needs start and end as decimal numbers\n", prog, path.c_str(), m.lineno[r]);
             return 1;
         }
         start[r] = std::max<int64_t>(start[r], 250) - 250;                     // dcnv.go:83-86
-        const std::string chrom = w.substr(0, t1);
+        const std::string_view chrom = m.chrom(r);
         size_t k = 0;
         while (k < chroms.size() && chroms[k] != chrom) ++k;
-        if (k == chroms.size()) { chroms.push_back(chrom); rows_of.emplace_back(); }
+        if (k == chroms.size()) { chroms.emplace_back(chrom); rows_of.emplace_back(); }
         rows_of[k].push_back(r);
     }
     const int contract = gdh_get_stats_contract();
@@ -705,7 +513,7 @@ int fasta_vals(const char* prog, gd_ctx* ctx, const std::string& fasta, const st
 // secs: gd_chunk_debias_timing's seven values.
 int debias_matrix(const char* prog, gd_ctx* ctx, const EArgs& a, Matrix* m, std::vector<double>* vals, double* secs)
 {
-    const size_t N = m->n, rows = m->where.size();
+    const size_t N = m->n, rows = m->rows();
     if (rows == 0) { fprintf(stderr, "%s: %s has no rows\n", prog, a.input.c_str()); return 1; }
     if (!a.gc_values.empty()) {
         if (int rc = read_vals(prog, a.gc_values, rows, vals)) return rc;
@@ -740,7 +548,7 @@ int svd_scaler(const EArgs& a, int none) { return a.log2 ? GD_SVD_SCALER_LOG2 : 
 // five values, then n.
 int svd_matrix(const char* prog, gd_ctx* ctx, const EArgs& a, int scaler, Matrix* m, double* secs)
 {
-    const size_t N = m->n, rows = m->where.size();
+    const size_t N = m->n, rows = m->rows();
     if (rows == 0) { fprintf(stderr, "%s: %s has no rows\n", prog, a.input.c_str()); return 1; }
     std::vector<float> out(rows * N);
     std::vector<double> s(std::min(rows, N));
@@ -777,24 +585,17 @@ int run_debias(const EArgs& a, FILE* out)
 {
     Matrix m;
     if (int rc = read_matrix(a.input, &m)) return rc;
-    gd_ctx* ctx = nullptr;
-    if (int rc = open_device("debias", &ctx)) return rc;
+    gdh::cli::Device ctx;
+    if (!ctx.open("debias")) return 1;
     std::vector<double> vals;
     double secs[7] = {0, 0, 0, 0, 0, 0, 0};
-    const int rc = a.has_svd ? svd_matrix("debias", ctx, a, svd_scaler(a, GD_SVD_SCALER_NONE), &m, secs) : debias_matrix("debias", ctx, a, &m, &vals, secs);
-    gd_destroy(ctx);
-    if (rc) return rc;
-    const size_t N = m.n, rows = m.where.size();
+    if (int rc = a.has_svd ? svd_matrix("debias", ctx, a, svd_scaler(a, GD_SVD_SCALER_NONE), &m, secs) : debias_matrix("debias", ctx, a, &m, &vals, secs))
+        return rc;
+    ctx.reset();                                 // before the rows are formatted and written
+    const size_t N = m.n, rows = m.rows();
     if (!a.gc_fasta.empty())                     // the covariate the FASTA gave, for the record: --gc-values takes it back
         for (size_t r = 0; r < rows; ++r) fprintf(stderr, "%s\t%.17g\n", m.where[r].c_str(), vals[r]);
-    std::string o = m.header;
-    o += '\n';
-    char buf[64];
-    for (size_t r = 0; r < rows; ++r) {
-        o += m.where[r];
-        for (size_t s = 0; s < N; ++s) { snprintf(buf, sizeof buf, "\t%.9g", (double)m.depths[r * N + s]); o += buf; }
-        o += '\n';
-    }
+    const std::string o = gdh::matrix_text(m);
     if (fwrite(o.data(), 1, o.size(), out) != o.size() || fflush(out) != 0) { fprintf(stderr, "debias: error writing the rows\n"); return 1; }
     if (getenv("GOLEFT_EMDEPTH_TIMING")) a.has_svd ? print_svd_timing(rows, N, secs) : print_debias_timing(rows, N, secs);
     return 0;
@@ -802,7 +603,7 @@ int run_debias(const EArgs& a, FILE* out)
 
 int apply_scales(Matrix* m, const std::vector<float>& scale)
 {
-    const size_t N = m->n, rows = m->where.size();
+    const size_t N = m->n, rows = m->rows();
     for (size_t r = 0; r < rows; ++r)
         for (size_t s = 0; s < N; ++s) {
             const float d = m->depths[r * N + s] * scale[s];            // float32, one rounding
@@ -821,7 +622,7 @@ int run(const EArgs& a, FILE* out)
     const double t_start = now_s();
     Matrix m;
     if (int rc = read_matrix(a.input, &m)) return rc;
-    const size_t N = m.n, rows = m.where.size();
+    const size_t N = m.n, rows = m.rows();
     if (!a.scales.empty()) {
         std::vector<float> scale;
         if (int rc = read_scales(a.scales, N, &scale)) return rc;
@@ -838,8 +639,8 @@ int run(const EArgs& a, FILE* out)
         if (v < 1) { fprintf(stderr, "emdepth: GOLEFT_EMDEPTH_ROWS must be at least 1\n"); return 1; }
         block = (size_t)v;
     }
-    gd_ctx* ctx = nullptr;
-    if (int rc = open_device("emdepth", &ctx)) return rc;
+    gdh::cli::Device ctx;
+    if (!ctx.open("emdepth")) return 1;
     double med_secs[4] = {0, 0, 0, 0}, gc_secs[7] = {0, 0, 0, 0, 0, 0, 0}, svd_secs[6] = {0, 0, 0, 0, 0, 0};
     EArgs norm = a;                              // what the normalisation after a debiasing is asked for
     if (a.gc()) {
@@ -854,17 +655,17 @@ int run(const EArgs& a, FILE* out)
         }
         std::vector<double> vals;
         if (rc == 0) rc = debias_matrix("emdepth", ctx, a, &m, &vals, gc_secs);
-        if (rc) { gd_destroy(ctx); return rc; }
+        if (rc) return rc;
     }
     if (a.has_svd)                               // always scaled: the rows below take no negative cell
-        if (int rc = svd_matrix("emdepth", ctx, a, svd_scaler(a, GD_SVD_SCALER_ZSCORE), &m, svd_secs)) { gd_destroy(ctx); return rc; }
+        if (int rc = svd_matrix("emdepth", ctx, a, svd_scaler(a, GD_SVD_SCALER_ZSCORE), &m, svd_secs)) return rc;
     if (a.normalize) {
         // the matrix goes up once for the medians and again, scaled, in its blocks
         std::vector<float> scale, med;
         std::vector<uint64_t> nonzero;
         int rc = sample_scales("emdepth", ctx, norm, m, &scale, &med, &nonzero, med_secs);
         if (rc == 0) rc = apply_scales(&m, scale);
-        if (rc) { gd_destroy(ctx); return rc; }
+        if (rc) return rc;
     }
     std::vector<uint8_t> cn(rows * N);
     double lib[3] = {0, 0, 0};
@@ -880,10 +681,9 @@ int run(const EArgs& a, FILE* out)
         if (rc == GD_OK) rc = gd_emcnv_finish(ctx, &n_cnvs, &n_members);
         if (rc != GD_OK) {
             fprintf(stderr, "emdepth: gd_emcnv: %s (%s)\n", gd_strerror(rc), gd_last_error(ctx));
-            gd_destroy(ctx);
             return 1;
         }
-        if (format_cnvs(ctx, m, n_cnvs, n_members, &cnv_text) != 0) { gd_destroy(ctx); return 1; }
+        if (format_cnvs(ctx, m, n_cnvs, n_members, &cnv_text) != 0) return 1;
         (void)gd_emcnv_timing(ctx, cnv_lib, 4);
     }
     for (size_t r0 = 0; !cnvs && r0 < rows; r0 += block) {
@@ -891,22 +691,15 @@ int run(const EArgs& a, FILE* out)
         const int rc = gd_emdepth(ctx, m.depths.data() + r0 * N, nb, (int)N, nullptr, nullptr, cn.data() + r0 * N, nullptr);
         if (rc != GD_OK) {
             fprintf(stderr, "emdepth: gd_emdepth: %s (%s)\n", gd_strerror(rc), gd_last_error(ctx));
-            gd_destroy(ctx);
             return 1;
         }
         double t[3] = {0, 0, 0};
         (void)gd_emdepth_timing(ctx, t, 3);
         for (int k = 0; k < 3; ++k) lib[k] += t[k];
     }
-    gd_destroy(ctx);
+    ctx.reset();                                 // before the rows are formatted and written
     const double t_write0 = now_s();
-    std::string o = m.header;
-    o += '\n';
-    for (size_t r = 0; r < rows; ++r) {
-        o += m.where[r];
-        for (size_t s = 0; s < N; ++s) { o += '\t'; o += (char)('0' + cn[r * N + s]); }     // 0 .. 9
-        o += '\n';
-    }
+    const std::string o = gdh::copy_number_text(m, cn);
     if (fwrite(o.data(), 1, o.size(), out) != o.size() || fflush(out) != 0) { fprintf(stderr, "emdepth: error writing the rows\n"); return 1; }
     if (cnvs) {                                  // after the rows: a run that fails leaves no calls file behind
         const double t0 = now_s();
@@ -915,10 +708,7 @@ int run(const EArgs& a, FILE* out)
     }
     if (timing && a.gc()) print_debias_timing(rows, N, gc_secs);
     if (timing && a.has_svd) print_svd_timing(rows, N, svd_secs);
-    if (timing && a.normalize)
-        fprintf(stderr, "{\"rows\": %zu, \"samples\": %zu, \"medians_upload_s\": %.4f, \"medians_kernels_s\": %.4f, "
-                        "\"medians_readback_s\": %.4f, \"medians_passes\": %d}\n",
-                rows, N, med_secs[0], med_secs[1], med_secs[2], (int)med_secs[3]);
+    if (timing && a.normalize) print_medians_timing(rows, N, med_secs);
     if (timing && cnvs)
         fprintf(stderr, "{\"rows\": %zu, \"samples\": %zu, \"block_rows\": %zu, \"total_s\": %.4f, \"read_s\": %.4f, \"upload_s\": %.4f, "
                         "\"kernel_s\": %.4f, \"cnv_kernels_s\": %.4f, \"readback_s\": %.4f, \"write_s\": %.4f, \"cnvs\": %llu, "
@@ -932,58 +722,22 @@ int run(const EArgs& a, FILE* out)
     return 0;
 }
 
+int run_command(const Command& k, int (*run_it)(const EArgs&, FILE*), int argc, const char* const* argv, const char* out_path)
+{
+    EArgs a;
+    const int p = parse_args(k, argc, argv, &a);
+    if (p > 0) return 0;
+    if (p < 0) return p == -2 ? 1 : 255;
+    return gdh::cli::run_to_output(k.prog, out_path, [&](FILE* out) { return run_it(a, out); });
+}
+
 }  // namespace
 
-extern "C" int gdh_emdepth_run(int argc, const char* const* argv, const char* out_path)
-{
-    EArgs a;
-    const int p = parse_args(argc, argv, &a, CMD_EMDEPTH);
-    if (p > 0) return 0;
-    if (p < 0) return p == -2 ? 1 : 255;
-    FILE* out = stdout;
-    if (out_path) {
-        out = fopen(out_path, "w");
-        if (!out) { fprintf(stderr, "emdepth: cannot create %s\n", out_path); return 1; }
-    }
-    int r = run(a, out);
-    if (out_path) { if (fclose(out) != 0 && r == 0) r = 1; }
-    return r;
-}
-
+extern "C" int gdh_emdepth_run(int argc, const char* const* argv, const char* out_path) { return run_command(kEmdepth, run, argc, argv, out_path); }
 extern "C" int gdh_emdepth_main(int argc, const char* const* argv) { return gdh_emdepth_run(argc, argv, nullptr); }
 
-extern "C" int gdh_scales_run(int argc, const char* const* argv, const char* out_path)
-{
-    EArgs a;
-    const int p = parse_args(argc, argv, &a, CMD_SCALES);
-    if (p > 0) return 0;
-    if (p < 0) return 255;
-    FILE* out = stdout;
-    if (out_path) {
-        out = fopen(out_path, "w");
-        if (!out) { fprintf(stderr, "scales: cannot create %s\n", out_path); return 1; }
-    }
-    int r = run_scales(a, out);
-    if (out_path) { if (fclose(out) != 0 && r == 0) r = 1; }
-    return r;
-}
-
+extern "C" int gdh_scales_run(int argc, const char* const* argv, const char* out_path) { return run_command(kScales, run_scales, argc, argv, out_path); }
 extern "C" int gdh_scales_main(int argc, const char* const* argv) { return gdh_scales_run(argc, argv, nullptr); }
 
-extern "C" int gdh_debias_run(int argc, const char* const* argv, const char* out_path)
-{
-    EArgs a;
-    const int p = parse_args(argc, argv, &a, CMD_DEBIAS);
-    if (p > 0) return 0;
-    if (p < 0) return p == -2 ? 1 : 255;
-    FILE* out = stdout;
-    if (out_path) {
-        out = fopen(out_path, "w");
-        if (!out) { fprintf(stderr, "debias: cannot create %s\n", out_path); return 1; }
-    }
-    int r = run_debias(a, out);
-    if (out_path) { if (fclose(out) != 0 && r == 0) r = 1; }
-    return r;
-}
-
+extern "C" int gdh_debias_run(int argc, const char* const* argv, const char* out_path) { return run_command(kDebias, run_debias, argc, argv, out_path); }
 extern "C" int gdh_debias_main(int argc, const char* const* argv) { return gdh_debias_run(argc, argv, nullptr); }

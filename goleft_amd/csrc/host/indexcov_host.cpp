@@ -15,7 +15,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cinttypes>
 #include <cmath>
 #include <cstdio>
@@ -32,6 +31,7 @@
 #include "../gd_eigh.hpp"
 #include "../gd_round3g.hpp"
 #include "bam_reader.hpp"
+#include "cli.hpp"
 #include "index_sizes.hpp"
 
 namespace {
@@ -65,44 +65,34 @@ using gdh::ends_with;
 
 int parse_args(int argc, const char* const* argv, IArgs* a)
 {
-    for (int i = 1; i < argc; ++i) {
-        std::string arg = argv[i];
-        if (arg == "-h" || arg == "--help") { usage(stdout); return 1; }
-        if (arg == "--") { for (++i; i < argc; ++i) a->inputs.push_back(argv[i]); break; }
-        if (arg.size() > 1 && arg[0] == '-') {
-            std::string key = arg, val;
-            bool has_val = false;
-            const size_t eq = arg.find('=');
-            if (eq != std::string::npos) { key = arg.substr(0, eq); val = arg.substr(eq + 1); has_val = true; }
-            if (key == "-e" || key == "--includegl") { a->include_gl = true; continue; }
-            if (key == "-n" || key == "--extranormalize") { a->extra_norm = true; continue; }
-            int which = -1;
-            if (key == "-d" || key == "--directory") which = 0;
-            else if (key == "-p" || key == "--excludepatt") which = 1;
-            else if (key == "-X" || key == "--sex") which = 2;
-            else if (key == "-f" || key == "--fai") which = 3;
-            else if (key == "-c" || key == "--chrom") which = 4;
-            if (which < 0) { fprintf(stderr, "error: unknown argument %s\n", arg.c_str()); usage(stderr); return -1; }
-            if (!has_val) {
-                if (i + 1 >= argc) { fprintf(stderr, "error: missing value for %s\n", key.c_str()); usage(stderr); return -1; }
-                val = argv[++i];
-            }
-            if (which == 4) {
-                fprintf(stderr, "indexcov: %s %s is not supported: the reference appends the chosen chromosome to the full list "
-                                "instead of filtering by it\n", key.c_str(), val.c_str());
-                return -2;
-            }
-            (which == 0 ? a->dir : which == 1 ? a->exclude : which == 2 ? a->sex : a->fai) = val;
-            continue;
+    using gdh::cli::Args;
+    Args c(argc, argv, usage);
+    for (;;) {
+        const Args::Kind kind = c.next();
+        if (kind == Args::End) break;
+        if (kind == Args::Help) return 1;
+        if (kind == Args::Positional) { a->inputs.push_back(c.arg); continue; }
+        const std::string& key = c.key;
+        if (key == "-e" || key == "--includegl") { a->include_gl = true; continue; }
+        if (key == "-n" || key == "--extranormalize") { a->extra_norm = true; continue; }
+        const bool chrom = key == "-c" || key == "--chrom";
+        std::string* const text = key == "-d" || key == "--directory" ? &a->dir : key == "-p" || key == "--excludepatt" ? &a->exclude
+                                : key == "-X" || key == "--sex" ? &a->sex : key == "-f" || key == "--fai" ? &a->fai : nullptr;
+        if (!text && !chrom) return c.fail("unknown argument %s", c.arg.c_str());
+        if (!c.value()) return -1;
+        if (chrom) {
+            fprintf(stderr, "indexcov: %s %s is not supported: the reference appends the chosen chromosome to the full list "
+                            "instead of filtering by it\n", key.c_str(), c.val.c_str());
+            return -2;
         }
-        a->inputs.push_back(arg);
+        *text = c.val;
     }
-    if (a->dir.empty()) { fprintf(stderr, "error: --directory is required\n"); usage(stderr); return -1; }
-    if (a->inputs.empty()) { fprintf(stderr, "error: bam is required\n"); usage(stderr); return -1; }
+    if (a->dir.empty()) return c.fail("--directory is required");
+    if (a->inputs.empty()) return c.fail("bam is required");
     return 0;
 }
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+using gdh::cli::now_s;
 
 bool mkdir_p(const std::string& path)
 {
@@ -260,7 +250,6 @@ const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 
         const int rc_ = (call);                                                                       \
         if (rc_ != GD_OK) {                                                                           \
             fprintf(stderr, "indexcov: %s: %s (%s)\n", #call, gd_strerror(rc_), gd_last_error(ctx));  \
-            gd_destroy(ctx);                                                                          \
             return 1;                                                                                 \
         }                                                                                             \
     } while (0)
@@ -340,15 +329,8 @@ int run(const IArgs& a)
     for (const Sample& s : smp)
         if (!s.err.empty()) { fprintf(stderr, "indexcov: %s\n", s.err.c_str()); return 1; }
     t_read = now_s() - t_start;
-    gd_ctx* ctx = nullptr;
-    auto open_device = [&]() -> bool {
-        if (ctx) return true;
-        int device = 0;
-        if (const char* e = getenv("GOLEFT_DEVICE")) device = atoi(e);
-        const int rc = gd_create(device, &ctx);
-        if (rc != GD_OK) fprintf(stderr, "indexcov: no usable MI355X device (%s); this build has no CPU path\n", gd_strerror(rc));
-        return rc == GD_OK;
-    };
+    gdh::cli::Device ctx;                        // opened where the first device call is
+    auto open_device = [&]() -> bool { return ctx || ctx.open("indexcov"); };
     double t_crai_read = 0, t_crai_tile = 0;
     {
         // the slices of the .crai indexes become tile sizes: one device call for all of them
@@ -360,7 +342,6 @@ int run(const IArgs& a)
             std::string err;
             if (!gdh::tile_crai_indexes(ctx, all, paths, &err, &t_crai_tile)) {
                 fprintf(stderr, "indexcov: %s\n", err.c_str());
-                gd_destroy(ctx);
                 return 1;
             }
         }
@@ -372,7 +353,7 @@ int run(const IArgs& a)
         if (has_exclude && std::regex_search(refs[r].name, exclude)) continue;
         kept.push_back(r);
     }
-    if (kept.empty()) { fprintf(stderr, "(FATAL) indexcov: every reference is excluded by %s\n", a.exclude.c_str()); gd_destroy(ctx); return 1; }
+    if (kept.empty()) { fprintf(stderr, "(FATAL) indexcov: every reference is excluded by %s\n", a.exclude.c_str()); return 1; }
     const size_t R = kept.size();
     std::vector<uint8_t> is_sex(R);
     for (size_t k = 0; k < R; ++k) is_sex[k] = same_chrom(sex, refs[kept[k]].name) ? 1 : 0;
@@ -401,7 +382,6 @@ int run(const IArgs& a)
     IC_CHECK(gd_indexcov_medians(ctx, median.data()));
     if (dims.m == 0) {                                                         // (the reference panics in mat.NewDense)
         fprintf(stderr, "(FATAL) indexcov: no reference that is not a sex chromosome is left: nothing for the principal components\n");
-        gd_destroy(ctx);
         return 1;
     }
     for (size_t s = 0; s < N; ++s)
@@ -441,7 +421,7 @@ int run(const IArgs& a)
     const std::string base = a.dir + "/" + base_name(a.dir) + "-indexcov";
     FILE* fb = fopen((base + ".bed.gz").c_str(), "wb");
     FILE* fr = fopen((base + ".roc").c_str(), "w");
-    if (!fb || !fr) { fprintf(stderr, "indexcov: cannot create %s.bed.gz / .roc\n", base.c_str()); gd_destroy(ctx); return 1; }
+    if (!fb || !fr) { fprintf(stderr, "indexcov: cannot create %s.bed.gz / .roc\n", base.c_str()); return 1; }
     bool io_ok = bgzf_write(fb, "#chrom\tstart\tend\t" + joined + "\n");
     std::map<std::string, std::vector<double>> sexes;
     std::vector<float> slopes(N, 0.f);
@@ -517,7 +497,7 @@ int run(const IArgs& a)
     io_ok = io_ok && fwrite(kBgzfEof, 1, sizeof kBgzfEof, fb) == sizeof kBgzfEof;
     io_ok = (fclose(fb) == 0) && io_ok;
     io_ok = (fclose(fr) == 0) && io_ok;
-    if (!io_ok) { fprintf(stderr, "indexcov: error writing %s.bed.gz / .roc\n", base.c_str()); gd_destroy(ctx); return 1; }
+    if (!io_ok) { fprintf(stderr, "indexcov: error writing %s.bed.gz / .roc\n", base.c_str()); return 1; }
     for (float& s : slopes) s = s / (float)n_slopes;
     // checkSexes (:760-771)
     if (sexes.size() != sex.size()) {
@@ -526,12 +506,12 @@ int run(const IArgs& a)
         const bool fatal = sexes.empty() && !(sex.size() == 2 && sex[0] == "X" && sex[1] == "Y");
         fprintf(stderr, "%s indexcov: expected %zu sex chromosomes, found: %zu.\nyou can set the expected with --sex '%s'\n",
                 fatal ? "(FATAL)" : "(WARNING)", sex.size(), sexes.size(), keys.c_str());
-        if (fatal) { gd_destroy(ctx); return 1; }
+        if (fatal) { return 1; }
     }
     if (sexes.empty()) fprintf(stderr, "sex chromosomes not found.\n");
     double lib[5] = {0, 0, 0, 0, 0};
     (void)gd_indexcov_timing(ctx, lib, 5);
-    gd_destroy(ctx);
+    ctx.reset();
     // the principal components (pca :773-807) from the exact Gram matrix
     std::vector<double> pcs;
     if (n_pc >= 3) {

@@ -9,7 +9,6 @@
 // sequential float64 (this library is built without fused multiply-adds).  Rows: chrom, start, end, %.2f sum, splits.
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cinttypes>
 #include <cmath>
 #include <cstdio>
@@ -22,6 +21,7 @@
 #include "../../../include/goleft_depth.h"
 #include "../../../include/goleft_depth_host.h"
 #include "bam_reader.hpp"
+#include "cli.hpp"
 #include "index_sizes.hpp"
 
 namespace {
@@ -51,46 +51,29 @@ void usage(FILE* f)
 
 int parse_args(int argc, const char* const* argv, SArgs* a)
 {
-    for (int i = 1; i < argc; ++i) {
-        std::string arg = argv[i];
-        if (arg == "-h" || arg == "--help") { usage(stdout); return 1; }
-        if (arg == "--") { for (++i; i < argc; ++i) a->inputs.push_back(argv[i]); break; }
-        if (arg.size() > 1 && arg[0] == '-') {
-            std::string key = arg, val;
-            bool has_val = false;
-            const size_t eq = arg.find('=');
-            if (eq != std::string::npos) { key = arg.substr(0, eq); val = arg.substr(eq + 1); has_val = true; }
-            int which = -1;
-            if (key == "-n" || key == "--n") which = 0;
-            else if (key == "--fai") which = 1;
-            else if (key == "-p" || key == "--problematic") which = 2;
-            if (which < 0) { fprintf(stderr, "error: unknown argument %s\n", arg.c_str()); usage(stderr); return -1; }
-            if (!has_val) {
-                if (i + 1 >= argc) { fprintf(stderr, "error: missing value for %s\n", key.c_str()); usage(stderr); return -1; }
-                val = argv[++i];
-            }
-            if (which == 0) {
-                char* end = nullptr;
-                const long long v = strtoll(val.c_str(), &end, 10);
-                if (val.empty() || *end || v < 1 || v > INT32_MAX) {
-                    fprintf(stderr, "error: %s %s: the number of regions is an integer from 1 to 2147483647\n", key.c_str(), val.c_str());
-                    usage(stderr);
-                    return -1;
-                }
-                a->n = v; a->has_n = true;
-            } else {
-                (which == 1 ? a->fai : a->problematic) = val;
-            }
-            continue;
-        }
-        a->inputs.push_back(arg);
+    using gdh::cli::Args;
+    Args c(argc, argv, usage);
+    for (;;) {
+        const Args::Kind kind = c.next();
+        if (kind == Args::End) break;
+        if (kind == Args::Help) return 1;
+        if (kind == Args::Positional) { a->inputs.push_back(c.arg); continue; }
+        std::string* const text = c.key == "--fai" ? &a->fai : c.key == "-p" || c.key == "--problematic" ? &a->problematic : nullptr;
+        if (!text && c.key != "-n" && c.key != "--n") return c.fail("unknown argument %s", c.arg.c_str());
+        if (!c.value()) return -1;
+        if (text) { *text = c.val; continue; }
+        char* end = nullptr;
+        const long long v = strtoll(c.val.c_str(), &end, 10);
+        if (c.val.empty() || *end || v < 1 || v > INT32_MAX)
+            return c.fail("%s %s: the number of regions is an integer from 1 to 2147483647", c.key.c_str(), c.val.c_str());
+        a->n = v; a->has_n = true;
     }
-    if (!a->has_n) { fprintf(stderr, "error: --n is required\n"); usage(stderr); return -1; }
-    if (a->inputs.empty()) { fprintf(stderr, "error: indexes is required\n"); usage(stderr); return -1; }
+    if (!a->has_n) return c.fail("--n is required");
+    if (a->inputs.empty()) return c.fail("indexes is required");
     return 0;
 }
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+using gdh::cli::now_s;
 
 struct Sample : gdh::IndexSizes { std::string err; };
 
@@ -122,7 +105,6 @@ void put_row(std::string* o, const std::string& chrom, int64_t start, int64_t en
         const int rc_ = (call);                                                                         \
         if (rc_ != GD_OK) {                                                                             \
             fprintf(stderr, "indexsplit: %s: %s (%s)\n", #call, gd_strerror(rc_), gd_last_error(ctx));  \
-            gd_destroy(ctx);                                                                            \
             return 1;                                                                                   \
         }                                                                                               \
     } while (0)
@@ -172,16 +154,8 @@ int run(const SArgs& a, FILE* out)
     for (const Sample& s : smp)
         if (!s.err.empty()) { fprintf(stderr, "indexsplit: %s\n", s.err.c_str()); return 1; }
     const double t_read = now_s() - t_start;
-    int device = 0;
-    if (const char* e = getenv("GOLEFT_DEVICE")) device = atoi(e);
-    gd_ctx* ctx = nullptr;
-    {
-        const int rc = gd_create(device, &ctx);
-        if (rc != GD_OK) {
-            fprintf(stderr, "indexsplit: no usable MI355X device (%s); this build has no CPU path\n", gd_strerror(rc));
-            return 1;
-        }
-    }
+    gdh::cli::Device ctx;
+    if (!ctx.open("indexsplit")) return 1;
     double t_crai_read = 0, t_crai_tile = 0;
     {
         // the slices of the .crai indexes become tile sizes: one device call for all of them
@@ -190,7 +164,6 @@ int run(const SArgs& a, FILE* out)
         std::string err;
         if (!gdh::tile_crai_indexes(ctx, all, a.inputs, &err, &t_crai_tile)) {
             fprintf(stderr, "indexsplit: %s\n", err.c_str());
-            gd_destroy(ctx);
             return 1;
         }
     }
@@ -226,7 +199,7 @@ int run(const SArgs& a, FILE* out)
     IS_CHECK(gd_indexsplit_sums(ctx, cells.data(), cells.size()));
     double lib[3] = {0, 0, 0};
     (void)gd_indexsplit_timing(ctx, lib, 3);
-    gd_destroy(ctx);
+    ctx.reset();
     const double t_scan0 = now_s();
     // getPercents (:52-66); floats.Sum is the sequential loop of gonum's portable build
     std::vector<double> sums(R, 0.0);
@@ -308,14 +281,7 @@ extern "C" int gdh_indexsplit_run(int argc, const char* const* argv, const char*
     const int p = parse_args(argc, argv, &a);
     if (p > 0) return 0;
     if (p < 0) return 255;
-    FILE* out = stdout;
-    if (out_path) {
-        out = fopen(out_path, "w");
-        if (!out) { fprintf(stderr, "indexsplit: cannot create %s\n", out_path); return 1; }
-    }
-    int r = run(a, out);
-    if (out_path) { if (fclose(out) != 0 && r == 0) r = 1; }
-    return r;
+    return gdh::cli::run_to_output("indexsplit", out_path, [&](FILE* out) { return run(a, out); });
 }
 
 extern "C" int gdh_indexsplit_main(int argc, const char* const* argv) { return gdh_indexsplit_run(argc, argv, nullptr); }

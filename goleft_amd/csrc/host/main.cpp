@@ -33,6 +33,15 @@ static int leave(int rc)
     _exit(rc);
 }
 
+// the subcommands: the word that selects one, the argv[0] its entry sees, the entry
+struct Entry { const char* subcommand; const char* argv0; int (*entry)(int, const char* const*); };
+static const Entry kEntries[] = {
+    {"depthwed", "goleft depthwed", gdh_depthwed_main}, {"multidepth", "multidepth", gdh_multidepth_main},
+    {"covstats", "covstats", gdh_covstats_main},        {"indexcov", "indexcov", gdh_indexcov_main},
+    {"indexsplit", "indexsplit", gdh_indexsplit_main},  {"emdepth", "emdepth", gdh_emdepth_main},
+    {"scales", "scales", gdh_scales_main},              {"debias", "debias", gdh_debias_main},
+    {"samplename", "samplename", gdh_samplename_main},  {"cnveval", "cnveval", gdh_cnveval_main}};
+
 int main(int argc, char** argv)
 {
     gdh_set_fast_exit(1);
@@ -45,56 +54,12 @@ int main(int argc, char** argv)
             return leave(gdh_samtools_main((int)av.size(), av.data()));
         }
     }
-    if (argc > 1 && strcmp(argv[1], "depthwed") == 0) {
-        av.push_back("goleft depthwed");
-        for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
-        return leave(gdh_depthwed_main((int)av.size(), av.data()));
-    }
-    if (argc > 1 && strcmp(argv[1], "multidepth") == 0) {
-        av.push_back("multidepth");
-        for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
-        return leave(gdh_multidepth_main((int)av.size(), av.data()));
-    }
-    if (argc > 1 && strcmp(argv[1], "covstats") == 0) {
-        av.push_back("covstats");
-        for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
-        return leave(gdh_covstats_main((int)av.size(), av.data()));
-    }
-    if (argc > 1 && strcmp(argv[1], "indexcov") == 0) {
-        av.push_back("indexcov");
-        for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
-        return leave(gdh_indexcov_main((int)av.size(), av.data()));
-    }
-    if (argc > 1 && strcmp(argv[1], "indexsplit") == 0) {
-        av.push_back("indexsplit");
-        for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
-        return leave(gdh_indexsplit_main((int)av.size(), av.data()));
-    }
-    if (argc > 1 && strcmp(argv[1], "emdepth") == 0) {
-        av.push_back("emdepth");
-        for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
-        return leave(gdh_emdepth_main((int)av.size(), av.data()));
-    }
-    if (argc > 1 && strcmp(argv[1], "scales") == 0) {
-        av.push_back("scales");
-        for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
-        return leave(gdh_scales_main((int)av.size(), av.data()));
-    }
-    if (argc > 1 && strcmp(argv[1], "debias") == 0) {
-        av.push_back("debias");
-        for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
-        return leave(gdh_debias_main((int)av.size(), av.data()));
-    }
-    if (argc > 1 && strcmp(argv[1], "samplename") == 0) {
-        av.push_back("samplename");
-        for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
-        return leave(gdh_samplename_main((int)av.size(), av.data()));
-    }
-    if (argc > 1 && strcmp(argv[1], "cnveval") == 0) {
-        av.push_back("cnveval");
-        for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
-        return leave(gdh_cnveval_main((int)av.size(), av.data()));
-    }
+    for (const Entry& e : kEntries)
+        if (argc > 1 && strcmp(argv[1], e.subcommand) == 0) {
+            av.push_back(e.argv0);
+            for (int i = 2; i < argc; ++i) av.push_back(argv[i]);
+            return leave(e.entry((int)av.size(), av.data()));
+        }
     av.push_back("goleft depth");
     int first = 1;
     if (argc > 1 && strcmp(argv[1], "depth") == 0) first = 2;

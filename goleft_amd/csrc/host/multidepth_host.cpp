@@ -25,6 +25,7 @@
 #include "../../../include/goleft_depth.h"
 #include "../../../include/goleft_depth_host.h"
 #include "bam_reader.hpp"
+#include "cli.hpp"
 #include "gpu_ingest.hpp"
 
 namespace {
@@ -56,33 +57,26 @@ int parse_args(int argc, const char* const* argv, MArgs* a)
         {"--q", "-Q", 1}, {"--chrom", "-c", 2}, {"--mincov", nullptr, 1}, {"--maxcov", nullptr, 1},
         {"--maxskip", "-k", 1}, {"--minsize", "-m", 1}, {"--window", "-w", 1}, {"--processes", "-p", 1},
         {"--minsamples", nullptr, 3}};
-    for (int i = 1; i < argc; ++i) {
-        std::string arg = argv[i];
-        if (arg == "--help" || arg == "-h") { usage(stdout); return 1; }
-        if (arg.size() < 2 || arg[0] != '-') { a->bams.push_back(arg); continue; }
-        std::string val;
-        bool has_val = false;
-        const size_t eq = arg.find('=');
-        if (eq != std::string::npos) { val = arg.substr(eq + 1); arg = arg.substr(0, eq); has_val = true; }
+    using gdh::cli::Args;
+    Args c(argc, argv, usage, false);            // (no `--`: it is an unknown argument)
+    for (;;) {
+        const Args::Kind kind = c.next();
+        if (kind == Args::End) break;
+        if (kind == Args::Help) return 1;
+        if (kind == Args::Positional) { a->bams.push_back(c.arg); continue; }
+        const std::string &arg = c.key, &val = c.val;
         const Opt* o = nullptr;
-        for (const Opt& c : opts)
-            if (arg == c.lng || (c.sht && arg == c.sht)) o = &c;
-        if (!o) { fprintf(stderr, "error: unknown argument %s\n", arg.c_str()); usage(stderr); return -1; }
-        if (!has_val) {
-            if (i + 1 >= argc) { fprintf(stderr, "error: missing value for %s\n", arg.c_str()); usage(stderr); return -1; }
-            val = argv[++i];
-        }
+        for (const Opt& k : opts)
+            if (arg == k.lng || (k.sht && arg == k.sht)) o = &k;
+        if (!o) return c.fail("unknown argument %s", arg.c_str());
+        if (!c.value()) return -1;
         char* end = nullptr;
         errno = 0;
         long iv = 0;
         double dv = 0;
         if (o->kind == 1) { iv = strtol(val.c_str(), &end, 10); }
         if (o->kind == 3) { dv = strtod(val.c_str(), &end); }
-        if (o->kind != 2 && (errno || end == val.c_str() || *end)) {
-            fprintf(stderr, "error: error processing %s: invalid value %s\n", arg.c_str(), val.c_str());
-            usage(stderr);
-            return -1;
-        }
+        if (o->kind != 2 && (errno || end == val.c_str() || *end)) return c.fail("error processing %s: invalid value %s", arg.c_str(), val.c_str());
         const std::string n = o->lng;
         if (n == "--q") a->q = (int)iv;
         else if (n == "--chrom") a->chrom = val;
@@ -94,8 +88,8 @@ int parse_args(int argc, const char* const* argv, MArgs* a)
         else if (n == "--processes") a->processes = (int)iv;
         else if (n == "--minsamples") a->min_samples = dv;
     }
-    if (a->chrom.empty()) { fprintf(stderr, "error: --chrom is required\n"); usage(stderr); return -1; }
-    if (a->bams.empty()) { fprintf(stderr, "error: bams is required\n"); usage(stderr); return -1; }   // :53-55
+    if (a->chrom.empty()) return c.fail("--chrom is required");
+    if (a->bams.empty()) return c.fail("bams is required");     // :53-55
     return 0;
 }
 
@@ -154,7 +148,6 @@ struct Block { int64_t start, end; };        // 0-based start, 1-based end (:175
         if (rc_ != GD_OK) {                                                             \
             fprintf(stderr, "multidepth: %s failed: %s (%s)\n", #call, gd_strerror(rc_), \
                     ctx ? gd_last_error(ctx) : "");                                     \
-            if (ctx) gd_destroy(ctx);                                                   \
             return 2;                                                                   \
         }                                                                               \
     } while (0)
@@ -162,7 +155,7 @@ struct Block { int64_t start, end; };        // 0-based start, 1-based end (:175
 int run(const MArgs& a, FILE* out)
 {
     const int S = (int)a.bams.size();
-    gd_ctx* ctx = nullptr;
+    gdh::cli::Device ctx;
     std::string err;
     // header names (:59-73) and the chromosome length from the first BAM (:32-49)
     std::vector<std::string> names((size_t)S);
@@ -193,15 +186,7 @@ int run(const MArgs& a, FILE* out)
     fputc('\n', out);
     if (L <= 0) return 0;
 
-    int device = 0;
-    if (const char* e = getenv("GOLEFT_DEVICE")) device = atoi(e);
-    {
-        const int rc = gd_create(device, &ctx);
-        if (rc != GD_OK) {
-            fprintf(stderr, "multidepth: no usable MI355X device (%s); this build has no CPU path\n", gd_strerror(rc));
-            return 2;
-        }
-    }
+    if (!ctx.open("multidepth")) return 2;
     gd_params P;
     gd_default_params(&P);
     P.min_mapq = a.q;                                       // samtools depth -Q (:205); -q 0 = no base-quality test
@@ -228,12 +213,12 @@ int run(const MArgs& a, FILE* out)
             }
         }
         gdh::BamReader br;
-        if (!br.open(a.bams[(size_t)s], a.processes, &err)) { fprintf(stderr, "multidepth: %s\n", err.c_str()); gd_destroy(ctx); return 2; }
+        if (!br.open(a.bams[(size_t)s], a.processes, &err)) { fprintf(stderr, "multidepth: %s\n", err.c_str()); return 2; }
         br.seek_contig(want, &err);                         // .bai shortcut when there is one
         gdh::RecordBlock blk;
         for (;;) {
             const int rc = br.next_block(blk, 1u << 21, &err);
-            if (rc < 0) { fprintf(stderr, "multidepth: %s\n", err.c_str()); gd_destroy(ctx); return 2; }
+            if (rc < 0) { fprintf(stderr, "multidepth: %s\n", err.c_str()); return 2; }
             if (rc == 0 || blk.tid > want) break;           // coordinate sorted: done
             if (blk.tid != want) continue;
             gd_batch b;
@@ -292,8 +277,8 @@ int run(const MArgs& a, FILE* out)
         for (size_t k = 0; k < nb; ++k)
             for (size_t t = 0; t < tids.size(); ++t) sums[k * (size_t)S + (size_t)tids[t]] = gsum[k * tids.size() + t];
     }
-    if (!gdh_get_fast_exit()) gd_destroy(ctx);             // (goleft-depth exits right after: main.cpp)
-    ctx = nullptr;
+    if (gdh_get_fast_exit()) ctx.release();                // (goleft-depth exits right after: main.cpp)
+    ctx.reset();
     for (size_t k = 0; k < blocks.size(); ++k) {
         fprintf(out, "%s\t%" PRId64 "\t%" PRId64, a.chrom.c_str(), blocks[k].start, blocks[k].end);   // :182-184
         const double l = (double)(blocks[k].end - blocks[k].start);                      // last.pos0 - first.pos0 + 1
@@ -313,15 +298,7 @@ int gdh_multidepth_run(int argc, const char* const* argv, const char* out_path)
     const int rc = parse_args(argc, argv, &a);
     if (rc > 0) return 0;
     if (rc < 0) return 255;           // go-arg MustParse -> os.Exit(-1)
-    FILE* out = stdout;
-    if (out_path) {
-        out = fopen(out_path, "w");
-        if (!out) { fprintf(stderr, "multidepth: cannot create %s\n", out_path); return 1; }
-    }
-    int r = run(a, out);
-    if (out_path) { if (fclose(out) != 0 && r == 0) r = 1; }
-    else fflush(stdout);
-    return r;
+    return gdh::cli::run_to_output("multidepth", out_path, [&](FILE* out) { return run(a, out); });
 }
 
 int gdh_multidepth_main(int argc, const char* const* argv) { return gdh_multidepth_run(argc, argv, nullptr); }
