@@ -1,11 +1,13 @@
 // gd_api.hip -- C ABI of the per-base depth engine (include/goleft_depth.h).
 //
 // Host-side runtime around the CDNA4 kernels of gd_kernels.hpp, one translation unit.  This file: status strings,
-// gd_create / gd_destroy, the setters (stream, parameters, path, outputs, contigs, selection), options, statistics and
-// timing.  The rest of the ABI is in the gd_api_*.inc files included at the end, in this order: records (pinned
-// staging ring + copy stream, records host -> HBM, HBM-resident per-contig record streams), compute (route, launch
-// sequencing, look-back), results (read-back), aux, ingest, covstats, indexcov, indexsplit, crai, devmat, emdepth, emcnv,
-// colselect, chunkdebias, movdebias, svddebias, cnveval, comm.
+// gd_create, the setters (stream, parameters, path, outputs, contigs, selection), options, statistics and timing; then
+// the gd_api_*.inc files with the rest of the ABI, in this order: records (pinned staging ring + copy stream, records
+// host -> HBM, HBM-resident per-contig record streams), compute (route, launch sequencing, look-back), results
+// (read-back), aux, ingest, covstats, indexcov, indexsplit, crai, devmat, emdepth, emcnv, colselect, chunkdebias,
+// movdebias, svddebias, cnveval, comm; and behind them, where every kept state is a complete type, gd_destroy.  What the
+// context holds is owned by its members (gd_own.hpp, gd_api_state.hpp): gd_destroy is the order of the teardown, the
+// context's destructor the inventory.
 // Replaces gargs' process.Runner + the samtools child + the callback's parse loop of `goleft depth`
 // (depth/depth.go:392-394, :45, :282-325).
 #include "../../include/goleft_depth.h"
@@ -94,21 +96,21 @@ int gd_create(int device_id, gd_ctx** out)
     };
     hipError_t e;
     if ((e = hipSetDevice(device_id)) != hipSuccess) return bail(e);
-    if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) return bail(e);
-    if ((e = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking)) != hipSuccess) return bail(e);
-    if ((e = hipEventCreateWithFlags(&c->copy_done, hipEventDisableTiming)) != hipSuccess) return bail(e);
+    if ((e = c->stream.create(hipStreamNonBlocking)) != hipSuccess) return bail(e);
+    if ((e = c->copy_stream.create(hipStreamNonBlocking)) != hipSuccess) return bail(e);
+    if ((e = c->copy_done.create(hipEventDisableTiming)) != hipSuccess) return bail(e);
     for (auto& s : c->ring)
-        if ((e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming)) != hipSuccess) return bail(e);
+        if ((e = s.done.create(hipEventDisableTiming)) != hipSuccess) return bail(e);
     for (auto& ev : c->ev)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) return bail(e);
-    if ((e = hipMalloc(reinterpret_cast<void**>(&c->d_counters), sizeof(gd::Counters))) != hipSuccess) return bail(e);
-    if ((e = hipMalloc(reinterpret_cast<void**>(&c->d_region_cursor), sizeof(uint32_t))) != hipSuccess) return bail(e);
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&c->h_counters), sizeof(gd::Counters), hipHostMallocDefault)) != hipSuccess) return bail(e);
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&c->h_bounds), kSpecBounds * sizeof(int2), hipHostMallocDefault)) != hipSuccess) return bail(e);
+        if ((e = ev.create(hipEventDefault)) != hipSuccess) return bail(e);
+    if ((e = c->d_counters.alloc(1)) != hipSuccess) return bail(e);
+    if ((e = c->d_region_cursor.alloc(1)) != hipSuccess) return bail(e);
+    if ((e = c->h_counters.alloc(1)) != hipSuccess) return bail(e);
+    if ((e = c->h_bounds.alloc(kSpecBounds)) != hipSuccess) return bail(e);
     if ((e = hipMemset(c->d_counters, 0, sizeof(gd::Counters))) != hipSuccess) return bail(e);
-    if ((e = hipMalloc(reinterpret_cast<void**>(&c->d_ingest), 4 * sizeof(uint32_t))) != hipSuccess) return bail(e);
+    if ((e = c->d_ingest.alloc(4)) != hipSuccess) return bail(e);
     if ((e = hipMemset(c->d_ingest, 0, 4 * sizeof(uint32_t))) != hipSuccess) return bail(e);
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&c->h_ingest), 4 * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess) return bail(e);
+    if ((e = c->h_ingest.alloc(4)) != hipSuccess) return bail(e);
     // Warm-up: one compute of an EMPTY two-tile contig runs every kernel of the tile path once (prep, slow list, straight-
     // line tile kernel, run ordering, read-back) and makes the small fixed-size allocations -- the first launch of a kernel in
     // a process costs tens of microseconds that a job of chr20's size (0.14 ms a step) saw as 1.3 x in its first, usually
@@ -133,73 +135,16 @@ int gd_create(int device_id, gd_ctx** out)
     return GD_OK;
 }
 
-namespace { static void drop_pool(gd_ctx* c); static void cov_drop(gd_ctx* c); static void ic_drop(gd_ctx* c); static void is_drop(gd_ctx* c); static void ec_drop(gd_ctx* c); }
-
-void gd_destroy(gd_ctx* c)
-{
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-    (void)gd_ingest_abort(c);
-    cov_drop(c);
-    ic_drop(c);
-    is_drop(c);
-    ec_drop(c);
-    (void)gd_comm_destroy(c);
-    for (hipEvent_t e : c->comm_ev) if (e) (void)hipEventDestroy(e);
-    for (int k = 0; k < 2; ++k) {
-        if (c->ing_stage[k]) (void)hipHostFree(c->ing_stage[k]);
-        if (c->ing_staged[k]) (void)hipEventDestroy(c->ing_staged[k]);
-        if (c->ing_hp_done[k]) (void)hipEventDestroy(c->ing_hp_done[k]);
-    }
-    for (hipStream_t st : c->ing_stream) if (st) (void)hipStreamDestroy(st);
-    if (c->ing_hp) (void)hipStreamDestroy(c->ing_hp);
-    for (auto& b : c->ing_bufs) b.drop_all();
-    if (c->h_walk) (void)hipHostFree(c->h_walk);
-    if (c->d_rectab) (void)hipFree(c->d_rectab);
-    if (c->h_ingest) (void)hipHostFree(c->h_ingest);
-    for (auto& h : c->contigs) free_contig(h);
-    for (auto& s : c->ring) {
-        if (s.b.pos) (void)hipHostFree(s.b.pos);
-        if (s.b.flag) (void)hipHostFree(s.b.flag);
-        if (s.b.mapq) (void)hipHostFree(s.b.mapq);
-        if (s.b.cigar_off) (void)hipHostFree(s.b.cigar_off);
-        if (s.b.cigar) (void)hipHostFree(s.b.cigar);
-        if (s.done) (void)hipEventDestroy(s.done);
-    }
-    for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);
-    if (c->copy_done) (void)hipEventDestroy(c->copy_done);
-    void* frees[] = {c->d_ctgs, c->d_tiles, c->d_ftiles, c->d_perbase, c->d_wsum, c->d_wmin, c->d_chunks,
-                     c->d_ordered, c->d_tile_cnt, c->d_tile_off, c->d_super_cnt, c->d_counters,
-                     c->d_region_cursor, c->d_status, c->d_seq, c->d_md_bits, c->d_md_cnt, c->d_wed, c->d_scan_tmp, c->d_ingest};
-    for (void* p : frees) if (p) (void)hipFree(p);
-    if (c->h_counters) (void)hipHostFree(c->h_counters);
-    if (c->h_bounds) (void)hipHostFree(c->h_bounds);
-    if (c->h_batch) (void)hipHostFree(c->h_batch);
-    drop_pool(c);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    delete c;
-}
-
 const char* gd_last_error(const gd_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 int gd_set_stream(gd_ctx* c, void* s)
 {
     if (!c) return GD_E_INVALID;
     if (int r = set_device(c)) return r;
-    if (c->own_stream && c->stream) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipStreamDestroy(c->stream));
-    }
-    if (s) {
-        c->stream = static_cast<hipStream_t>(s);
-        c->own_stream = false;
-    } else {
-        HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        c->own_stream = true;
-    }
+    if (c->stream.owned() && c->stream) HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->stream.reset_checked());                // (a caller's stream is let go of, never destroyed)
+    if (s) c->stream.borrow(static_cast<hipStream_t>(s));
+    else HIPCHK(c, c->stream.create(hipStreamNonBlocking));
     return GD_OK;
 }
 
@@ -249,8 +194,8 @@ int gd_set_contigs(gd_ctx* c, int n, const int64_t* lengths)
     if (int r = set_device(c)) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-    for (auto& h : c->contigs) free_contig(h);
-    c->contigs.assign(n, ContigHost());
+    c->contigs.clear();                                    // (frees what the contigs own)
+    c->contigs.resize(n);
     for (int i = 0; i < n; ++i) {
         if (lengths[i] < 0 || lengths[i] > GD_MAX_CONTIG_LENGTH)
             return fail(c, GD_E_RANGE, "contig %d length %lld out of range", i, (long long)lengths[i]);
@@ -426,4 +371,23 @@ int gd_kernel_ms(gd_ctx* c, int id, float* ms)
 #include "gd_api_cnveval.inc"
 #include "gd_api_comm.inc"
 
+void gd_destroy(gd_ctx* c)
+{
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+    (void)gd_ingest_abort(c);      // joins the reader thread; the pending IngestStates go before the IngestBufs they point into
+    drop_state(c, c->cov);
+    drop_state(c, c->ic);
+    drop_state(c, c->isp);
+    drop_state(c, c->ec);
+    (void)gd_comm_destroy(c);
+    drop_pool(c);
+    delete c;
+}
+
 }  // extern "C"
+
+gd_ctx::gd_ctx() = default;
+gd_ctx::~gd_ctx() = default;

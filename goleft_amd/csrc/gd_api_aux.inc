@@ -43,7 +43,7 @@ static int depthwed_on_device(gd_ctx* c, int n_samples, int n_ctg, const int32_t
     // small tables + the matrix live in one context-owned allocation
     const size_t n_tab = off.size() + nwin.size() + clen.size() + row_beg.size();
     const size_t n_cells = (size_t)rows * (size_t)n_samples;
-    if (int r = ensure_dev(c, &c->d_wed, &c->cap_wed, n_tab + n_cells)) return r;
+    if (int r = ensure_dev(c, c->d_wed, n_tab + n_cells)) return r;
     int64_t* d = c->d_wed;
     std::vector<int64_t> tab;
     tab.reserve(n_tab);
@@ -97,7 +97,7 @@ int gd_seq_load(gd_ctx* c, const uint8_t* seq, int64_t len)
     if (len >= 0x7fffffffLL - 16) return fail(c, GD_E_RANGE, "sequence of %lld bases (contigs are < 2^31)", (long long)len);
     if (int r = set_device(c)) return r;
     const size_t padded = (((size_t)len + 3) & ~(size_t)3) + 8;
-    if (int r = ensure_dev(c, &c->d_seq, &c->cap_seq, padded)) return r;
+    if (int r = ensure_dev(c, c->d_seq, padded)) return r;
     if (len) HIPCHK(c, hipMemcpyAsync(c->d_seq, seq, (size_t)len, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_seq + len, 0, padded - (size_t)len, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));          // the caller's buffer is not retained
@@ -186,13 +186,13 @@ int gd_md_flags(gd_ctx* c, int n_samples, const int32_t* tids, int32_t min_cov, 
         return fail(c, GD_E_CAPACITY, "need room for %zu bitmap words", need);
     c->md_len = -1;
     if (need == 0) { c->md_len = 0; c->md_tids.assign(tids, tids + n_samples); return GD_OK; }
-    if (int r = ensure_dev(c, &c->d_md_bits, &c->cap_md, 2 * need)) return r;
+    if (int r = ensure_dev(c, c->d_md_bits, 2 * need)) return r;
     DevBuf d_ptrs;
     if (int r = d_ptrs.alloc(c, ptrs.size() * sizeof(ptrs[0]))) return r;
     gd::MdFlagsJob j{};
     j.depth = d_ptrs.as<const int32_t*>(); j.n_samples = n_samples; j.len = len; j.min_cov = min_cov; j.min_samples = min_samples;
     j.any_bits = c->d_md_bits; j.suf_bits = c->d_md_bits + need;
-    HIPCHK(c, hipMemcpyAsync(d_ptrs.p, ptrs.data(), ptrs.size() * sizeof(ptrs[0]), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_ptrs.get(), ptrs.data(), ptrs.size() * sizeof(ptrs[0]), hipMemcpyHostToDevice, c->stream));
     if (c->profiling) (void)hipEventRecord(c->ev[0], c->stream);
     hipLaunchKernelGGL(gd::gd_md_flags_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, j);
     if (c->profiling) (void)hipEventRecord(c->ev[1], c->stream);
@@ -217,8 +217,8 @@ int gd_md_begin(gd_ctx* c, int64_t len)
     c->md_len = -1;
     c->md_tids.clear();
     c->md_acc_len = -1;
-    if (int r = ensure_dev(c, &c->d_md_bits, &c->cap_md, 2 * std::max<size_t>(need, 1))) return r;
-    if (int r = ensure_dev(c, &c->d_md_cnt, &c->cap_md_cnt, (size_t)std::max<int64_t>(len, 1))) return r;
+    if (int r = ensure_dev(c, c->d_md_bits, 2 * std::max<size_t>(need, 1))) return r;
+    if (int r = ensure_dev(c, c->d_md_cnt, (size_t)std::max<int64_t>(len, 1))) return r;
     HIPCHK(c, hipMemsetAsync(c->d_md_bits, 0, 2 * std::max<size_t>(need, 1) * sizeof(uint32_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_md_cnt, 0, (size_t)std::max<int64_t>(len, 1) * sizeof(uint16_t), c->stream));
     c->md_acc_len = len;
@@ -244,7 +244,7 @@ int gd_md_accumulate(gd_ctx* c, int n_samples, const int32_t* tids, int32_t min_
     gd::MdAccJob j{};
     j.depth = d_ptrs.as<const int32_t*>(); j.n_samples = n_samples; j.len = len; j.min_cov = min_cov;
     j.cnt = c->d_md_cnt; j.any_bits = c->d_md_bits;
-    HIPCHK(c, hipMemcpyAsync(d_ptrs.p, ptrs.data(), ptrs.size() * sizeof(ptrs[0]), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_ptrs.get(), ptrs.data(), ptrs.size() * sizeof(ptrs[0]), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(gd::gd_md_acc_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, j);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return GD_OK;
@@ -277,7 +277,7 @@ int gd_md_load_flags(gd_ctx* c, const uint32_t* any_bits, const uint32_t* suf_bi
     const size_t need = (size_t)((len + 31) / 32);
     c->md_len = -1;
     c->md_tids.clear();
-    if (int r = ensure_dev(c, &c->d_md_bits, &c->cap_md, 2 * std::max<size_t>(need, 1))) return r;
+    if (int r = ensure_dev(c, c->d_md_bits, 2 * std::max<size_t>(need, 1))) return r;
     if (need) {
         HIPCHK(c, hipMemcpyAsync(c->d_md_bits, any_bits, need * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->d_md_bits + need, suf_bits, need * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));

@@ -55,15 +55,15 @@ static int cd_run(gd_ctx* c, const float* depths, const int64_t* d_from, float* 
     if (int r = d_med.alloc(c, C * N * sizeof(uint32_t))) return r;
     if (!d_resident) if (int r = d_out.alloc(c, cells * sizeof(float))) return r;
     if (out64) if (int r = d_out64.alloc(c, cells * sizeof(double))) return r;
-    if (!d_resident) HIPCHK(c, hipMemcpyAsync(d_cells.p, depths, cells * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_order.p, order.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_slices.p, ch.slices.data(), (C + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_cor.p, ch.chunk_of_row.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (!d_resident) HIPCHK(c, hipMemcpyAsync(d_cells.get(), depths, cells * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_order.get(), order.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_slices.get(), ch.slices.data(), (C + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_cor.get(), ch.chunk_of_row.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cd_secs[1] = ing_now() - t1;
 
     gd::CdJob j{};
-    j.cells = static_cast<const uint32_t*>(d_resident ? (void*)d_resident : d_cells.p);
+    j.cells = static_cast<const uint32_t*>(d_resident ? (void*)d_resident : d_cells.get());
     j.n_rows = (int64_t)n_rows; j.n = n_samples; j.n_chunks = (uint32_t)C;
     j.order = d_order.as<const uint32_t>(); j.slices = d_slices.as<const uint32_t>();
     j.chunk_of_row = d_cor.as<const uint32_t>(); j.med = d_med.as<uint32_t>();
@@ -90,9 +90,9 @@ static int cd_run(gd_ctx* c, const float* depths, const int64_t* d_from, float* 
     c->cd_secs[2] = ing_now() - t2;
 
     const double t3 = ing_now();
-    if (out) HIPCHK(c, hipMemcpyAsync(out, d_out.p, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (out64) HIPCHK(c, hipMemcpyAsync(out64, d_out64.p, cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (med) HIPCHK(c, hipMemcpyAsync(med, d_med.p, C * N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (out) HIPCHK(c, hipMemcpyAsync(out, d_out.get(), cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (out64) HIPCHK(c, hipMemcpyAsync(out64, d_out64.get(), cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (med) HIPCHK(c, hipMemcpyAsync(med, d_med.get(), C * N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cd_secs[3] = ing_now() - t3;
     if (chunk_of_row) memcpy(chunk_of_row, ch.chunk_of_row.data(), n_rows * sizeof(uint32_t));

@@ -30,9 +30,9 @@ static int cs_run(gd_ctx* c, bool cells, const void* d_in, size_t n_rows, int n_
     if (int r = nonzero.alloc(c, N * sizeof(uint64_t))) return r;
     if (int r = flags.alloc(c, 2 * sizeof(uint32_t))) return r;
     const double t0 = ing_now();
-    HIPCHK(c, hipMemsetAsync(counts.p, 0, N * gd::CS_BINS * sizeof(uint32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(zeros.p, 0, N * sizeof(uint32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(flags.p, 0, 2 * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(counts.get(), 0, N * gd::CS_BINS * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(zeros.get(), 0, N * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(flags.get(), 0, 2 * sizeof(uint32_t), c->stream));
     gd::CsJob j{};
     j.cells = d_in; j.n_rows = (int64_t)n_rows; j.n = n_samples;
     j.counts = counts.as<uint32_t>(); j.zeros = zeros.as<uint32_t>(); j.prefix = prefix.as<uint64_t>(); j.rem = rem.as<int32_t>();
@@ -49,7 +49,7 @@ static int cs_run(gd_ctx* c, bool cells, const void* d_in, size_t n_rows, int n_
         hipLaunchKernelGGL((gd::gd_colselect_pick_kernel<gd::CS_PICK_LENGTH>), pgrid, pwg, 0, c->stream, j);
         HIPCHK(c, hipGetLastError());
         uint32_t seen[2] = {0, 0};
-        HIPCHK(c, hipMemcpyAsync(seen, flags.p, sizeof seen, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(seen, flags.get(), sizeof seen, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (seen[1]) return fail(c, GD_E_INVALID, "sample medians: a cell of the device matrix is negative");
         passes = (int)seen[0];                  // the longest answer, in bytes
@@ -64,13 +64,13 @@ static int cs_run(gd_ctx* c, bool cells, const void* d_in, size_t n_rows, int n_
         hipLaunchKernelGGL((gd::gd_colselect_pick_kernel<gd::CS_PICK_DIGIT>), pgrid, pwg, 0, c->stream, j);
     }
     HIPCHK(c, hipGetLastError());
-    if (d_prefix_out) HIPCHK(c, hipMemcpyAsync(d_prefix_out, prefix.p, N * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+    if (d_prefix_out) HIPCHK(c, hipMemcpyAsync(d_prefix_out, prefix.get(), N * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->sm_secs[1] = ing_now() - t0;
     c->sm_passes = 1 + passes;
     const double t1 = ing_now();
-    HIPCHK(c, hipMemcpyAsync(prefix_out, prefix.p, N * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (nonzero_out) HIPCHK(c, hipMemcpyAsync(nonzero_out, nonzero.p, N * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(prefix_out, prefix.get(), N * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (nonzero_out) HIPCHK(c, hipMemcpyAsync(nonzero_out, nonzero.get(), N * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->sm_secs[2] = ing_now() - t1;
     return GD_OK;
@@ -91,11 +91,11 @@ int gd_sample_medians(gd_ctx* c, const float* depths, size_t n_rows, int n_sampl
     DevBuf in;
     const double t0 = ing_now();
     if (int r = in.alloc(c, bytes)) return r;
-    HIPCHK(c, hipMemcpyAsync(in.p, depths, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(in.get(), depths, bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->sm_secs[0] = ing_now() - t0;
     std::vector<uint64_t> keys((size_t)n_samples);
-    if (int r = cs_run(c, false, in.p, n_rows, n_samples, keys.data(), n_nonzero)) return r;
+    if (int r = cs_run(c, false, in.get(), n_rows, n_samples, keys.data(), n_nonzero)) return r;
     mat_keys_to_float(keys, med);
     return GD_OK;
 }

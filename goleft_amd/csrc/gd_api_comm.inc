@@ -134,8 +134,8 @@ int gd_comm_init(gd_ctx* c, int rank, int world, const void* id, size_t bytes)
     c->comm = comm;
     c->comm_rank = rank;
     c->comm_world = world;
-    for (hipEvent_t& e : c->comm_ev)
-        if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (Event& e : c->comm_ev)
+        if (!e) HIPCHK(c, e.create(hipEventDisableTiming));
     c->comm_seq = 0;
     return GD_OK;
 }

@@ -15,9 +15,9 @@ static void compute_survey(gd_ctx* c, ComputeState& S)
         const ContigHost& h = c->contigs[tid];
         if (h.length <= 0) continue;
         if (h.n_reads)
-            S.raw_aligned = S.raw_aligned && (reinterpret_cast<uintptr_t>(h.pos) & 15u) == 0 &&
-                            (reinterpret_cast<uintptr_t>(h.off) & 15u) == 0 && (reinterpret_cast<uintptr_t>(h.flag) & 7u) == 0 &&
-                            (reinterpret_cast<uintptr_t>(h.mapq) & 3u) == 0;
+            S.raw_aligned = S.raw_aligned && (reinterpret_cast<uintptr_t>(h.pos.get()) & 15u) == 0 &&
+                            (reinterpret_cast<uintptr_t>(h.off.get()) & 15u) == 0 && (reinterpret_cast<uintptr_t>(h.flag.get()) & 7u) == 0 &&
+                            (reinterpret_cast<uintptr_t>(h.mapq.get()) & 3u) == 0;
     }
 }
 
@@ -121,39 +121,26 @@ static int compute_prepare(gd_ctx* c, ComputeState& S)
                     (long long)c->n_win_total, (long long)c->export_max_w);
 
     // ---- allocations -------------------------------------------------------
-    size_t cap;
-    if (int r = ensure_dev(c, &c->d_ctgs, &c->cap_ctgs, c->h_ctgs.size())) return r;
-    cap = c->cap_tiles;
-    if ((size_t)c->n_tiles > c->cap_tiles) {
-        size_t c1 = cap, c2 = cap, c3 = cap, c4 = cap;
-        if (int r = ensure_dev(c, &c->d_tiles, &c1, (size_t)c->n_tiles)) return r;
-        if (int r = ensure_dev(c, &c->d_tile_cnt, &c2, (size_t)c->n_tiles)) return r;
-        if (int r = ensure_dev(c, &c->d_tile_off, &c3, (size_t)c->n_tiles)) return r;
-        if (int r = ensure_dev(c, &c->d_super_cnt, &c4, (size_t)c->n_tiles / gd::SUPER + 1)) return r;
-        c->cap_tiles = c1;
-    }
+    // (every array is asked on its own whether it has the room: arrays of one size grow in the same calls)
+    if (int r = ensure_dev(c, c->d_ctgs, c->h_ctgs.size())) return r;
+    if (int r = ensure_dev(c, c->d_tiles, (size_t)c->n_tiles)) return r;
+    if (int r = ensure_dev(c, c->d_tile_cnt, (size_t)c->n_tiles)) return r;
+    if (int r = ensure_dev(c, c->d_tile_off, (size_t)c->n_tiles)) return r;
+    if (int r = ensure_dev(c, c->d_super_cnt, (size_t)c->n_tiles / gd::SUPER + 1)) return r;
     if (straight_line_allowed(c))                        // (allocations belong here, not in the enqueue)
-        if (int r = ensure_dev(c, &c->d_ftiles, &c->cap_ftiles, (size_t)c->n_tiles)) return r;
+        if (int r = ensure_dev(c, c->d_ftiles, (size_t)c->n_tiles)) return r;
     if (c->keep_perbase) {
-        if (int r = ensure_dev(c, &c->d_perbase, &c->cap_perbase, (size_t)S.base_off)) return r;
+        if (int r = ensure_dev(c, c->d_perbase, (size_t)S.base_off)) return r;
     } else if (c->d_perbase) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(c->d_perbase));        // windows-only: give the HBM back
-        c->d_perbase = nullptr;
-        c->cap_perbase = 0;
+        HIPCHK(c, c->d_perbase.reset_checked());     // windows-only: give the HBM back
     }
-    if ((size_t)S.win_off > c->cap_win || !c->d_wsum) {
-        size_t c1 = c->cap_win, c2 = c->cap_win;
-        if (int r = ensure_dev(c, &c->d_wsum, &c1, (size_t)std::max<int64_t>(S.win_off, 1))) return r;
-        if (int r = ensure_dev(c, &c->d_wmin, &c2, (size_t)std::max<int64_t>(S.win_off, 1))) return r;
-        c->cap_win = c1;
-    }
-    if (!c->d_chunks) {
-        size_t want = std::max<size_t>(1u << 16, (size_t)c->n_tiles * 2);
-        size_t c1 = 0, c2 = 0;
-        if (int r = ensure_dev(c, &c->d_chunks, &c1, want)) return r;
-        if (int r = ensure_dev(c, &c->d_ordered, &c2, want)) return r;
-        c->cap_runs = c1;
+    if (int r = ensure_dev(c, c->d_wsum, (size_t)std::max<int64_t>(S.win_off, 1))) return r;
+    if (int r = ensure_dev(c, c->d_wmin, (size_t)std::max<int64_t>(S.win_off, 1))) return r;
+    if (!c->d_ordered) {                                 // (the second of the two: with it the pair is whole)
+        const size_t want = std::max<size_t>(1u << 16, (size_t)c->n_tiles * 2);
+        if (int r = ensure_dev(c, c->d_chunks, want)) return r;
+        if (int r = ensure_dev(c, c->d_ordered, want)) return r;
     }
     // records staged on the copy stream must have landed
     HIPCHK(c, hipEventRecord(c->copy_done, c->copy_stream));
@@ -206,7 +193,7 @@ static int compute_enqueue(gd_ctx* c, ComputeState& S)
     job.win_min = c->d_wmin;
     job.n_win_total = c->n_win_total;
     job.run_chunks = c->d_chunks;
-    job.run_cap = (uint32_t)std::min<size_t>(c->cap_runs, 0xffffffffu);
+    job.run_cap = (uint32_t)std::min<size_t>(c->d_ordered.cap(), 0xffffffffu);
     job.tile_cnt = c->d_tile_cnt;
     job.tile_off = c->d_tile_off;
     job.super_cnt = c->d_super_cnt;
@@ -226,7 +213,7 @@ static int compute_enqueue(gd_ctx* c, ComputeState& S)
     // gd_prep_kernel counts slow tiles in n_slow[parity] and zeroes the OTHER counter for the next compute; a
     // compute that ran without it (scatter path, streaming sums, an enqueue that failed) leaves this one stale
     if (!c->slow_counter_clean)
-        HIPCHK(c, hipMemsetAsync((char*)c->d_counters + offsetof(gd::Counters, n_slow) + job.parity * sizeof(uint32_t),
+        HIPCHK(c, hipMemsetAsync(c->d_counters.as<char>() + offsetof(gd::Counters, n_slow) + job.parity * sizeof(uint32_t),
                                  0, sizeof(uint32_t), c->stream));
     c->slow_counter_clean = false;
 
@@ -258,7 +245,7 @@ static int compute_enqueue(gd_ctx* c, ComputeState& S)
     }
     job.n_units = (uint32_t)S.n_units;
     if (route == GD_TK_SCATTER) {
-        if (int r = ensure_dev(c, &c->d_status, &c->cap_status, (size_t)c->n_tiles)) return r;
+        if (int r = ensure_dev(c, c->d_status, (size_t)c->n_tiles)) return r;
         job.tile_status = c->d_status;
         if (int r = compute_stage(c, S, GD_K_PREP)) return r;
         // the per-base array doubles as the difference array: zero it, padding included
@@ -315,7 +302,7 @@ static int compute_enqueue(gd_ctx* c, ComputeState& S)
     // link, so that one synchronisation serves both.  Two hipMemcpyAsync did the same through the runtime's copy path,
     // whose first use behind running kernels cost the first gd_compute of a process 1.3 - 13 ms inside the enqueue
     // (measured box to box), and every later one two copy commands.
-    S.spec = std::min(kSpecBounds, c->cap_runs);
+    S.spec = std::min(kSpecBounds, c->d_ordered.cap());
     hipLaunchKernelGGL(gd::gd_readback_kernel, dim3(1), dim3(256), 0, c->stream, c->d_counters, c->d_ordered, (uint32_t)S.spec,
                        c->h_counters, c->h_bounds);
     HIPCHK(c, hipGetLastError());
@@ -360,12 +347,10 @@ static int compute_complete(gd_ctx* c, ComputeState& S)
             if (want * 2 <= c->lookback) c->lookback = want;
         }
     }
-    if ((size_t)k.run_cursor > c->cap_runs) {
-        size_t want = (size_t)k.run_cursor + (size_t)k.run_cursor / 8 + 1024;
-        size_t c1 = c->cap_runs, c2 = c->cap_runs;
-        if (int r = ensure_dev(c, &c->d_chunks, &c1, want)) return r;
-        if (int r = ensure_dev(c, &c->d_ordered, &c2, want)) return r;
-        c->cap_runs = c1;
+    if ((size_t)k.run_cursor > c->d_ordered.cap()) {
+        const size_t want = (size_t)k.run_cursor + (size_t)k.run_cursor / 8 + 1024;
+        if (int r = ensure_dev(c, c->d_chunks, want)) return r;
+        if (int r = ensure_dev(c, c->d_ordered, want)) return r;
         ++S.reruns;
         return 1;
     }

@@ -9,24 +9,10 @@ struct CovState {
     int64_t target = 0, skip_left = 0;
     gd_covstats_counts tot{};                  // over every range decoded since gd_covstats_begin
     std::vector<int64_t> ovf[3];               // overflow values read back after every range
-    void *d_slots = nullptr, *d_recs = nullptr, *d_role = nullptr, *d_tile = nullptr, *d_ovf = nullptr;
-    size_t cap_slots = 0, cap_recs = 0, cap_role = 0, cap_tile = 0, cap_ovf = 0;
-    unsigned long long* d_acc = nullptr;       // [CS_ACC_WORDS]
-    unsigned long long* d_hist = nullptr;      // [3 * CS_HBINS]
-    ~CovState()
-    {
-        void* frees[] = {d_slots, d_recs, d_role, d_tile, d_ovf, d_acc, d_hist};
-        for (void* p : frees) if (p) (void)hipFree(p);
-    }
+    DevArr<uint8_t> d_slots, d_recs, d_role, d_tile, d_ovf;   // in bytes (IngestBufs::fit)
+    DevArr<unsigned long long> d_acc;          // [CS_ACC_WORDS]
+    DevArr<unsigned long long> d_hist;         // [3 * CS_HBINS]
 };
-
-static void cov_drop(gd_ctx* c)
-{
-    if (!c->cov) return;
-    (void)hipStreamSynchronize(c->stream);
-    delete c->cov;
-    c->cov = nullptr;
-}
 
 // The virtual offset of byte b of the inflated range (b == total: where the member after the range begins).
 static uint64_t cov_at(const IngestState* g, uint64_t b)
@@ -43,12 +29,12 @@ int gd_covstats_begin(gd_ctx* c, int64_t n, int64_t skip)
     if (!c || skip < 0) return GD_E_INVALID;
     if (int r = set_device(c)) return r;
     if (!c->cov) {
-        c->cov = new (std::nothrow) CovState();
+        c->cov.reset(new (std::nothrow) CovState());
         if (!c->cov) return GD_E_NOMEM;
     }
     CovState& s = *c->cov;
-    if (!s.d_acc) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s.d_acc), gd::CS_ACC_WORDS * sizeof(unsigned long long)));
-    if (!s.d_hist) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s.d_hist), 3ull * gd::CS_HBINS * sizeof(unsigned long long)));
+    if (!s.d_acc) HIPCHK(c, s.d_acc.alloc(gd::CS_ACC_WORDS));
+    if (!s.d_hist) HIPCHK(c, s.d_hist.alloc(3ull * gd::CS_HBINS));
     HIPCHK(c, hipMemsetAsync(s.d_acc, 0, gd::CS_ACC_WORDS * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipMemsetAsync(s.d_hist, 0, 3ull * gd::CS_HBINS * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -89,7 +75,7 @@ int gd_covstats_decode(gd_ctx* c, uint64_t first_voffset, const uint64_t* anchor
     const double td1 = ing_now();
     // the walk's per-segment tables (page-locked: the kernels read and write them over the link)
     if (int r = ingest_walk_table(c, n_seg * (5 * sizeof(uint64_t) + 2 * sizeof(uint32_t)), "covstats")) return r;
-    uint64_t* t_beg = reinterpret_cast<uint64_t*>(c->h_walk);
+    uint64_t* t_beg = c->h_walk.as<uint64_t>();
     uint64_t* t_end = t_beg + n_seg;
     uint64_t* t_slot = t_end + n_seg;
     uint64_t* t_rbase = t_slot + n_seg;
@@ -103,11 +89,11 @@ int gd_covstats_decode(gd_ctx* c, uint64_t first_voffset, const uint64_t* anchor
         t_slot[i] = n_slots;
         n_slots += (t_end[i] - t_beg[i]) / 36 + 1;
     }
-    if (!IngestBufs::fit(&s.d_slots, &s.cap_slots, (size_t)n_slots * sizeof(gd::CsRec)))
+    if (!IngestBufs::fit(s.d_slots, (size_t)n_slots * sizeof(gd::CsRec)))
         return fail(c, GD_E_NOMEM, "device allocation for the covstats walk failed");
     gd::CsWalkJob wj{};
     wj.data = g->d_out; wj.n_bytes = total; wj.seg_beg = t_beg; wj.seg_end = t_end; wj.slot_base = t_slot;
-    wj.n_seg = (uint32_t)n_seg; wj.open_end = last_range ? 0u : 1u; wj.slots = static_cast<gd::CsRec*>(s.d_slots);
+    wj.n_seg = (uint32_t)n_seg; wj.open_end = last_range ? 0u : 1u; wj.slots = s.d_slots.as<gd::CsRec>();
     wj.n_rec = t_nrec; wj.end_off = t_endoff; wj.flags = t_flags;
     hipLaunchKernelGGL(gd::gd_cs_walk_kernel, dim3((unsigned)n_seg), dim3(64), 0, c->stream, wj);
     HIPCHK(c, hipGetLastError());
@@ -130,30 +116,30 @@ int gd_covstats_decode(gd_ctx* c, uint64_t first_voffset, const uint64_t* anchor
     if (s.target <= 0) {
         done = s.skip_left == 0;                             // the sampling loop does not run at all
     } else if (N > first) {
-        if (!IngestBufs::fit(&s.d_recs, &s.cap_recs, (size_t)N * sizeof(gd::CsRec)) ||
-            !IngestBufs::fit(&s.d_role, &s.cap_role, (size_t)N) ||
-            !IngestBufs::fit(&s.d_ovf, &s.cap_ovf, 3 * (size_t)N * sizeof(int64_t)))
+        if (!IngestBufs::fit(s.d_recs, (size_t)N * sizeof(gd::CsRec)) ||
+            !IngestBufs::fit(s.d_role, (size_t)N) ||
+            !IngestBufs::fit(s.d_ovf, 3 * (size_t)N * sizeof(int64_t)))
             return fail(c, GD_E_NOMEM, "device allocation for the covstats scan failed");
         const uint64_t n_tiles = (N + gd::CS_TILE - 1) / gd::CS_TILE;
         if (n_tiles > 0x7fffffffull) return fail(c, GD_E_RANGE, "too many records in one range");
-        if (!IngestBufs::fit(&s.d_tile, &s.cap_tile, (size_t)n_tiles * 24))
+        if (!IngestBufs::fit(s.d_tile, (size_t)n_tiles * 24))
             return fail(c, GD_E_NOMEM, "device allocation for the covstats scan failed");
         hipLaunchKernelGGL(gd::gd_cs_compact_kernel, dim3((unsigned)n_seg), dim3(256), 0, c->stream,
-                           static_cast<const gd::CsRec*>(s.d_slots), (const uint64_t*)t_slot, (const uint64_t*)t_rbase,
-                           (const uint32_t*)t_nrec, (uint32_t)n_seg, static_cast<gd::CsRec*>(s.d_recs));
+                           s.d_slots.as<const gd::CsRec>(), (const uint64_t*)t_slot, (const uint64_t*)t_rbase,
+                           (const uint32_t*)t_nrec, (uint32_t)n_seg, s.d_recs.as<gd::CsRec>());
         HIPCHK(c, hipGetLastError());
         // the stop word and the overflow counters start over in every range (the counts go on)
         const unsigned long long reset[gd::CS_ACC_WORDS - gd::CS_ACC_STOP] = {~0ull, 0, 0, 0, 0};
         HIPCHK(c, hipMemcpyAsync(s.d_acc + gd::CS_ACC_STOP, reset, sizeof reset, hipMemcpyHostToDevice, c->stream));
         gd::CsScanJob sj{};
-        sj.rec = static_cast<const gd::CsRec*>(s.d_recs); sj.n = N; sj.first = first; sj.target = s.target;
+        sj.rec = s.d_recs.as<const gd::CsRec>(); sj.n = N; sj.first = first; sj.target = s.target;
         sj.sizes0 = s.tot.sizes; sj.ins0 = s.tot.inserts;
-        uint64_t* tw = static_cast<uint64_t*>(s.d_tile);
+        uint64_t* tw = s.d_tile.as<uint64_t>();
         sj.pre_g = tw; sj.pre_e = tw + n_tiles;
         sj.tile_g = reinterpret_cast<uint32_t*>(tw + 2 * n_tiles); sj.tile_e = sj.tile_g + n_tiles;
         sj.n_tiles = (uint32_t)n_tiles;
-        sj.role = static_cast<uint8_t*>(s.d_role); sj.acc = s.d_acc; sj.hist = s.d_hist;
-        sj.ovf = static_cast<int64_t*>(s.d_ovf); sj.ovf_cap = N;
+        sj.role = s.d_role.as<uint8_t>(); sj.acc = s.d_acc; sj.hist = s.d_hist;
+        sj.ovf = s.d_ovf.as<int64_t>(); sj.ovf_cap = N;
         hipLaunchKernelGGL(gd::gd_cs_tile_kernel, dim3((unsigned)n_tiles), dim3(256), 0, c->stream, sj);
         hipLaunchKernelGGL(gd::gd_cs_tscan_kernel, dim3(1), dim3(256), 0, c->stream, sj);
         hipLaunchKernelGGL(gd::gd_cs_select_kernel, dim3((unsigned)n_tiles), dim3(256), 0, c->stream, sj);
@@ -169,7 +155,7 @@ int gd_covstats_decode(gd_ctx* c, uint64_t first_voffset, const uint64_t* anchor
             std::vector<int64_t>& v = s.ovf[k];
             const size_t at = v.size();
             v.resize(at + (size_t)m);
-            HIPCHK(c, hipMemcpy(v.data() + at, static_cast<int64_t*>(s.d_ovf) + (size_t)k * N, (size_t)m * sizeof(int64_t),
+            HIPCHK(c, hipMemcpy(v.data() + at, s.d_ovf.as<int64_t>() + (size_t)k * N, (size_t)m * sizeof(int64_t),
                                 hipMemcpyDeviceToHost));
         }
         s.tot.unmapped = (int64_t)acc[0]; s.tot.counted = (int64_t)acc[1]; s.tot.bad = (int64_t)acc[2];

@@ -34,11 +34,11 @@ int gd_crai_sizes(gd_ctx* c, int32_t n_seq, const int64_t* seq_off, const int64_
     if (int r = d_start.alloc(c, (size_t)L * sizeof(int64_t))) return r;
     if (int r = d_span.alloc(c, (size_t)L * sizeof(int64_t))) return r;
     if (int r = d_len.alloc(c, (size_t)L * sizeof(int32_t))) return r;
-    HIPCHK(c, hipMemcpyAsync(d_seq_off.p, seq_off, (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_seq_off.get(), seq_off, (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     if (L > 0) {
-        HIPCHK(c, hipMemcpyAsync(d_start.p, aln_start, (size_t)L * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_span.p, aln_span, (size_t)L * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_len.p, slice_len, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_start.get(), aln_start, (size_t)L * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_span.get(), aln_span, (size_t)L * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_len.get(), slice_len, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     }
     gd::CraiJob j{};
     j.n_seq = n_seq;
@@ -47,8 +47,8 @@ int gd_crai_sizes(gd_ctx* c, int32_t n_seq, const int64_t* seq_off, const int64_
     const unsigned grid = (unsigned)std::min<size_t>((S + gd::CRAI_WAVES - 1) / gd::CRAI_WAVES, 2048);
     hipLaunchKernelGGL(gd::gd_crai_kernel<false>, dim3(grid), dim3(gd::CRAI_WAVES * 64), 0, c->stream, j);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(tile_off, d_tile_off.p, (S + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(status, d_status.p, S * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(tile_off, d_tile_off.get(), (S + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(status, d_status.get(), S * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // the scan: the total decides whether the write pass runs at all, so it is needed here either way
     tile_off[0] = 0;
@@ -58,11 +58,11 @@ int gd_crai_sizes(gd_ctx* c, int32_t n_seq, const int64_t* seq_off, const int64_
     if ((uint64_t)total > (uint64_t)cap) return fail(c, GD_E_CAPACITY, "crai: %lld tiles, room for %zu", (long long)total, cap);
     if (total == 0) return GD_OK;
     if (int r = d_sizes.alloc(c, (size_t)total * sizeof(int64_t))) return r;
-    HIPCHK(c, hipMemcpyAsync(d_tile_off.p, tile_off, (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_tile_off.get(), tile_off, (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     j.sizes = d_sizes.as<int64_t>();
     hipLaunchKernelGGL(gd::gd_crai_kernel<true>, dim3(grid), dim3(gd::CRAI_WAVES * 64), 0, c->stream, j);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(sizes, d_sizes.p, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sizes, d_sizes.get(), (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));              // (the buffers are freed on return)
     return GD_OK;
 }

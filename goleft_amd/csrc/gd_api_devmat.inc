@@ -51,7 +51,7 @@ static void mat_keys_to_float(const std::vector<uint64_t>& keys, float* med)
 static int dm_from_cells(gd_ctx* c, const int64_t* d_cells, float* d_out, size_t n_rows, int n_samples, DevBuf& flag)
 {
     if (int r = flag.alloc(c, sizeof(uint32_t))) return r;
-    HIPCHK(c, hipMemsetAsync(flag.p, 0, sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(flag.get(), 0, sizeof(uint32_t), c->stream));
     gd::DmJob j{};
     j.cells = d_cells; j.depths = d_out; j.n_rows = (int64_t)n_rows; j.n = n_samples; j.flag = flag.as<uint32_t>();
     dim3 grid, wg;
@@ -65,7 +65,7 @@ static int dm_from_cells(gd_ctx* c, const int64_t* d_cells, float* d_out, size_t
 static int dm_refuse_negative(gd_ctx* c, const char* who, const DevBuf& flag)
 {
     uint32_t negative = 0;
-    HIPCHK(c, hipMemcpyAsync(&negative, flag.p, sizeof negative, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&negative, flag.get(), sizeof negative, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (negative) return fail(c, GD_E_INVALID, "%s: a cell of the device matrix is negative", who);
     return GD_OK;
@@ -76,7 +76,7 @@ static int dm_check(gd_ctx* c, const char* who, const float* d_depths, size_t n_
 {
     DevBuf w;
     if (int r = w.alloc(c, sizeof(unsigned long long))) return r;
-    HIPCHK(c, hipMemsetAsync(w.p, 0xff, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(w.get(), 0xff, sizeof(unsigned long long), c->stream));
     gd::DmJob j{};
     j.depths = const_cast<float*>(d_depths); j.n_rows = (int64_t)n_rows; j.n = n_samples;
     j.first = w.as<unsigned long long>();
@@ -85,7 +85,7 @@ static int dm_check(gd_ctx* c, const char* who, const float* d_depths, size_t n_
     hipLaunchKernelGGL(gd::gd_devmat_check_kernel, grid, wg, 0, c->stream, j);
     HIPCHK(c, hipGetLastError());
     unsigned long long first = 0;
-    HIPCHK(c, hipMemcpyAsync(&first, w.p, sizeof first, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&first, w.get(), sizeof first, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     static_assert(sizeof(size_t) == sizeof first, "the kernel's `none` is gdm::kNone");
     return mat_refuse_cell(c, who, (size_t)first, n_samples);
@@ -106,7 +106,7 @@ int gd_device_scale(gd_ctx* c, float* d_depths, size_t n_rows, int n_samples, co
     const size_t N = (size_t)n_samples;
     DevBuf f;
     if (int r = f.alloc(c, N * sizeof(float))) return r;
-    HIPCHK(c, hipMemcpyAsync(f.p, scale, N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(f.get(), scale, N * sizeof(float), hipMemcpyHostToDevice, c->stream));
     gd::DmJob j{};
     j.depths = d_depths; j.scale = f.as<const float>(); j.n_rows = (int64_t)n_rows; j.n = n_samples;
     dim3 grid, wg;

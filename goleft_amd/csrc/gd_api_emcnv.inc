@@ -15,44 +15,28 @@ struct EcState {
     uint64_t n_cnvs = 0, n_members = 0;
     double secs[4] = {0, 0, 0, 0};               // upload, EM kernel, CNV kernels, read-back
     // kept for the whole run (grow-only)
-    uint8_t* carry[2] = {nullptr, nullptr};
-    uint32_t* start = nullptr; size_t cap_start = 0;
-    uint32_t* end = nullptr; size_t cap_end = 0;
-    uint64_t* mbits = nullptr; size_t cap_mbits = 0;
-    uint64_t* rowoff = nullptr; size_t cap_rowoff = 0;
-    float* m_depth = nullptr; size_t cap_m_depth = 0;
-    uint8_t* m_cn = nullptr; size_t cap_m_cn = 0;
-    float* m_fc = nullptr; size_t cap_m_fc = 0;
+    DevArr<uint8_t> carry[2];
+    DevArr<uint32_t> start, end;
+    DevArr<uint64_t> mbits, rowoff;
+    DevArr<float> m_depth;
+    DevArr<uint8_t> m_cn;
+    DevArr<float> m_fc;
     // a block's temporaries (grow-only, nothing kept in them)
-    float* in = nullptr; size_t cap_in = 0;
-    float* scale = nullptr;
-    double* lambda = nullptr; size_t cap_lambda = 0;
-    uint8_t* cn = nullptr; size_t cap_cn = 0;
-    float* fc = nullptr; size_t cap_fc = 0;
-    uint32_t* rowcnt = nullptr; size_t cap_rowcnt = 0;
-    uint64_t* tiles = nullptr; size_t cap_tiles = 0;
-    uint64_t* total = nullptr;                   // one word: a scan's total
+    DevArr<float> in, scale;
+    DevArr<double> lambda;
+    DevArr<uint8_t> cn;
+    DevArr<float> fc;
+    DevArr<uint32_t> rowcnt;
+    DevArr<uint64_t> tiles;
+    DevArr<uint64_t> total;                      // one word: a scan's total
     // the result (gd_emcnv_finish)
-    uint32_t *c_sample = nullptr, *c_psize = nullptr, *c_emit = nullptr, *c_count = nullptr, *c_last = nullptr;
-    uint64_t* member_off = nullptr;
-    uint32_t* o_row = nullptr; float* o_depth = nullptr; uint8_t* o_cn = nullptr; float* o_fc = nullptr;
-    ~EcState()
-    {
-        for (void* p : {(void*)carry[0], (void*)carry[1], (void*)start, (void*)end, (void*)mbits, (void*)rowoff, (void*)m_depth,
-                        (void*)m_cn, (void*)m_fc, (void*)in, (void*)scale, (void*)lambda, (void*)cn, (void*)fc, (void*)rowcnt,
-                        (void*)tiles, (void*)total, (void*)c_sample, (void*)c_psize, (void*)c_emit, (void*)c_count, (void*)c_last,
-                        (void*)member_off, (void*)o_row, (void*)o_depth, (void*)o_cn, (void*)o_fc})
-            if (p) (void)hipFree(p);
-    }
+    DevArr<uint32_t> c_sample, c_psize, c_emit, c_count, c_last;
+    DevArr<uint64_t> member_off;
+    DevArr<uint32_t> o_row;
+    DevArr<float> o_depth;
+    DevArr<uint8_t> o_cn;
+    DevArr<float> o_fc;
 };
-
-static void ec_drop(gd_ctx* c)
-{
-    if (!c->ec) return;
-    (void)hipStreamSynchronize(c->stream);
-    delete c->ec;
-    c->ec = nullptr;
-}
 
 // workgroups of the two per-block kernels, which stride over the rows
 static unsigned ec_grid(uint64_t items, uint64_t per_wg)
@@ -67,11 +51,11 @@ static unsigned ec_cover(uint64_t items, uint64_t per_wg) { return (unsigned)std
 static int ec_scan(gd_ctx* c, EcState& s, const uint32_t* in, uint64_t n, uint64_t base, uint64_t* out, uint64_t* d_total)
 {
     const uint64_t tiles = (n + gd::EMCNV_SCAN_TILE - 1) / gd::EMCNV_SCAN_TILE;
-    if (int r = ensure_dev(c, &s.tiles, &s.cap_tiles, (size_t)tiles)) return r;
+    if (int r = ensure_dev(c, s.tiles, (size_t)tiles)) return r;
     hipLaunchKernelGGL(gd::gd_emcnv_scan_tile_kernel, dim3((unsigned)tiles), dim3(gd::EMCNV_WG), 0, c->stream, in, n, s.tiles);
     hipLaunchKernelGGL(gd::gd_emcnv_scan_top_kernel, dim3(1), dim3(gd::EMCNV_WG), 0, c->stream, s.tiles, tiles, base, d_total);
     hipLaunchKernelGGL(gd::gd_emcnv_scan_apply_kernel, dim3((unsigned)tiles), dim3(gd::EMCNV_WG), 0, c->stream, in, n,
-                       (const uint64_t*)s.tiles, out);
+                       (const uint64_t*)s.tiles.get(), out);
     HIPCHK(c, hipGetLastError());
     return GD_OK;
 }
@@ -91,14 +75,14 @@ static int ec_add(gd_ctx* c, EcState& s, bool cells, const void* d_in, const flo
     double t0 = ing_now();
     // (ensure_dev copies what is kept on the copy stream and waits for both streams: the copy stream is idle during a run,
     // and the compute stream has been waited for wherever an array that is kept grows)
-    if (int r = ensure_dev(c, &s.start, &s.cap_start, R + B, true, R)) return r;
-    if (int r = ensure_dev(c, &s.end, &s.cap_end, R + B, true, R)) return r;
-    if (int r = ensure_dev(c, &s.mbits, &s.cap_mbits, (R + B) * W, true, R * W)) return r;
-    if (int r = ensure_dev(c, &s.rowoff, &s.cap_rowoff, R + B, true, R)) return r;
-    if (int r = ensure_dev(c, &s.lambda, &s.cap_lambda, B * gd::EM_CENTRES)) return r;
-    if (int r = ensure_dev(c, &s.cn, &s.cap_cn, B * N)) return r;
-    if (int r = ensure_dev(c, &s.fc, &s.cap_fc, B * N)) return r;
-    if (int r = ensure_dev(c, &s.rowcnt, &s.cap_rowcnt, B)) return r;
+    if (int r = ensure_dev(c, s.start, R + B, true, R)) return r;
+    if (int r = ensure_dev(c, s.end, R + B, true, R)) return r;
+    if (int r = ensure_dev(c, s.mbits, (R + B) * W, true, R * W)) return r;
+    if (int r = ensure_dev(c, s.rowoff, R + B, true, R)) return r;
+    if (int r = ensure_dev(c, s.lambda, B * gd::EM_CENTRES)) return r;
+    if (int r = ensure_dev(c, s.cn, B * N)) return r;
+    if (int r = ensure_dev(c, s.fc, B * N)) return r;
+    if (int r = ensure_dev(c, s.rowcnt, B)) return r;
     HIPCHK(c, hipMemcpyAsync(s.start + R, starts, B * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(s.end + R, ends, B * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -122,9 +106,9 @@ static int ec_add(gd_ctx* c, EcState& s, bool cells, const void* d_in, const flo
     uint64_t total = 0;
     if (int r = ec_fetch(c, s.total, &total)) return r;
     if (total > s.members) {
-        if (int r = ensure_dev(c, &s.m_depth, &s.cap_m_depth, (size_t)total, true, (size_t)s.members)) return r;
-        if (int r = ensure_dev(c, &s.m_cn, &s.cap_m_cn, (size_t)total, true, (size_t)s.members)) return r;
-        if (int r = ensure_dev(c, &s.m_fc, &s.cap_m_fc, (size_t)total, true, (size_t)s.members)) return r;
+        if (int r = ensure_dev(c, s.m_depth, (size_t)total, true, (size_t)s.members)) return r;
+        if (int r = ensure_dev(c, s.m_cn, (size_t)total, true, (size_t)s.members)) return r;
+        if (int r = ensure_dev(c, s.m_fc, (size_t)total, true, (size_t)s.members)) return r;
         j.m_depth = s.m_depth; j.m_cn = s.m_cn; j.m_fc = s.m_fc;
         if (cells) hipLaunchKernelGGL(gd::gd_emcnv_gather_kernel<int64_t>, grid, wg, 0, c->stream, j);
         else hipLaunchKernelGGL(gd::gd_emcnv_gather_kernel<float>, grid, wg, 0, c->stream, j);
@@ -167,20 +151,20 @@ int gd_emcnv_begin(gd_ctx* c, int n_samples)
     if (!c) return GD_E_INVALID;
     if (int r = em_check_n(c, n_samples)) return r;      // (a refused begin leaves an earlier state alone)
     if (int r = set_device(c)) return r;
-    ec_drop(c);
-    c->ec = new (std::nothrow) EcState();
+    drop_state(c, c->ec);
+    c->ec.reset(new (std::nothrow) EcState());
     if (!c->ec) return GD_E_NOMEM;
     EcState& s = *c->ec;
     auto body = [&]() -> int {
         s.n = n_samples;
         s.words = (n_samples + 63) / 64;
-        for (auto& p : s.carry) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&p), (size_t)s.words * 64));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s.scale), (size_t)n_samples * sizeof(float)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s.total), sizeof(uint64_t)));
+        for (auto& p : s.carry) HIPCHK(c, p.alloc((size_t)s.words * 64));
+        HIPCHK(c, s.scale.alloc((size_t)n_samples));
+        HIPCHK(c, s.total.alloc(1));
         return GD_OK;
     };
     const int rc = body();
-    if (rc != GD_OK) ec_drop(c);
+    if (rc != GD_OK) drop_state(c, c->ec);
     return rc;
 }
 
@@ -192,7 +176,7 @@ int gd_emcnv_add(gd_ctx* c, const float* depths, size_t n_rows, const uint32_t* 
     const size_t N = (size_t)s.n;
     if (int r = mat_check(c, "emcnv", depths, n_rows, s.n)) return r;
     const double t0 = ing_now();
-    if (int r = ensure_dev(c, &s.in, &s.cap_in, n_rows * N)) return r;
+    if (int r = ensure_dev(c, s.in, n_rows * N)) return r;
     HIPCHK(c, hipMemcpyAsync(s.in, depths, n_rows * N * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     s.secs[0] += ing_now() - t0;
@@ -213,7 +197,7 @@ int gd_emcnv_add_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, const f
         HIPCHK(c, hipStreamSynchronize(c->stream));
         s.secs[0] += ing_now() - t0;
     }
-    return ec_add(c, s, true, d_cells, scale ? s.scale : nullptr, n_rows, starts, ends, cn_out);
+    return ec_add(c, s, true, d_cells, scale ? s.scale.get() : nullptr, n_rows, starts, ends, cn_out);
 }
 
 // gd_emcnv_add for float32 rows that are in HBM already: gd_devmat.hpp's check in place of the host's, no upload
@@ -266,18 +250,18 @@ int gd_emcnv_finish(gd_ctx* c, uint64_t* n_cnvs, uint64_t* n_members)
         uint64_t n_c = 0, n_m = 0;
         if (int r = ec_fetch(c, s.total, &n_c)) return r;
         if (n_c > 0x7fffffffull * gd::EMCNV_WAVES) return fail(c, GD_E_RANGE, "emcnv: more than 2^33 - 4 CNVs");
-        // the result is the state's only once it is whole
-        DevList res;
-        uint32_t *c_sample, *c_psize, *c_emit, *c_count, *c_last, *o_row = nullptr;
-        uint64_t* member_off;
-        float *o_depth = nullptr, *o_fc = nullptr;
-        uint8_t* o_cn = nullptr;
-        if (int r = res.alloc(c, &c_sample, n_c)) return r;
-        if (int r = res.alloc(c, &c_psize, n_c)) return r;
-        if (int r = res.alloc(c, &c_emit, n_c)) return r;
-        if (int r = res.alloc(c, &c_count, n_c)) return r;
-        if (int r = res.alloc(c, &c_last, n_c)) return r;
-        if (int r = res.alloc(c, &member_off, n_c + 1, true)) return r;
+        // the result is the state's only once it is whole (until then this call owns it, and frees it on return)
+        DevArr<uint32_t> c_sample, c_psize, c_emit, c_count, c_last, o_row;
+        DevArr<uint64_t> member_off;
+        DevArr<float> o_depth, o_fc;
+        DevArr<uint8_t> o_cn;
+        HIPCHK(c, c_sample.alloc(n_c));
+        HIPCHK(c, c_psize.alloc(n_c));
+        HIPCHK(c, c_emit.alloc(n_c));
+        HIPCHK(c, c_count.alloc(n_c));
+        HIPCHK(c, c_last.alloc(n_c));
+        HIPCHK(c, member_off.alloc(n_c + 1));
+        HIPCHK(c, hipMemsetAsync(member_off, 0, (n_c + 1) * sizeof(uint64_t), c->stream));
         if (n_c > 0) {
             j.c_sample = c_sample; j.c_psize = c_psize; j.c_emit = c_emit; j.c_count = c_count; j.c_last = c_last;
             j.n_cnvs = n_c;
@@ -285,19 +269,20 @@ int gd_emcnv_finish(gd_ctx* c, uint64_t* n_cnvs, uint64_t* n_members)
             HIPCHK(c, hipGetLastError());
             if (int r = ec_scan(c, s, c_count, n_c, 0, member_off, member_off + n_c)) return r;
             if (int r = ec_fetch(c, member_off + n_c, &n_m)) return r;
-            if (int r = res.alloc(c, &o_row, n_m)) return r;
-            if (int r = res.alloc(c, &o_depth, n_m)) return r;
-            if (int r = res.alloc(c, &o_cn, n_m)) return r;
-            if (int r = res.alloc(c, &o_fc, n_m)) return r;
+            HIPCHK(c, o_row.alloc(n_m));
+            HIPCHK(c, o_depth.alloc(n_m));
+            HIPCHK(c, o_cn.alloc(n_m));
+            HIPCHK(c, o_fc.alloc(n_m));
             j.member_off = member_off;
             j.o_row = o_row; j.o_depth = o_depth; j.o_cn = o_cn; j.o_fc = o_fc;
             hipLaunchKernelGGL(gd::gd_emcnv_members_kernel, dim3(ec_cover(n_c, gd::EMCNV_WAVES)), wg, 0, c->stream, j);
             HIPCHK(c, hipGetLastError());
         }
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        res.release();
-        s.c_sample = c_sample; s.c_psize = c_psize; s.c_emit = c_emit; s.c_count = c_count; s.c_last = c_last;
-        s.member_off = member_off; s.o_row = o_row; s.o_depth = o_depth; s.o_cn = o_cn; s.o_fc = o_fc;
+        // (onto empty owners -- this runs once per gd_emcnv_begin -- so the moves free nothing)
+        s.c_sample = std::move(c_sample); s.c_psize = std::move(c_psize); s.c_emit = std::move(c_emit);
+        s.c_count = std::move(c_count); s.c_last = std::move(c_last); s.member_off = std::move(member_off);
+        s.o_row = std::move(o_row); s.o_depth = std::move(o_depth); s.o_cn = std::move(o_cn); s.o_fc = std::move(o_fc);
         s.n_cnvs = n_c; s.n_members = n_m;
         s.secs[2] += ing_now() - t0;
     }
@@ -334,7 +319,7 @@ int gd_emcnv_end(gd_ctx* c)
 {
     if (!c) return GD_E_INVALID;
     if (int r = set_device(c)) return r;
-    ec_drop(c);
+    drop_state(c, c->ec);
     return GD_OK;
 }
 

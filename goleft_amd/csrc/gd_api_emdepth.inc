@@ -61,10 +61,10 @@ static int em_run(gd_ctx* c, bool cells, const void* d_in, const float* d_scale,
                           b_cn.as<uint8_t>(), b_fc.as<float>(), &c->em_secs[1]))
         return r;
     const double t1 = ing_now();
-    if (lambda) HIPCHK(c, hipMemcpyAsync(lambda, b_lambda.p, n_rows * gd::EM_CENTRES * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (iters) HIPCHK(c, hipMemcpyAsync(iters, b_iters.p, n_rows, hipMemcpyDeviceToHost, c->stream));
-    if (cn) HIPCHK(c, hipMemcpyAsync(cn, b_cn.p, cellsN, hipMemcpyDeviceToHost, c->stream));
-    if (log2fc) HIPCHK(c, hipMemcpyAsync(log2fc, b_fc.p, cellsN * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (lambda) HIPCHK(c, hipMemcpyAsync(lambda, b_lambda.get(), n_rows * gd::EM_CENTRES * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (iters) HIPCHK(c, hipMemcpyAsync(iters, b_iters.get(), n_rows, hipMemcpyDeviceToHost, c->stream));
+    if (cn) HIPCHK(c, hipMemcpyAsync(cn, b_cn.get(), cellsN, hipMemcpyDeviceToHost, c->stream));
+    if (log2fc) HIPCHK(c, hipMemcpyAsync(log2fc, b_fc.get(), cellsN * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->em_secs[2] = ing_now() - t1;
     return GD_OK;
@@ -87,10 +87,10 @@ int gd_emdepth(gd_ctx* c, const float* depths, size_t n_rows, int n_samples, dou
     DevBuf in;
     const double t0 = ing_now();
     if (int r = in.alloc(c, bytes)) return r;
-    HIPCHK(c, hipMemcpyAsync(in.p, depths, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(in.get(), depths, bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->em_secs[0] = ing_now() - t0;
-    return em_run(c, false, in.p, nullptr, n_rows, n_samples, lambda, iters, cn, log2fc);
+    return em_run(c, false, in.get(), nullptr, n_rows, n_samples, lambda, iters, cn, log2fc);
 }
 
 int gd_emdepth_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, int n_samples, const float* scale, double* lambda,
@@ -108,7 +108,7 @@ int gd_emdepth_cells(gd_ctx* c, const int64_t* d_cells, size_t n_rows, int n_sam
     if (scale) {
         const double t0 = ing_now();
         if (int r = d_scale.alloc(c, (size_t)n_samples * sizeof(float))) return r;
-        HIPCHK(c, hipMemcpyAsync(d_scale.p, scale, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_scale.get(), scale, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->em_secs[0] = ing_now() - t0;
     }

@@ -12,37 +12,18 @@ struct IcState {
     std::vector<int64_t> sample_off, tile_off, cell_off, col_off, median;
     std::vector<int32_t> tile_cnt, longest;
     std::vector<uint8_t> is_sex;
-    std::vector<void*> dev;                    // every device allocation, freed together
+    DevList dev;                               // every device allocation: job's arrays and the four below point into it
     gd::IcJob job{};
     long long *d_P = nullptr, *d_G = nullptr, *d_sums = nullptr;
     const int2* d_pairs = nullptr; size_t n_pairs = 0;   // the upper triangle of 32-sample blocks, built once
     bool uploaded = false, buffers = false;      // upload finished; the result buffers of compute exist
     double secs[5] = {0, 0, 0, 0, 0};          // upload, median + depth, cells / slots / counters / pca8, CN, Gram
-    void drop_dev()
-    {
-        for (void* p : dev) if (p) (void)hipFree(p);
-        dev.clear();
-        job = gd::IcJob{};
-        d_P = d_G = d_sums = nullptr;
-        d_pairs = nullptr; n_pairs = 0;
-        uploaded = buffers = false;
-    }
-    ~IcState() { drop_dev(); }
 };
-
-static void ic_drop(gd_ctx* c)
-{
-    if (!c->ic) return;
-    (void)hipStreamSynchronize(c->stream);
-    delete c->ic;
-    c->ic = nullptr;
-}
 
 static int ic_alloc_bytes(gd_ctx* c, IcState& s, void** p, size_t bytes)
 {
-    void* q = nullptr;
-    HIPCHK(c, hipMalloc(&q, std::max<size_t>(bytes, 1)));
-    s.dev.push_back(q);
+    uint8_t* q = nullptr;
+    if (int r = s.dev.alloc(c, &q, bytes)) return r;
     *p = q;
     return GD_OK;
 }
@@ -84,8 +65,8 @@ int gd_indexcov_upload(gd_ctx* c, int32_t n_samples, int32_t n_refs, const int64
     for (int64_t i = 0; i < T; ++i)
         if (sizes[i] < 0) return fail(c, GD_E_INVALID, "indexcov: negative tile size at %lld", (long long)i);
     if (int r = set_device(c)) return r;
-    ic_drop(c);
-    c->ic = new (std::nothrow) IcState();
+    drop_state(c, c->ic);
+    c->ic.reset(new (std::nothrow) IcState());
     if (!c->ic) return GD_E_NOMEM;
     IcState& s = *c->ic;
     // a failure below leaves no half-built state behind: the context is as before the first upload
@@ -146,7 +127,7 @@ int gd_indexcov_upload(gd_ctx* c, int32_t n_samples, int32_t n_refs, const int64
     return GD_OK;
     };
     const int rc = body();
-    if (rc != GD_OK) ic_drop(c);
+    if (rc != GD_OK) drop_state(c, c->ic);
     else s.uploaded = true;
     return rc;
 }
@@ -225,7 +206,7 @@ int gd_indexcov_compute(gd_ctx* c, int with_gram)
             s.n_pairs = pairs.size();
             return GD_OK;
         };
-        if (const int r = make()) { ic_drop(c); return r; }
+        if (const int r = make()) { drop_state(c, c->ic); return r; }
         s.buffers = true;
     }
     HIPCHK(c, hipMemsetAsync(j.counters, 0, N * 4 * sizeof(unsigned long long), c->stream));

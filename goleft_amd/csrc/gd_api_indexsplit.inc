@@ -9,25 +9,11 @@ struct IsState {
     int64_t n_cells = 0;
     std::vector<int32_t> longest;
     int32_t most = 0;                          // the largest of longest
-    int32_t* d_longest = nullptr;
-    int64_t* d_cell_off = nullptr;
-    double* d_sums = nullptr;
+    DevArr<int32_t> d_longest;
+    DevArr<int64_t> d_cell_off;
+    DevArr<double> d_sums;
     double secs[3] = {0, 0, 0};                // upload, kernel, read-back: summed over the calls since begin
-    ~IsState()
-    {
-        if (d_longest) (void)hipFree(d_longest);
-        if (d_cell_off) (void)hipFree(d_cell_off);
-        if (d_sums) (void)hipFree(d_sums);
-    }
 };
-
-static void is_drop(gd_ctx* c)
-{
-    if (!c->isp) return;
-    (void)hipStreamSynchronize(c->stream);
-    delete c->isp;
-    c->isp = nullptr;
-}
 
 constexpr int32_t kIsMaxTiles = 1 << 24;       // per reference (a .bai ends at 2^29 bases: 32 768 tiles)
 
@@ -37,7 +23,7 @@ int gd_indexsplit_begin(gd_ctx* c, int32_t n_refs, const int32_t* longest)
 {
     if (!c || !longest) return GD_E_INVALID;
     if (int r = set_device(c)) return r;
-    is_drop(c);
+    drop_state(c, c->isp);
     if (n_refs < 1 || n_refs > (1 << 20)) return fail(c, GD_E_RANGE, "indexsplit: 1 .. 2^20 references, not %d", n_refs);
     const size_t R = (size_t)n_refs;
     std::vector<int64_t> cell_off(R);
@@ -50,16 +36,16 @@ int gd_indexsplit_begin(gd_ctx* c, int32_t n_refs, const int32_t* longest)
         cells += longest[r];
         most = std::max(most, longest[r]);
     }
-    c->isp = new (std::nothrow) IsState();
+    c->isp.reset(new (std::nothrow) IsState());
     if (!c->isp) return GD_E_NOMEM;
     IsState& s = *c->isp;
     // a failure below leaves no half-built state behind
     auto body = [&]() -> int {
         s.R = n_refs; s.n_cells = cells; s.most = most;
         s.longest.assign(longest, longest + R);
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s.d_longest), R * sizeof(int32_t)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s.d_cell_off), R * sizeof(int64_t)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s.d_sums), std::max<size_t>((size_t)cells, 1) * sizeof(double)));
+        HIPCHK(c, s.d_longest.alloc(R));
+        HIPCHK(c, s.d_cell_off.alloc(R));
+        HIPCHK(c, s.d_sums.alloc((size_t)cells));
         HIPCHK(c, hipMemcpyAsync(s.d_longest, s.longest.data(), R * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(s.d_cell_off, cell_off.data(), R * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemsetAsync(s.d_sums, 0, std::max<size_t>((size_t)cells, 1) * sizeof(double), c->stream));
@@ -67,7 +53,7 @@ int gd_indexsplit_begin(gd_ctx* c, int32_t n_refs, const int32_t* longest)
         return GD_OK;
     };
     const int rc = body();
-    if (rc != GD_OK) is_drop(c);
+    if (rc != GD_OK) drop_state(c, c->isp);
     return rc;
 }
 
@@ -107,9 +93,9 @@ int gd_indexsplit_add(gd_ctx* c, int32_t n_samples, const int64_t* sample_off, c
     if (int r = d_sizes.alloc(c, (size_t)T * sizeof(int64_t))) return r;
     if (int r = d_tile_off.alloc(c, N * R * sizeof(int64_t))) return r;
     if (int r = d_tile_cnt.alloc(c, N * R * sizeof(int32_t))) return r;
-    HIPCHK(c, hipMemcpyAsync(d_sizes.p, sizes, (size_t)T * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_tile_off.p, tile_off, N * R * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_tile_cnt.p, tile_cnt, N * R * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_sizes, sizes, (size_t)T * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_tile_off, tile_off, N * R * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_tile_cnt, tile_cnt, N * R * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const double t1 = ing_now();
     gd::IsJob j{};

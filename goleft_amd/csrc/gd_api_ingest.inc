@@ -162,9 +162,9 @@ int gd_ingest_begin(gd_ctx* c, uint64_t n_bytes, uint64_t base_coffset, size_t n
         if (!b.busy) { g->bufs = &b; break; }
     if (!g->bufs) return bail(GD_E_STATE, "no free range buffers (internal error)");
     g->bufs->busy = true;
-    if (!IngestBufs::fit_host(&g->bufs->tab, &g->bufs->cap_tab, tab_bytes))
+    if (!IngestBufs::fit_host(g->bufs->tab, tab_bytes))
         return bail(GD_E_NOMEM, "cannot page-lock the BGZF member table");
-    g->t_in_off = static_cast<uint64_t*>(g->bufs->tab);
+    g->t_in_off = g->bufs->tab.as<uint64_t>();
     g->t_out_off = g->t_in_off + n_members;
     g->t_in_len = reinterpret_cast<uint32_t*>(g->t_out_off + n_members);
     g->t_out_len = g->t_in_len + n_members;
@@ -204,17 +204,16 @@ int gd_ingest_begin(gd_ctx* c, uint64_t n_bytes, uint64_t base_coffset, size_t n
     }
     // (what exists and holds THIS range stays -- whatever the estimate says now: an estimate 0.1 % above the last one is no
     // reason to free ten gigabytes)
-    if ((size_t)n_bytes + gd::INF_SLACK <= g->bufs->cap_in) want_in = (size_t)n_bytes;
-    if ((size_t)total + gd::INF_SLACK <= g->bufs->cap_out) want_out = (size_t)total;
-    if (!IngestBufs::fit(&g->bufs->in, &g->bufs->cap_in, std::max<size_t>(want_in, (size_t)n_bytes) + gd::INF_SLACK) ||
-        !IngestBufs::fit(&g->bufs->out, &g->bufs->cap_out, std::max<size_t>(want_out, (size_t)total) + gd::INF_SLACK))
+    if ((size_t)n_bytes + gd::INF_SLACK <= g->bufs->in.cap()) want_in = (size_t)n_bytes;
+    if ((size_t)total + gd::INF_SLACK <= g->bufs->out.cap()) want_out = (size_t)total;
+    if (!IngestBufs::fit(g->bufs->in, std::max<size_t>(want_in, (size_t)n_bytes) + gd::INF_SLACK) ||
+        !IngestBufs::fit(g->bufs->out, std::max<size_t>(want_out, (size_t)total) + gd::INF_SLACK))
         return bail(GD_E_NOMEM, "device allocation for the BAM decode failed");
-    g->d_in = static_cast<uint8_t*>(g->bufs->in);
-    g->d_out = static_cast<uint8_t*>(g->bufs->out);
+    g->d_in = g->bufs->in;
+    g->d_out = g->bufs->out;
     for (int k = 0; k < 2; ++k)
-        if ((!c->ing_stage[k] &&
-             hipHostMalloc(reinterpret_cast<void**>(&c->ing_stage[k]), IngestState::kStage, hipHostMallocDefault) != hipSuccess) ||
-            (!c->ing_staged[k] && hipEventCreateWithFlags(&c->ing_staged[k], hipEventDisableTiming | hipEventBlockingSync) != hipSuccess))
+        if ((!c->ing_stage[k] && c->ing_stage[k].alloc(IngestState::kStage) != hipSuccess) ||
+            (!c->ing_staged[k] && c->ing_staged[k].create(hipEventDisableTiming | hipEventBlockingSync) != hipSuccess))
             return bail(GD_E_NOMEM, "cannot allocate the page-locked staging buffers");
     // GD_OPT_INGEST_CU_SPLIT = n > 0 (with GD_OPT_INGEST_DMA = 0): every n-th CU belongs to the copy kernel that pulls the
     // staged pieces over the link, the others to the inflate launches -- a copy kernel reaches twice a copy engine's rate
@@ -228,15 +227,20 @@ int gd_ingest_begin(gd_ctx* c, uint64_t n_bytes, uint64_t base_coffset, size_t n
             for (int i = 0; i < ncu; ++i) ((i % c->ing_cu_split) == 0 ? mask_copy : mask_rest)[(size_t)i / 32] |= 1u << (i % 32);
         }
     }
-    for (hipStream_t& s : c->ing_stream)
+    for (Stream& s : c->ing_stream)
         if (!s) {
-            const hipError_t e = mask_rest.empty() ? hipStreamCreateWithFlags(&s, hipStreamNonBlocking)
-                                                   : hipExtStreamCreateWithCUMask(&s, (uint32_t)mask_rest.size(), mask_rest.data());
+            hipStream_t made = nullptr;
+            const hipError_t e = mask_rest.empty() ? hipStreamCreateWithFlags(&made, hipStreamNonBlocking)
+                                                   : hipExtStreamCreateWithCUMask(&made, (uint32_t)mask_rest.size(), mask_rest.data());
             if (e != hipSuccess) return bail(GD_E_HIP, "cannot create a stream");
+            s.adopt(made);
         }
-    if (!mask_copy.empty() && !c->ing_hp &&
-        hipExtStreamCreateWithCUMask(&c->ing_hp, (uint32_t)mask_copy.size(), mask_copy.data()) != hipSuccess)
-        return bail(GD_E_HIP, "cannot create a CU-masked stream");
+    if (!mask_copy.empty() && !c->ing_hp) {
+        hipStream_t made = nullptr;
+        if (hipExtStreamCreateWithCUMask(&made, (uint32_t)mask_copy.size(), mask_copy.data()) != hipSuccess)
+            return bail(GD_E_HIP, "cannot create a CU-masked stream");
+        c->ing_hp.adopt(made);
+    }
     return GD_OK;
 }
 
@@ -286,12 +290,14 @@ static int ingest_send(gd_ctx* c, IngestState* g, int k, size_t piece)
         if (!c->ing_hp) {
             int lo = 0, hi = 0;
             (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-            HIPCHK(c, hipStreamCreateWithPriority(&c->ing_hp, hipStreamNonBlocking, hi));
+            hipStream_t made = nullptr;
+            HIPCHK(c, hipStreamCreateWithPriority(&made, hipStreamNonBlocking, hi));
+            c->ing_hp.adopt(made);
         }
         gd::H2DJob hj{};
         hj.seg[0] = gd::H2DSeg{g->d_in + g->fed, c->ing_stage[k], piece};
         hipLaunchKernelGGL(gd::gd_h2d_kernel, dim3(c->ing_copy_grid), dim3(256), 0, c->ing_hp, hj);
-        if (!c->ing_hp_done[k]) HIPCHK(c, hipEventCreateWithFlags(&c->ing_hp_done[k], hipEventDisableTiming));
+        if (!c->ing_hp_done[k]) HIPCHK(c, c->ing_hp_done[k].create(hipEventDisableTiming));
         HIPCHK(c, hipEventRecord(c->ing_hp_done[k], c->ing_hp));
         HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ing_hp_done[k], 0));
     }
@@ -322,7 +328,8 @@ static int ingest_inflate_complete(gd_ctx* c, IngestState* g)
     gd::inflate_launch(ij, is, c->inflate_kernel);
     hipEvent_t done = nullptr;
     HIPCHK(c, hipEventCreateWithFlags(&done, hipEventDisableTiming | hipEventBlockingSync));   // (waited for by the decoding thread for tens of milliseconds: asleep, not spinning)
-    g->inf_done.push_back(done);
+    g->inf_done.emplace_back();
+    g->inf_done.back().adopt(done);
     HIPCHK(c, hipEventRecord(done, is));
     g->next = last;
     return GD_OK;
@@ -436,12 +443,11 @@ static bool ingest_voff(const IngestState* g, uint64_t v, uint64_t* out)
 // for the depth read and covstats: both decode ing_q[0], so never at once.)
 static int ingest_walk_table(gd_ctx* c, size_t bytes, const char* whose)
 {
-    if (bytes <= c->cap_walk) return GD_OK;
-    if (c->h_walk) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipHostFree(c->h_walk); c->h_walk = nullptr; c->cap_walk = 0; }   // (a kernel of the last call may still read it)
+    if (bytes <= c->h_walk.cap()) return GD_OK;
+    if (c->h_walk) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->h_walk.reset(); }   // (a kernel of the last call may still read it)
     const size_t want = std::max<size_t>(2 * bytes + 4096, 2u << 20);   // (rarely again: see IngestBufs::fit_host)
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_walk), want, hipHostMallocDefault) != hipSuccess)
+    if (c->h_walk.alloc(want) != hipSuccess)
         return fail(c, GD_E_NOMEM, "cannot page-lock the %s walk's tables", whose);
-    c->cap_walk = want;
     return GD_OK;
 }
 
@@ -478,7 +484,7 @@ static int ingest_decode(gd_ctx* c, int32_t tid, int32_t ref_id, const uint64_t*
     const double td1 = ing_now();
     // ---- count the records of every anchor segment ----------------------------------------------
     if (int r = ingest_walk_table(c, n_anchors * 6 * sizeof(uint64_t) + n_anchors * 4 * sizeof(uint32_t), "record")) return r;
-    uint64_t* s_beg = reinterpret_cast<uint64_t*>(c->h_walk);
+    uint64_t* s_beg = c->h_walk.as<uint64_t>();
     uint64_t* s_end = s_beg + n_anchors;
     uint64_t* s_rbase = s_end + n_anchors;
     uint64_t* s_obase = s_rbase + n_anchors;
@@ -508,9 +514,9 @@ static int ingest_decode(gd_ctx* c, int32_t tid, int32_t ref_id, const uint64_t*
             s_tbase[i] = n_tab;
             n_tab += len / 36 + 1;
         }
-        if (fits && n_tab * 8 > c->cap_rectab) HIPCHK(c, hipStreamSynchronize(c->stream));   // (a walk of the last call may still read it)
-        if (fits && IngestBufs::fit(&c->d_rectab, &c->cap_rectab, (size_t)n_tab * 8)) {
-            bj.tab = static_cast<uint32_t*>(c->d_rectab);
+        if (fits && n_tab * 8 > c->d_rectab.cap()) HIPCHK(c, hipStreamSynchronize(c->stream));   // (a walk of the last call may still read it)
+        if (fits && IngestBufs::fit(c->d_rectab, (size_t)n_tab * 8)) {
+            bj.tab = c->d_rectab.as<uint32_t>();
             bj.tab_base = s_tbase;
         }
     }
@@ -549,9 +555,7 @@ static int ingest_decode(gd_ctx* c, int32_t tid, int32_t ref_id, const uint64_t*
     HIPCHK(c, hipStreamSynchronize(c->copy_stream));
     ContigHost& h = c->contigs[tid];
     if (!append) {
-        const int64_t len = h.length;
         free_contig(h);
-        h.length = len;
     } else if (h.ck_ok) {                     // derived structures no longer cover the stream
         HIPCHK(c, hipStreamSynchronize(c->stream));
         drop_ck(h);
@@ -566,8 +570,8 @@ static int ingest_decode(gd_ctx* c, int32_t tid, int32_t ref_id, const uint64_t*
             if (eo <= 4294967295.0) want_o = (size_t)eo;
         }
         if (append) {
-            if (h.n_reads + want_r > h.cap_reads) want_r = std::max(want_r, h.cap_reads / 2);
-            if (h.n_ops + want_o > h.cap_ops) want_o = std::max(want_o, h.cap_ops / 2);
+            if (h.n_reads + want_r > h.cap_reads()) want_r = std::max(want_r, h.cap_reads() / 2);
+            if (h.n_ops + want_o > h.cigar.cap()) want_o = std::max(want_o, h.cigar.cap() / 2);
         }
         if (int r = reserve_records(c, h, want_r, want_o, Growth::EXACT)) return r;
         c->ing_secs[5] += ing_now() - td2;

@@ -43,8 +43,8 @@ static int md_run(gd_ctx* c, const float* depths, const int64_t* d_from, float* 
     if (int r = d_order.alloc(c, n_rows * sizeof(uint32_t))) return r;
     if (!d_resident) if (int r = d_out.alloc(c, cells * sizeof(float))) return r;
     if (med) if (int r = d_med.alloc(c, cells * sizeof(double))) return r;
-    if (!d_resident) HIPCHK(c, hipMemcpyAsync(d_cells.p, depths, cells * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_order.p, order.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (!d_resident) HIPCHK(c, hipMemcpyAsync(d_cells.get(), depths, cells * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_order.get(), order.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->md_secs[1] = ing_now() - t1;
 
@@ -70,8 +70,8 @@ static int md_run(gd_ctx* c, const float* depths, const int64_t* d_from, float* 
     c->md_secs[2] = ing_now() - t2;
 
     const double t3 = ing_now();
-    if (out) HIPCHK(c, hipMemcpyAsync(out, d_out.p, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (med) HIPCHK(c, hipMemcpyAsync(med, d_med.p, cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (out) HIPCHK(c, hipMemcpyAsync(out, d_out.get(), cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (med) HIPCHK(c, hipMemcpyAsync(med, d_med.get(), cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->md_secs[3] = ing_now() - t3;
     return GD_OK;

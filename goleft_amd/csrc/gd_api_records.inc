@@ -154,11 +154,11 @@ static int index_records(gd_ctx* c, ContigHost& h, size_t r0, size_t r1, int32_t
     if (r1 <= r0) return GD_OK;
     const size_t n_idx = (size_t)(h.length >> 6) + 2;
     const bool idx = c->ingest_index && h.ridx_reads == r0;      // (an index with a hole is no index)
-    if (idx && !h.ridx) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&h.ridx), n_idx * sizeof(uint32_t)));
+    if (idx && !h.ridx) HIPCHK(c, h.ridx.alloc(n_idx));
     if (!idx && !check) return GD_OK;
     gd::IndexJob j{};
     j.pos = h.pos; j.off = h.off; j.cigar = h.cigar;
-    j.ridx = idx ? h.ridx : nullptr;
+    j.ridx = idx ? h.ridx.get() : nullptr;
     j.n_idx = (uint32_t)n_idx;
     j.out = c->d_ingest;
     j.bad_out = c->d_ingest + (committed ? 3 : 0);
@@ -227,21 +227,22 @@ int gd_acquire(gd_ctx* c, size_t reads_cap, size_t ops_cap, gd_batch* out)
     if (reads_cap < 1) reads_cap = 1;
     if (ops_cap < 1) ops_cap = 1;
     if (s.b.reads_cap < reads_cap) {
-        if (s.b.pos) { (void)hipHostFree(s.b.pos); (void)hipHostFree(s.b.flag);
-                       (void)hipHostFree(s.b.mapq); (void)hipHostFree(s.b.cigar_off); }
+        s.pos.reset(); s.flag.reset(); s.mapq.reset(); s.cigar_off.reset();
         s.b.pos = nullptr; s.b.flag = nullptr; s.b.mapq = nullptr; s.b.cigar_off = nullptr;
         s.b.reads_cap = 0;
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s.b.pos), reads_cap * sizeof(int32_t), hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s.b.flag), reads_cap * sizeof(uint16_t), hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s.b.mapq), reads_cap * sizeof(uint8_t), hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s.b.cigar_off), (reads_cap + 1) * sizeof(uint32_t), hipHostMallocDefault));
+        HIPCHK(c, s.pos.alloc(reads_cap));
+        HIPCHK(c, s.flag.alloc(reads_cap));
+        HIPCHK(c, s.mapq.alloc(reads_cap));
+        HIPCHK(c, s.cigar_off.alloc(reads_cap + 1));
+        s.b.pos = s.pos; s.b.flag = s.flag; s.b.mapq = s.mapq; s.b.cigar_off = s.cigar_off;
         s.b.reads_cap = reads_cap;
     }
     if (s.b.ops_cap < ops_cap) {
-        if (s.b.cigar) (void)hipHostFree(s.b.cigar);
+        s.cigar.reset();
         s.b.cigar = nullptr;
         s.b.ops_cap = 0;
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s.b.cigar), ops_cap * sizeof(uint32_t), hipHostMallocDefault));
+        HIPCHK(c, s.cigar.alloc(ops_cap));
+        s.b.cigar = s.cigar;
         s.b.ops_cap = ops_cap;
     }
     s.b.slot = c->ring_next;
@@ -260,25 +261,23 @@ int gd_commit(gd_ctx* c, const gd_batch* b, int32_t tid, size_t n_reads, size_t 
 
 // Makes room for n_reads / n_ops more records of a contig.  EXACT: in one step (a producer that knows its totals: gd_push,
 // gd_reserve; growing geometrically block by block drains the copy pipeline at every step).  DOUBLING: at least twice
-// what is there (gd_commit, block by block).
+// what is there (gd_commit, block by block).  The arrays get exactly the capacity decided here (regrow_dev): what an array
+// holds and what the contig believes it holds are one number.  A group that failed half way is finished by the next call.
 enum class Growth { EXACT, DOUBLING };
 static int reserve_records(gd_ctx* c, ContigHost& h, size_t n_reads, size_t n_ops, Growth g)
 {
     const size_t need_r = h.n_reads + n_reads, need_o = h.n_ops + n_ops;
-    if (need_r > h.cap_reads) {
-        const size_t ncap = g == Growth::DOUBLING ? std::max(need_r, h.cap_reads * 2) : need_r;
-        size_t c1 = h.cap_reads, c2 = h.cap_reads, c3 = h.cap_reads, c4 = h.cap_reads ? h.cap_reads + 1 : 0;
-        if (int r = ensure_dev(c, &h.pos, &c1, ncap, true, h.n_reads)) return r;
-        if (int r = ensure_dev(c, &h.flag, &c2, ncap, true, h.n_reads)) return r;
-        if (int r = ensure_dev(c, &h.mapq, &c3, ncap, true, h.n_reads)) return r;
-        if (int r = ensure_dev(c, &h.off, &c4, ncap + 1, true, h.n_reads ? h.n_reads + 1 : 0)) return r;
-        h.cap_reads = ncap;
+    const size_t cap_r = h.cap_reads();
+    if (need_r > cap_r) {
+        const size_t ncap = g == Growth::DOUBLING ? std::max(need_r, cap_r * 2) : need_r;
+        if (h.pos.cap() < ncap) if (int r = regrow_dev(c, h.pos, ncap, true, h.n_reads)) return r;
+        if (h.flag.cap() < ncap) if (int r = regrow_dev(c, h.flag, ncap, true, h.n_reads)) return r;
+        if (h.mapq.cap() < ncap) if (int r = regrow_dev(c, h.mapq, ncap, true, h.n_reads)) return r;
+        if (h.off.cap() < ncap + 1) if (int r = regrow_dev(c, h.off, ncap + 1, true, h.n_reads ? h.n_reads + 1 : 0)) return r;
     }
-    if (need_o > h.cap_ops) {
-        const size_t ncap = g == Growth::DOUBLING ? std::max(need_o, h.cap_ops * 2) : need_o;
-        size_t co = h.cap_ops;
-        if (int r = ensure_dev(c, &h.cigar, &co, ncap, true, h.n_ops)) return r;
-        h.cap_ops = ncap;
+    if (need_o > h.cigar.cap()) {
+        const size_t ncap = g == Growth::DOUBLING ? std::max(need_o, h.cigar.cap() * 2) : need_o;
+        if (int r = regrow_dev(c, h.cigar, ncap, true, h.n_ops)) return r;
     }
     return GD_OK;
 }
@@ -487,7 +486,8 @@ int gd_adopt_device(gd_ctx* c, int32_t tid, const gd_batch* d, size_t n_reads, s
     ContigHost& h = c->contigs[tid];
     ContigHost t;                                          // the new stream, checked before the old one is let go
     t.length = h.length;
-    t.pos = d->pos; t.flag = d->flag; t.mapq = d->mapq; t.off = d->cigar_off; t.cigar = d->cigar;
+    t.pos.borrow(d->pos, n_reads); t.flag.borrow(d->flag, n_reads); t.mapq.borrow(d->mapq, n_reads);   // (the caller frees them)
+    t.off.borrow(d->cigar_off, n_reads + 1); t.cigar.borrow(d->cigar, n_ops);
     t.n_reads = n_reads; t.n_ops = n_ops;
     t.adopted = true;
     if (n_reads) {
@@ -509,7 +509,7 @@ int gd_adopt_device(gd_ctx* c, int32_t tid, const gd_batch* d, size_t n_reads, s
         take_ingest_span(c, (int32_t)w[1]);
     }
     free_contig(h);
-    h = t;
+    h = std::move(t);
     c->computed = false;
     return GD_OK;
 }
@@ -522,11 +522,7 @@ int gd_reset(gd_ctx* c)
     (void)gd_ingest_abort(c);                              // a device BAM read in progress (its reader thread) ends here
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-    for (auto& h : c->contigs) {
-        int64_t len = h.length;
-        free_contig(h);
-        h.length = len;
-    }
+    for (auto& h : c->contigs) free_contig(h);             // (the lengths stay)
     c->bounds.clear();
     return forget_records_state(c);
 }

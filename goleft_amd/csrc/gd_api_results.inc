@@ -79,8 +79,8 @@ int gd_region_windows(gd_ctx* c, int32_t tid, int64_t start, int64_t end, int64_
     if (int r = d_m.alloc(c, k * sizeof(int32_t))) return r;
     hipLaunchKernelGGL(gd::gd_region_windows_kernel, dim3((unsigned)k), dim3(256), 0, c->stream,
                        c->d_perbase + h.base_off, h.length, start, end, (int32_t)W, first, d_s.as<int64_t>(), d_m.as<int32_t>());
-    HIPCHK(c, hipMemcpyAsync(sums, d_s.p, k * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    if (mins) HIPCHK(c, hipMemcpyAsync(mins, d_m.p, k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sums, d_s.get(), k * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (mins) HIPCHK(c, hipMemcpyAsync(mins, d_m.get(), k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return GD_OK;
 }
@@ -116,7 +116,7 @@ int gd_region_callable(gd_ctx* c, int32_t tid, int64_t start, int64_t end, gd_ru
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (cnt > bcap) { bcap = cnt; continue; }
         std::vector<int2> b(cnt);
-        if (cnt) HIPCHK(c, hipMemcpy(b.data(), d_b.p, cnt * sizeof(int2), hipMemcpyDeviceToHost));
+        if (cnt) HIPCHK(c, hipMemcpy(b.data(), d_b.get(), cnt * sizeof(int2), hipMemcpyDeviceToHost));
         std::sort(b.begin(), b.end(), [](const int2& a, const int2& z) { return a.x < z.x; });
         *n = cnt;
         if (cap < cnt || !out) return fail(c, GD_E_CAPACITY, "need room for %u runs", cnt);
@@ -286,7 +286,7 @@ int gd_device_runs(gd_ctx* c, const int32_t** d_bounds, size_t* n_bounds)
 {
     if (!c) return GD_E_INVALID;
     if (!c->computed) return fail(c, GD_E_STATE, "no results: call gd_compute first");
-    if (d_bounds) *d_bounds = reinterpret_cast<const int32_t*>(c->d_ordered);
+    if (d_bounds) *d_bounds = c->d_ordered.as<const int32_t>();
     if (n_bounds) *n_bounds = c->bounds.size();
     return GD_OK;
 }

@@ -4,7 +4,14 @@
 // (compute_route) and the launch helpers of the tile kernels that take its answer, the long-read structures
 // (gd_chunk.hpp) and the state of a device BAM read.  Included by gd_api.hip only (one translation unit: the
 // kernels of gd_kernels.hpp are not inline).
+//
+// Ownership: every device array, page-locked array, event and stream the context keeps is a member of one of
+// gd_own.hpp's four owner types, here or in a state the context holds by unique_ptr, and goes when its holder goes:
+// nothing is freed by name.  What grows goes through ensure_dev, reserve_records (a contig's records) or IngestBufs::fit /
+// fit_host (the device BAM read); DevBuf and DevList are one call's scratch.  Raw pointers are aliases or the caller's.
 #pragma once
+
+#include "gd_own.hpp"
 
 #include <memory>
 #include <atomic>
@@ -12,6 +19,8 @@
 #include <thread>
 
 namespace {
+
+using gd_own::DevArr, gd_own::PinArr, gd_own::Event, gd_own::Stream;
 
 constexpr int kRingSlots = 4;
 constexpr size_t kSpecBounds = 4096;     // boundaries copied to the host before their count is known (one synchronisation)
@@ -24,23 +33,19 @@ constexpr int kMaxSpan = 1 << 27;   // tile-relative byte offsets of the tile ke
 // One device allocation shared by the derived arrays of a batch of contigs (long-read structures, position
 // indexes, long-read structures): a batch is built with one hipMalloc and no per-contig host round trip; the
 // block goes back to HBM when the last contig that points into it drops its share.
-struct DevBlock {
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~DevBlock() { if (p) (void)hipFree(p); }
-};
-typedef std::shared_ptr<DevBlock> BlockRef;
+typedef std::shared_ptr<DevArr<uint8_t>> BlockRef;
 
 struct ContigHost {
     int64_t length = 0;
-    // device record stream (owned unless adopted)
-    int32_t*  pos = nullptr;
-    uint16_t* flag = nullptr;
-    uint8_t*  mapq = nullptr;
-    uint32_t* off = nullptr;
-    uint32_t* cigar = nullptr;
+    // device record stream (owned; adopted: borrowed from the caller, who frees it).  reserve_records grows pos, flag,
+    // mapq and off (one element more) together, off last: its capacity is the group's
+    DevArr<int32_t>  pos;
+    DevArr<uint16_t> flag;
+    DevArr<uint8_t>  mapq;
+    DevArr<uint32_t> off;
+    DevArr<uint32_t> cigar;
     size_t n_reads = 0, n_ops = 0;
-    size_t cap_reads = 0, cap_ops = 0;
+    size_t cap_reads() const { return off.cap() ? off.cap() - 1 : 0; }
     bool adopted = false;
     int32_t last_pos = -0x7fffffff;
     // long-read path (gd_chunk.hpp): deletion lists, read records and tile indexes, built straight from the records
@@ -55,7 +60,7 @@ struct ContigHost {
     uint64_t  n_dels = 0;              // deletions in dl
     bool ck_ok = false;                // lrec / lfq / dl / pck describe the current records
     // built as the records arrive (gd_index_records_kernel): the position index, ridx[k] = first read with pos >= 64 k
-    uint32_t* ridx = nullptr;          // (length >> 6) + 2 entries; valid up to entry pos[ridx_reads - 1] >> 6
+    DevArr<uint32_t> ridx;             // (length >> 6) + 2 entries; valid up to entry pos[ridx_reads - 1] >> 6
     size_t ridx_reads = 0;             // records it covers (== n_reads: gd_prep_kernel uses it)
     bool ing_left = false;             // device BAM read in parts: a record of another reference has ended this one's records
     // layout in the result arrays of the last compute (-1 = not computed)
@@ -66,8 +71,12 @@ struct ContigHost {
 };
 
 struct RingSlot {
-    gd_batch b{};
-    hipEvent_t done = nullptr;
+    gd_batch b{};            // what gd_acquire hands out: its pointers and capacities mirror the owners below
+    PinArr<int32_t> pos;
+    PinArr<uint16_t> flag;
+    PinArr<uint8_t> mapq;
+    PinArr<uint32_t> cigar_off, cigar;
+    Event done;
     bool busy = false;       // its copy may still be in flight (`done`)
     bool held = false;       // handed out by gd_acquire, not committed yet
 };
@@ -81,50 +90,33 @@ namespace { struct FillPool; struct CovState; struct IcState; struct IsState; st
 // Device buffers of one pending range (compressed bytes, inflated bytes, member tables): grow-only and
 // kept by the context between ranges -- allocating and freeing gigabytes per range cost 0.1-0.2 s.
 struct IngestBufs {
-    void *in = nullptr, *out = nullptr, *tab = nullptr;
-    size_t cap_in = 0, cap_out = 0, cap_tab = 0;
+    gd_own::DevArr<uint8_t> in, out;
+    gd_own::PinArr<uint8_t> tab;
     bool busy = false;
-    static bool fit(void** p, size_t* cap, size_t need)
+    static bool fit(gd_own::DevArr<uint8_t>& a, size_t need)
     {
-        if (need <= *cap && *p) return true;
+        if (need <= a.cap() && a) return true;
         // (a quarter more than asked for when it has to GROW: ranges of about one size -- a reference read in parts --
         // would otherwise free and allocate again for every range a little larger than the last, and a hipFree waits for
         // the whole device, the other range's inflate kernels included)
-        const size_t want = *p ? need + need / 4 : (need ? need : 1);
-        if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-        if (hipMalloc(p, want) != hipSuccess) { *p = nullptr; return false; }
-        *cap = want;
-        return true;
+        const size_t want = a ? need + need / 4 : (need ? need : 1);
+        a.reset();
+        return a.alloc(want) == hipSuccess;
     }
     // The member tables live in PAGE-LOCKED HOST memory that the kernels read (and write: the status words) over the
     // link: a few bytes per member, once.  As device arrays they were five blocking uploads per range -- each of which
     // queued on the copy engine behind the 64 MB pieces of the read in progress (20 ms per gd_ingest_begin measured).
-    static bool fit_host(void** p, size_t* cap, size_t need)
+    static bool fit_host(gd_own::PinArr<uint8_t>& a, size_t need)
     {
-        if (need <= *cap && *p) return true;
-        if (*p) { (void)hipHostFree(*p); *p = nullptr; *cap = 0; }
+        if (need <= a.cap() && a) return true;
+        a.reset();
         // generously: freeing page-locked memory waits for the device like hipFree does -- ranges of slightly different
         // member counts (a reference read in parts) must not do that between every two of them (measured: 50 ms per
         // gd_ingest_begin, 1.4 s per genome)
         const size_t want = std::max<size_t>(2 * need + 4096, 8u << 20);
-        if (hipHostMalloc(p, want, hipHostMallocDefault) != hipSuccess) { *p = nullptr; return false; }
-        *cap = want;
-        return true;
+        return a.alloc(want) == hipSuccess;
     }
-    void drop()
-    {
-        if (in) (void)hipFree(in);
-        if (out) (void)hipFree(out);
-        in = out = nullptr;
-        cap_in = cap_out = 0;
-    }
-    void drop_all()
-    {
-        drop();
-        if (tab) (void)hipHostFree(tab);
-        tab = nullptr;
-        cap_tab = 0;
-    }
+    void drop() { in.reset(); out.reset(); }
 };
 
 
@@ -149,11 +141,13 @@ struct ComputeState {
 struct GdUniqueId { char internal[128]; };   // ncclUniqueId's layout (rccl.h: NCCL_UNIQUE_ID_BYTES = 128)
 
 struct gd_ctx {
+    __attribute__((visibility("hidden"))) gd_ctx();     // (both defined at the end of gd_api.hip, where the kept states
+    __attribute__((visibility("hidden"))) ~gd_ctx();    // are complete types)
     int device = 0;
-    hipStream_t stream = nullptr;       // compute stream
-    bool own_stream = true;
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t copy_done = nullptr;
+    // the two streams are declared first: they are destroyed last, after everything that may have work on them
+    Stream stream;                      // compute stream: the context's own, or the caller's (gd_set_stream), borrowed
+    Stream copy_stream;
+    Event copy_done;
     gd_params params{};
     std::vector<ContigHost> contigs;
     std::vector<int32_t> selected;      // empty = all
@@ -168,7 +162,7 @@ struct gd_ctx {
     bool fast_kernel = true;            // GD_OPT_FAST_KERNEL: the straight-line tile kernel (gd_tile_fast.hpp) for
                                         // ordinary tiles, the generic one for the rest; 0 = generic for every tile
     std::vector<uint8_t> batch_tab_ck;  // host copy of the job table of the last ck batch
-    uint32_t* h_batch = nullptr; size_t cap_h_batch = 0;   // pinned: per-contig totals / status words coming back
+    PinArr<uint32_t> h_batch;           // pinned: per-contig totals / status words coming back
     int tile_opt = 1;                   // bit 0: non-temporal per-base stores (2 % faster: the vector is
                                         // never re-read by the kernel)
     bool lookback_pinned = false;       // max_span_hint given: never shrink below it
@@ -177,11 +171,11 @@ struct gd_ctx {
     bool sums_only = false;             // gd_set_outputs(GD_OUT_SUMS_ONLY): window sums, nothing else
     bool ran_sums_only = false;         // what the last gd_compute produced
     bool span_forces_long = false;      // AUTO: the tile path met a read too long for it
-    unsigned long long* d_status = nullptr;  size_t cap_status = 0;   // scatter path look-back words
+    DevArr<unsigned long long> d_status;   // scatter path look-back words
     int lookback = kDefaultLookback;
     // gd_index_records_kernel's words: [0] check flags, [1] the largest reference span of any record that has arrived
     // since gd_reset / gd_set_contigs (INT_MAX: a record it did not walk), [2] the last position of the last launch
-    uint32_t* d_ingest = nullptr;
+    DevArr<uint32_t> d_ingest;
     bool ingest_span_dirty = false;     // [1] may have grown since the host last read it
     int32_t ingest_span = 0;            // the host's copy (0: nothing measured)
     bool ingest_index = true;           // GD_OPT_INGEST_INDEX
@@ -189,32 +183,32 @@ struct gd_ctx {
     double timing[4] = {0, 0, 0, 0};    // gd_compute_timing: allocations + contig table, enqueue, wait, total of the last gd_compute
 
     // device job state
-    gd::ContigDev* d_ctgs = nullptr;  size_t cap_ctgs = 0;
+    DevArr<gd::ContigDev> d_ctgs;
     std::vector<gd::ContigDev> h_ctgs;
     std::vector<gd::ContigDev> up_ctgs;   // what d_ctgs holds
     gd::ContigDev* up_ctgs_dev = nullptr;
     uint32_t slow_grid = 64;             // workgroups of gd_tile_slow_kernel
     std::vector<int32_t> job_tids;      // contig table index -> tid
-    gd::TileInfo* d_tiles = nullptr;  size_t cap_tiles = 0;
-    gd::TileFast* d_ftiles = nullptr; size_t cap_ftiles = 0;
-    int32_t* d_perbase = nullptr;     size_t cap_perbase = 0;
-    int64_t* d_wsum = nullptr;        size_t cap_win = 0;
-    int32_t* d_wmin = nullptr;
-    int2* d_chunks = nullptr;         size_t cap_runs = 0;
-    int2* d_ordered = nullptr;
-    uint32_t* d_tile_cnt = nullptr;
-    uint32_t* d_tile_off = nullptr;
-    uint32_t* d_super_cnt = nullptr;
-    gd::Counters* d_counters = nullptr;
-    gd::Counters* h_counters = nullptr;   // pinned
-    int2* h_bounds = nullptr;             // pinned: the first kSpecBounds ordered boundaries travel with the counters
+    DevArr<gd::TileInfo> d_tiles;         // d_tiles, d_tile_cnt, d_tile_off (and d_super_cnt, a SUPER-th of them) grow together
+    DevArr<gd::TileFast> d_ftiles;
+    DevArr<int32_t> d_perbase;
+    DevArr<int64_t> d_wsum;               // d_wsum and d_wmin grow together
+    DevArr<int32_t> d_wmin;
+    DevArr<int2> d_chunks;                // d_chunks and d_ordered grow together, d_ordered last: its capacity is
+    DevArr<int2> d_ordered;               // Job::run_cap (never above d_chunks')
+    DevArr<uint32_t> d_tile_cnt;
+    DevArr<uint32_t> d_tile_off;
+    DevArr<uint32_t> d_super_cnt;
+    DevArr<gd::Counters> d_counters;
+    PinArr<gd::Counters> h_counters;
+    PinArr<int2> h_bounds;                // the first kSpecBounds ordered boundaries travel with the counters
     uint32_t parity = 0;                  // Counters::n_slow in use (alternates per compute)
     bool slow_counter_clean = false;      // the last enqueue ran gd_prep_kernel, which zeroed the other counter
-    uint32_t* d_region_cursor = nullptr;
+    DevArr<uint32_t> d_region_cursor;
 
-    int64_t* d_wed = nullptr; size_t cap_wed = 0;      // gd_depthwed: tables + the sites x samples matrix
-    uint32_t* d_md_bits = nullptr; size_t cap_md = 0;  // gd_md_flags: `any` words then `suf` words
-    uint16_t* d_md_cnt = nullptr; size_t cap_md_cnt = 0;   // gd_md_begin .. gd_md_finish: samples >= min_cov per position
+    DevArr<int64_t> d_wed;                             // gd_depthwed: tables + the sites x samples matrix
+    DevArr<uint32_t> d_md_bits;                        // gd_md_flags: `any` words then `suf` words
+    DevArr<uint16_t> d_md_cnt;                         // gd_md_begin .. gd_md_finish: samples >= min_cov per position
     int64_t md_acc_len = -1;                           // gd_md_begin's length (-1: not begun)
     int64_t md_acc_samples = 0;
     int64_t md_len = -1;                               // positions the bitmaps cover (-1: none yet)
@@ -237,14 +231,14 @@ struct gd_ctx {
     IngestBufs ing_bufs[kIngestDepth];
     // staging of the device BAM read, created by the first gd_ingest_begin and kept until gd_destroy
     // (page-locking 128 MB per contig would cost more than many contigs' whole decode)
-    uint8_t* ing_stage[2] = {};                        // page-locked staging buffers: one is filled while the other's piece leaves
-    hipEvent_t ing_staged[2] = {};                     // ... recorded on the copy stream: the buffer's piece has arrived
+    Stream ing_hp;                                     // GD_OPT_INGEST_DMA 0: the copy kernel's stream, high priority or (GD_OPT_INGEST_CU_SPLIT) CU-masked
+    Stream ing_stream[8];                              // inflate launches rotate over these (two pending ranges x 4)
+    PinArr<uint8_t> ing_stage[2];                      // page-locked staging buffers: one is filled while the other's piece leaves
+    Event ing_staged[2];                               // ... recorded on the copy stream: the buffer's piece has arrived
     int ing_cu_split = 0;                              // GD_OPT_INGEST_CU_SPLIT: every n-th CU for the copy kernel, the rest for the inflate launches
     bool ing_copy_engine = true;                       // GD_OPT_INGEST_DMA: a staged piece leaves with a copy command (1) or with a copy kernel on ing_hp (0)
     unsigned ing_copy_grid = 16;                        // GD_OPT_INGEST_COPY_GRID: workgroups of the copy kernel that pulls a staged piece over the link
-    hipStream_t ing_hp = nullptr;                       // GD_OPT_INGEST_DMA 0: the copy kernel's stream, high priority or (GD_OPT_INGEST_CU_SPLIT) CU-masked
-    hipEvent_t ing_hp_done[2] = {};                     // ... the copy stream waits for these before it records ing_staged[k]
-    hipStream_t ing_stream[8] = {};                     // inflate launches rotate over these (two pending ranges x 4)
+    Event ing_hp_done[2];                               // ing_hp: the copy stream waits for these before it records ing_staged[k]
     unsigned ing_launch_seq = 0;
     int ing_copy_threads = 1;                          // GD_OPT_COPY_THREADS: threads filling the staging buffer
     bool h2d_kernel = true;                            // GD_OPT_H2D_KERNEL: staging blocks reach HBM through gd_h2d_kernel
@@ -256,12 +250,12 @@ struct gd_ctx {
     int push_threads = 16;
     FillPool* pool = nullptr; int pool_workers = 0;    // host worker threads (gd_push fills, gd_commit validates), created on first use
     size_t push_chunk = 1u << 20;                      // GD_OPT_PUSH_CHUNK: records per staging block of gd_push                             // GD_OPT_PUSH_THREADS: threads of gd_push filling a ring block
-    uint32_t* d_scan_tmp = nullptr; size_t cap_scan_tmp = 0;   // launch_scan: block totals
-    void* d_rectab = nullptr; size_t cap_rectab = 0;           // ... and the record table the counting walk leaves for the extraction (device, grow-only)
-    CovState* cov = nullptr;                                   // gd_covstats_*: the sampling state and its buffers (gd_api_covstats.inc)
-    IcState* ic = nullptr;                                     // gd_indexcov_*: the cohort's tile sizes and results (gd_api_indexcov.inc)
-    IsState* isp = nullptr;                                    // gd_indexsplit_*: the cohort's cell sums (gd_api_indexsplit.inc)
-    EcState* ec = nullptr;                                     // gd_emcnv_*: the positions, member bits and member values of the rows so far (gd_api_emcnv.inc)
+    DevArr<uint32_t> d_scan_tmp;                               // launch_scan: block totals
+    DevArr<uint8_t> d_rectab;                                  // ... and the record table the counting walk leaves for the extraction (device, grow-only)
+    std::unique_ptr<CovState> cov;                             // gd_covstats_*: the sampling state and its buffers (gd_api_covstats.inc)
+    std::unique_ptr<IcState> ic;                               // gd_indexcov_*: the cohort's tile sizes and results (gd_api_indexcov.inc)
+    std::unique_ptr<IsState> isp;                              // gd_indexsplit_*: the cohort's cell sums (gd_api_indexsplit.inc)
+    std::unique_ptr<EcState> ec;                               // gd_emcnv_*: the positions, member bits and member values of the rows so far (gd_api_emcnv.inc)
     double sm_secs[3] = {0, 0, 0};                             // gd_sample_medians*: upload, kernels, read-back of the last call (gd_api_colselect.inc)
     int sm_passes = 0;                                         // ... and the passes over the matrix it ran
     double cd_secs[7] = {0, 0, 0, 0, 0, 0, 0};                 // gd_chunk_debias: sort + chunking, upload, kernels, read-back of the last call; its chunks, its largest chunk;
@@ -271,10 +265,10 @@ struct gd_ctx {
     double sv_secs[5] = {0, 0, 0, 0, 0};                       // gd_svd_debias*: upload, statistics + Gram, eigenpairs (host), projection, read-back of the last call (gd_api_svddebias.inc)
     double ce_secs[4] = {0, 0, 0, 0};                          // gd_cnveval: preparation + upload, kernels, read-back of the last call, and the first kernel's part of the second (gd_api_cnveval.inc)
     double em_secs[3] = {0, 0, 0};                             // gd_emdepth*: upload, kernel, read-back of the last call (gd_api_emdepth.inc)
-    uint8_t* h_walk = nullptr; size_t cap_walk = 0;            // gd_ingest_decode, gd_covstats_decode: per-segment tables of the record walk (page-locked host memory
+    PinArr<uint8_t> h_walk;                                    // gd_ingest_decode, gd_covstats_decode: per-segment tables of the record walk (page-locked host memory
                                                                // the walk kernels read and write over the link: no copy command)
-    uint32_t* h_ingest = nullptr;                              // page-locked: d_ingest's words as the host reads them (gd_copy_words_kernel)
-    uint8_t* d_seq = nullptr;  size_t cap_seq = 0;     // gd_seq_load: one contig's bases, zero padded
+    PinArr<uint32_t> h_ingest;                                 // page-locked: d_ingest's words as the host reads them (gd_copy_words_kernel)
+    DevArr<uint8_t> d_seq;                             // gd_seq_load: one contig's bases, zero padded
     int64_t seq_len = -1;
     uint32_t seq_padded = 0;
 
@@ -284,7 +278,7 @@ struct gd_ctx {
     // gd_comm_init: one RCCL communicator per context (gd_api_comm.inc)
     void* comm = nullptr;
     int comm_rank = 0, comm_world = 0;
-    hipEvent_t comm_ev[3] = {nullptr, nullptr, nullptr};   // [0], [1]: the last two gathers; [2]: "computed so far"
+    Event comm_ev[3];                                      // [0], [1]: the last two gathers; [2]: "computed so far"
     unsigned comm_seq = 0;
     const int64_t* comm_last_send = nullptr;   // the buffer the last gd_gather_export reads (it may still be reading it)
     unsigned comm_last_ev = 0;                 // ... and which of comm_ev[0 / 1] is recorded behind it
@@ -296,7 +290,7 @@ struct gd_ctx {
     gd_stats stats{};
 
     bool profiling = false;
-    hipEvent_t ev[GD_K_COUNT + 1] = {};
+    Event ev[GD_K_COUNT + 1];
     float kernel_ms[GD_K_COUNT] = {};
 };
 
@@ -336,64 +330,60 @@ int in_flight(gd_ctx* c)
                         __FILE__, __LINE__);                                           \
     } while (0)
 
-// One device buffer of one call, freed when the call returns however it returns: the only owner of per-call device
-// memory in the ABI (states that live across calls have destructors of their own).  Never allocated: as() is null.
-struct DevBuf {
-    void* p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(gd_ctx* c, size_t bytes)
-    {
-        HIPCHK(c, hipMalloc(&p, bytes ? bytes : 1));
-        return GD_OK;
-    }
-    template <typename T> T* as() const { return static_cast<T*>(p); }
-    void* release() { void* q = p; p = nullptr; return q; }       // the buffer is the caller's from here on
+// One device buffer of one call, freed when the call returns however it returns.  Never allocated: as() is null.
+// (A DevArr of bytes whose alloc reports through the context, as every per-call buffer's did: it stays for that.)
+struct DevBuf : DevArr<uint8_t> {
+    int alloc(gd_ctx* c, size_t bytes) { HIPCHK(c, DevArr<uint8_t>::alloc(bytes)); return GD_OK; }
 };
 
-// Its companion for a call whose number of buffers is only known as it runs: all freed on return, unless release() has
-// handed them to a state that keeps them.
+// Its companion for a call whose number of buffers is only known as it runs: all freed on return.
 struct DevList {
-    std::vector<void*> v;
-    DevList() = default;
-    DevList(const DevList&) = delete;
-    DevList& operator=(const DevList&) = delete;
-    ~DevList() { for (void* p : v) (void)hipFree(p); }
+    std::vector<DevBuf> v;
     // *out = count elements (at least one), zeroed on the context's stream when asked for
     template <typename T>
     int alloc(gd_ctx* c, T** out, size_t count, bool zero = false)
     {
         const size_t bytes = (count ? count : 1) * sizeof(T);
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(out), bytes));
-        v.push_back(*out);
+        v.emplace_back();
+        if (int r = v.back().alloc(c, bytes)) return r;
+        *out = v.back().template as<T>();
         if (zero) HIPCHK(c, hipMemsetAsync(*out, 0, bytes, c->stream));
         return GD_OK;
     }
-    void release() { v.clear(); }
 };
 
-// Room for `need` elements in a device array the context keeps (grow-only, by half at least); with keep, the first `used`
-// stay.  Waits for both of the context's streams before the old block goes.
+// Exactly `ncap` elements for a device array the context keeps; with keep, the first `used` stay.  The new block first,
+// then the copy on the copy stream, then a wait for both of the context's streams, then the old block goes.
 template <typename Tp>
-int ensure_dev(gd_ctx* c, Tp** p, size_t* cap, size_t need, bool keep = false, size_t used = 0)
+int regrow_dev(gd_ctx* c, DevArr<Tp>& a, size_t ncap, bool keep, size_t used)
 {
-    if (need <= *cap && *p) return GD_OK;
-    size_t ncap = std::max(need, *cap + *cap / 2);
-    if (ncap == 0) ncap = 1;
-    DevBuf nb;                                   // (freed again when the copy or a synchronisation fails)
-    if (int r = nb.alloc(c, ncap * sizeof(Tp))) return r;
-    if (*p) {
+    DevArr<Tp> nb;                               // (freed again when the copy or a synchronisation fails)
+    HIPCHK(c, nb.alloc(ncap));
+    if (a) {
         if (keep && used)
-            HIPCHK(c, hipMemcpyAsync(nb.p, *p, used * sizeof(Tp), hipMemcpyDeviceToDevice, c->copy_stream));
+            HIPCHK(c, hipMemcpyAsync(nb.get(), a.get(), used * sizeof(Tp), hipMemcpyDeviceToDevice, c->copy_stream));
         HIPCHK(c, hipStreamSynchronize(c->copy_stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(*p));
+        HIPCHK(c, a.reset_checked());
     }
-    *p = static_cast<Tp*>(nb.release());
-    *cap = ncap;
+    a = std::move(nb);                           // (onto an empty owner: no second free)
     return GD_OK;
+}
+
+// Room for `need` elements in such an array: grow-only, by half at least.
+template <typename Tp>
+int ensure_dev(gd_ctx* c, DevArr<Tp>& a, size_t need, bool keep = false, size_t used = 0)
+{
+    if (need <= a.cap() && a) return GD_OK;
+    return regrow_dev(c, a, std::max(need, a.cap() + a.cap() / 2), keep, used);
+}
+
+// A state kept across calls (gd_ctx::cov, ic, isp, ec) goes: not before the kernels that read its arrays have ended.
+template <class S>
+void drop_state(gd_ctx* c, std::unique_ptr<S>& s)
+{
+    if (s) (void)hipStreamSynchronize(c->stream);
+    s.reset();
 }
 
 void drop_ck(ContigHost& h)
@@ -405,26 +395,12 @@ void drop_ck(ContigHost& h)
     h.ck_ok = false;
 }
 
+// Everything but the length starts over; what the contig owns is freed (adopted records are borrowed: they are not).
 void free_contig(ContigHost& h)
 {
-    drop_ck(h);
-    if (!h.adopted) {
-        if (h.pos) (void)hipFree(h.pos);
-        if (h.flag) (void)hipFree(h.flag);
-        if (h.mapq) (void)hipFree(h.mapq);
-        if (h.off) (void)hipFree(h.off);
-        if (h.cigar) (void)hipFree(h.cigar);
-    }
-    if (h.ridx) (void)hipFree(h.ridx);
-    h.ridx = nullptr; h.ridx_reads = 0;
-    h.ing_left = false;
-    h.pos = nullptr; h.flag = nullptr; h.mapq = nullptr; h.off = nullptr; h.cigar = nullptr;
-    h.n_reads = h.n_ops = h.cap_reads = h.cap_ops = 0;
-    h.adopted = false;
-    h.last_pos = -0x7fffffff;
-    h.base_off = h.win_off = -1;
-    h.n_win = 0;
-    h.run_beg = h.run_end = 0;
+    const int64_t length = h.length;
+    h = ContigHost();
+    h.length = length;
 }
 
 int64_t derive_step(const gd_params& p)
@@ -542,7 +518,7 @@ int launch_scan(gd_ctx* c, uint32_t* v, uint32_t n)
         return GD_OK;
     }
     const uint32_t nb = (n + gd::SCAN_BLOCK - 1u) / gd::SCAN_BLOCK;
-    if (int r = ensure_dev(c, &c->d_scan_tmp, &c->cap_scan_tmp, (size_t)nb + 1)) return r;
+    if (int r = ensure_dev(c, c->d_scan_tmp, (size_t)nb + 1)) return r;
     hipLaunchKernelGGL(gd::gd_scan_totals_kernel, dim3(nb), dim3(256), 0, c->stream, v, n, c->d_scan_tmp);
     hipLaunchKernelGGL(gd::gd_unit_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_scan_tmp, nb);
     hipLaunchKernelGGL(gd::gd_scan_apply_kernel, dim3(nb), dim3(256), 0, c->stream, v, n, c->d_scan_tmp, nb);
@@ -550,7 +526,7 @@ int launch_scan(gd_ctx* c, uint32_t* v, uint32_t n)
 }
 
 // ---- derived record arrays, built per BATCH of contigs ----------------------------------------------------
-// Bump allocation inside one DevBlock: every array starts on a 256-byte boundary.
+// Bump allocation inside one block: every array starts on a 256-byte boundary.
 struct Carve {
     size_t at = 0;
     size_t take(size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; }
@@ -560,26 +536,23 @@ struct Carve {
 // is large enough -- a re-normalisation of the same contigs allocates nothing -- else a new allocation.
 int batch_block(gd_ctx* c, BlockRef keep, size_t need, BlockRef* out)
 {
-    if (keep && keep.use_count() == 1 && keep->bytes >= need) { *out = std::move(keep); return GD_OK; }
+    if (keep && keep.use_count() == 1 && keep->cap() >= need) { *out = std::move(keep); return GD_OK; }
     keep.reset();
-    BlockRef b = std::make_shared<DevBlock>();
+    BlockRef b = std::make_shared<DevArr<uint8_t>>();
     const auto ta = std::chrono::steady_clock::now();
-    HIPCHK(c, hipMalloc(&b->p, need ? need : 1));
+    HIPCHK(c, b->alloc(need));
     // (a first large allocation can wait for the driver to clear memory another process -- or this one -- just released:
     // 0.4 ms on one box, half a second on another; gd_compute_timing reports it with the other device allocations)
     c->alloc_in_enqueue += std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count();
-    b->bytes = need ? need : 1;
     *out = std::move(b);
     return GD_OK;
 }
 
 int batch_host(gd_ctx* c, size_t words)
 {
-    if (words <= c->cap_h_batch && c->h_batch) return GD_OK;
-    if (c->h_batch) { (void)hipHostFree(c->h_batch); c->h_batch = nullptr; c->cap_h_batch = 0; }
-    const size_t cap = std::max<size_t>(words, 256);
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_batch), cap * sizeof(uint32_t), hipHostMallocDefault));
-    c->cap_h_batch = cap;
+    if (words <= c->h_batch.cap() && c->h_batch) return GD_OK;
+    c->h_batch.reset();
+    HIPCHK(c, c->h_batch.alloc(std::max<size_t>(words, 256)));
     return GD_OK;
 }
 
@@ -624,7 +597,7 @@ int ck_enqueue(gd_ctx* c, const std::vector<ContigHost*>& hs, CkPending* P)
     P->o_jobs = cv.take(nj * sizeof(gd::DelJob) + (nj + 1) * sizeof(uint32_t));   // the jobs, then ubeg
     P->o_tot = cv.take(2 * nj * sizeof(uint32_t));               // [deletions x n][largest spans x n]
     if (int r = batch_block(c, std::move(keep), cv.at, &P->blk)) return r;
-    char* const base = static_cast<char*>(P->blk->p);
+    char* const base = P->blk->as<char>();
     // job table (host copy kept in the context until the next batch)
     c->batch_tab_ck.assign(nj * sizeof(gd::DelJob) + (nj + 1) * sizeof(uint32_t), 0);
     gd::DelJob* jobs = reinterpret_cast<gd::DelJob*>(c->batch_tab_ck.data());
@@ -670,7 +643,7 @@ int ck_readback(gd_ctx* c, const CkPending& P, uint32_t* dst)
 {
     const size_t nj = P.hs.size();
     if (nj == 0) return GD_OK;
-    char* const base = static_cast<char*>(P.blk->p);
+    char* const base = P.blk->as<char>();
     // (dst is page-locked: a one-wave kernel stores the 2 n words there -- no copy commands; there used to be 1 + n of them)
     hipLaunchKernelGGL(gd::gd_copy_words_kernel, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<const uint32_t*>(base + P.o_tot), dst,
                        (uint32_t)(2 * nj));
@@ -796,11 +769,7 @@ struct IngestState {
     // and the upload of the bytes still to come.
     static constexpr int kBatches = 8;
     int n_launch = 0;
-    std::vector<hipEvent_t> inf_done;                   // one per inflate launch of THIS range
+    std::vector<gd_own::Event> inf_done;                // one per inflate launch of THIS range
     bool inflated = false;                              // every member inflated and its status checked
-    ~IngestState()
-    {
-        for (hipEvent_t e : inf_done) (void)hipEventDestroy(e);
-        if (bufs) bufs->busy = false;
-    }
+    ~IngestState() { if (bufs) bufs->busy = false; }
 };

@@ -90,7 +90,7 @@ static int sv_run(gd_ctx* c, const float* d_src, float* d_dst, size_t n_rows, in
                        c->stream, j);
     HIPCHK(c, hipGetLastError());
     std::vector<double> V(N * N), w;             // G is symmetric to the bit: row-major is gd_eigh.hpp's column-major
-    HIPCHK(c, hipMemcpyAsync(V.data(), d_gram.p, N * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(V.data(), d_gram.get(), N * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->sv_secs[1] = ing_now() - t1;
 
@@ -112,7 +112,7 @@ static int sv_run(gd_ctx* c, const float* d_src, float* d_dst, size_t n_rows, in
     c->sv_secs[2] = ing_now() - t2;
 
     const double t3 = ing_now();
-    if (n) HIPCHK(c, hipMemcpyAsync(d_vt.p, vt.data(), n * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (n) HIPCHK(c, hipMemcpyAsync(d_vt.get(), vt.data(), n * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
     j.n_removed = (int32_t)n;
     if (log2s) sv_project<gd::SvLog2>(c, j, row_grid);
     else sv_project<gd::SvLinear>(c, j, row_grid);
@@ -141,13 +141,13 @@ int gd_svd_debias_scaled(gd_ctx* c, const float* depths, size_t n_rows, int n_sa
     DevBuf d;
     const double t0 = ing_now();
     if (int r = d.alloc(c, bytes)) return r;
-    HIPCHK(c, hipMemcpyAsync(d.p, depths, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d.get(), depths, bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->sv_secs[0] = ing_now() - t0;
     if (int r = sv_run(c, d.as<const float>(), d.as<float>(), n_rows, n_samples, min_variance_pct, scaler, s, n_removed, centre_cells))
         return r;
     const double t4 = ing_now();
-    HIPCHK(c, hipMemcpyAsync(out, d.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, d.get(), bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->sv_secs[4] = ing_now() - t4;
     return GD_OK;
