@@ -32,6 +32,20 @@ class GdIndexcovDims(C.Structure):
                 ("n_samples", C.c_int32), ("n_refs", C.c_int32)]
 
 
+class GdIndexCounts(C.Structure):
+    _fields_ = [("records", C.c_int64), ("range_records", C.c_int64), ("runs", C.c_int64), ("n_no_coor", C.c_int64),
+                ("resume", C.c_uint64), ("slices", C.c_int32), ("guesses", C.c_int32), ("rounds", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class GdIndexRun(C.Structure):
+    _fields_ = [("ref", C.c_int32), ("bin", C.c_uint32), ("beg", C.c_uint64), ("end", C.c_uint64)]
+
+
+class GdIndexRef(C.Structure):
+    _fields_ = [("first_beg", C.c_uint64), ("last_end", C.c_uint64), ("n_mapped", C.c_uint64), ("n_unmapped", C.c_uint64)]
+
+
 class GdStats(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_ops", C.c_uint64), ("n_ref_bases", C.c_uint64),
                 ("n_windows", C.c_uint64), ("n_tiles", C.c_uint64), ("n_runs", C.c_uint64),
@@ -102,6 +116,12 @@ SYMBOLS = {
     "gd_covstats_begin": (C.c_int, [_P, C.c_int64, C.c_int64]),
     "gd_covstats_decode": (C.c_int, [_P, C.c_uint64, _P, C.c_size_t, C.c_int, _P]),
     "gd_covstats_histogram": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
+    "gd_index_begin": (C.c_int, [_P, C.c_int32, _P, C.c_uint64, C.c_uint64]),
+    "gd_index_decode": (C.c_int, [_P, C.c_int, _P]),
+    "gd_index_result": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P, C.c_size_t, C.POINTER(C.c_size_t), _P,
+                                  C.POINTER(C.c_uint64)]),
+    "gd_index_windows": (C.c_int, [_P, _P, C.c_size_t]),
+    "gd_index_timing": (C.c_int, [_P, _P, C.c_size_t]),
     "gd_indexcov_upload": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "gd_indexcov_get_dims": (C.c_int, [_P, _P, _P, _P, _P]),
     "gd_indexcov_medians": (C.c_int, [_P, _P]),

@@ -4,7 +4,7 @@
 // gd_create, the setters (stream, parameters, path, outputs, contigs, selection), options, statistics and timing; then
 // the gd_api_*.inc files with the rest of the ABI, in this order: records (pinned staging ring + copy stream, records
 // host -> HBM, HBM-resident per-contig record streams), compute (route, launch sequencing, look-back), results
-// (read-back), aux, ingest, covstats, indexcov, indexsplit, crai, devmat, emdepth, emcnv, colselect, chunkdebias,
+// (read-back), aux, ingest, covstats, index, indexcov, indexsplit, crai, devmat, emdepth, emcnv, colselect, chunkdebias,
 // movdebias, svddebias, cnveval, comm; and behind them, where every kept state is a complete type, gd_destroy.  What the
 // context holds is owned by its members (gd_own.hpp, gd_api_state.hpp): gd_destroy is the order of the teardown, the
 // context's destructor the inventory.
@@ -284,6 +284,18 @@ int gd_set_option(gd_ctx* c, int option, int64_t value)
         if (value < 0 || value > (1 << 30)) return fail(c, GD_E_INVALID, "moving debias segment: 0 (the default for the window) or 1 .. 2^30 sorted rows");
         c->md_segment = value;
         break;
+    case GD_OPT_INDEX_SLICE:
+        if (value < 64 || value > (1 << 30)) return fail(c, GD_E_INVALID, "index slice: 64 .. 2^30 bytes");
+        c->idx_slice = value;
+        break;
+    case GD_OPT_INDEX_GUESS_CHECKS:
+        if (value < 0 || value > 64) return fail(c, GD_E_INVALID, "index guess checks: 0 .. 64 records");
+        c->idx_checks = (int)value;
+        break;
+    case GD_OPT_INDEX_REPAIR_ROUNDS:
+        if (value < 0 || value > (1 << 20)) return fail(c, GD_E_INVALID, "index repair rounds: 0 .. 2^20");
+        c->idx_repair_rounds = (int)value;
+        break;
     // retired (include/goleft_depth.h): the number is reserved and only the default is accepted
     case GD_OPT_INGEST_PIECE_STREAMS: case GD_OPT_INFLATE_LDS_PAD: case GD_OPT_INGEST_HYBRID: case GD_OPT_INGEST_BATCHES:
     case GD_OPT_INGEST_WALK_CUS:
@@ -316,6 +328,9 @@ int gd_get_option(gd_ctx* c, int option, int64_t* value)
     case GD_OPT_INGEST_RANGE_HINT: *value = (int64_t)c->ing_range_hint; break;
     case GD_OPT_INFLATE_KERNEL: *value = c->inflate_kernel; break;
     case GD_OPT_MOVDEBIAS_SEGMENT: *value = c->md_segment; break;
+    case GD_OPT_INDEX_SLICE: *value = c->idx_slice; break;
+    case GD_OPT_INDEX_GUESS_CHECKS: *value = c->idx_checks; break;
+    case GD_OPT_INDEX_REPAIR_ROUNDS: *value = c->idx_repair_rounds; break;
     case GD_OPT_INGEST_PIECE_STREAMS: case GD_OPT_INFLATE_LDS_PAD: case GD_OPT_INGEST_HYBRID: case GD_OPT_INGEST_BATCHES:
     case GD_OPT_INGEST_WALK_CUS: *value = retired_option_default(option); break;
     default: return fail(c, GD_E_INVALID, "unknown option %d", option);
@@ -358,6 +373,7 @@ int gd_kernel_ms(gd_ctx* c, int id, float* ms)
 #include "gd_api_aux.inc"
 #include "gd_api_ingest.inc"
 #include "gd_api_covstats.inc"
+#include "gd_api_index.inc"
 #include "gd_api_indexcov.inc"
 #include "gd_api_indexsplit.inc"
 #include "gd_api_crai.inc"
@@ -379,6 +395,7 @@ void gd_destroy(gd_ctx* c)
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     (void)gd_ingest_abort(c);      // joins the reader thread; the pending IngestStates go before the IngestBufs they point into
     drop_state(c, c->cov);
+    drop_state(c, c->idx);
     drop_state(c, c->ic);
     drop_state(c, c->isp);
     drop_state(c, c->ec);

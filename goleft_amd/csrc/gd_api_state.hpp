@@ -85,7 +85,7 @@ struct RingSlot {
 
 // State of a device BAM read between gd_ingest_begin and gd_ingest_finish.
 struct IngestState;
-namespace { struct FillPool; struct CovState; struct IcState; struct IsState; struct EcState; }
+namespace { struct FillPool; struct CovState; struct IdxState; struct IcState; struct IsState; struct EcState; }
 
 // Device buffers of one pending range (compressed bytes, inflated bytes, member tables): grow-only and
 // kept by the context between ranges -- allocating and freeing gigabytes per range cost 0.1-0.2 s.
@@ -253,6 +253,11 @@ struct gd_ctx {
     DevArr<uint32_t> d_scan_tmp;                               // launch_scan: block totals
     DevArr<uint8_t> d_rectab;                                  // ... and the record table the counting walk leaves for the extraction (device, grow-only)
     std::unique_ptr<CovState> cov;                             // gd_covstats_*: the sampling state and its buffers (gd_api_covstats.inc)
+    std::unique_ptr<IdxState> idx;                             // gd_index_*: the runs, linear index and counts of the file so far (gd_api_index.inc)
+    int64_t idx_slice = 65536;                                 // GD_OPT_INDEX_SLICE
+    int idx_checks = 3;                                        // GD_OPT_INDEX_GUESS_CHECKS
+    int idx_repair_rounds = 4;                                 // GD_OPT_INDEX_REPAIR_ROUNDS
+    double idx_secs[5] = {0, 0, 0, 0, 0};                      // gd_index_timing
     std::unique_ptr<IcState> ic;                               // gd_indexcov_*: the cohort's tile sizes and results (gd_api_indexcov.inc)
     std::unique_ptr<IsState> isp;                              // gd_indexsplit_*: the cohort's cell sums (gd_api_indexsplit.inc)
     std::unique_ptr<EcState> ec;                               // gd_emcnv_*: the positions, member bits and member values of the rows so far (gd_api_emcnv.inc)

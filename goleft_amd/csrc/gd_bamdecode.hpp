@@ -15,6 +15,9 @@
 //                          mapq / cigar_off / cigar at the segment's base (exclusive prefix sums of the counts, host side)
 //   gd_bam_walk_kernel<true>   the same walk a second time, extracting (when no table fits)
 //   gd_cs_walk_kernel      CsWalk: every record of a range, across references, to a CsRec slot (gd_covstats.hpp)
+//   gd_idx_walk_kernel     IndexWalk: every record of a range to an IdxRec slot -- what a .bai is made of (gd_baiindex.hpp);
+//                          its segments begin at GUESSED record starts (gd_bamguess.hpp), so a corrupt walk is no verdict
+//                          before the host has confirmed the segment's start (gd_api_index.inc)
 // Only the fields `samtools depth -Q q` consults are extracted.
 #pragma once
 
@@ -170,9 +173,15 @@ __device__ __forceinline__ void bam_walk(const Job& j, P p)
         const uint64_t wbase = s_wbase;
         for (uint32_t i = lane; i < BW_WIN / 16; i += 64) {
             const uint64_t a = wbase + 16ull * i;
-            uint32_t w[4] = {0, 0, 0, 0};
+            // (two words in registers, the stream's last bytes gathered one by one: a local array copied with a runtime
+            // length is an alloca, which the compiler moves to LDS -- a kilobyte per workgroup on top of the 3.4 KB below)
+            uint64_t w[2] = {0, 0};
             if (a + 16 <= j.n_bytes) __builtin_memcpy(w, j.data + a, 16);
-            else if (a < j.n_bytes) __builtin_memcpy(w, j.data + a, (size_t)(j.n_bytes - a));
+            else
+                for (uint64_t k = a; k < j.n_bytes; ++k) {
+                    const uint64_t b = (uint64_t)j.data[k] << (8u * (uint32_t)((k - a) & 7u));
+                    if (k - a < 8) w[0] |= b; else w[1] |= b;
+                }
             __builtin_memcpy(s_win + 16u * i, w, 16);
         }
         __syncthreads();
@@ -377,6 +386,105 @@ struct CsWalk {
 };
 
 __global__ __launch_bounds__(64) void gd_cs_walk_kernel(CsWalkJob j) { bam_walk(j, CsWalk{}); }
+
+// One record as the indexer sees it (SAMv1 5.2; DESIGN.md section 3.19, rules 1 and 2).
+struct IdxRec {
+    int32_t  ref;                   // refID (-1: unplaced)
+    int32_t  beg;                   // POS as stored
+    int32_t  end;                   // POS + the reference length of the STORED CIGAR; POS + 1 when unmapped or that length is 0
+    uint32_t bin;                   // reg2bin(beg, end) | IX_UNMAPPED | IX_BADSPAN
+    uint64_t vbeg;                  // virtual offset of the record's first byte
+};
+constexpr uint32_t IX_UNMAPPED = 1u << 31;   // flag 0x4
+constexpr uint32_t IX_BADSPAN = 1u << 30;    // placed, and POS < 0 or end > 2^29: a .bai cannot hold it (end is POS + 1 then)
+constexpr uint32_t IX_BIN = 0xffffu;
+
+__device__ __forceinline__ uint32_t bai_reg2bin(uint32_t beg, uint32_t end)
+{
+    --end;
+    if (beg >> 14 == end >> 14) return 4681u + (beg >> 14);
+    if (beg >> 17 == end >> 17) return 585u + (beg >> 17);
+    if (beg >> 20 == end >> 20) return 73u + (beg >> 20);
+    if (beg >> 23 == end >> 23) return 9u + (beg >> 23);
+    if (beg >> 26 == end >> 26) return 1u + (beg >> 26);
+    return 0u;
+}
+
+struct IdxWalkJob {
+    const uint8_t* data;            // inflated bytes of the range
+    uint64_t n_bytes;
+    const uint64_t* seg_beg;        // [n_seg] where the segment's walk begins: a record start, or a guess at one
+    const uint64_t* seg_end;        // [n_seg] the next guess (the range's last segment: n_bytes)
+    const uint64_t* slot_base;      // [n_seg] first slot of the segment
+    uint32_t n_seg;
+    uint32_t open_end;              // more of the file follows: the segment that ends with the range may end in a cut record
+    IdxRec* slots;
+    uint64_t n_slots;               // nothing is written at or behind this slot
+    uint32_t* n_rec;                // [n_seg]
+    uint64_t* end_off;              // [n_seg] where the walk stopped: the first record start at or behind seg_end
+    uint32_t* flags;                // [n_seg] BW_CORRUPT
+    const uint64_t* m_out;          // [n_mem] the range's members: exclusive sums of their ISIZE (m_out[0] = 0)
+    const uint64_t* m_coff;         // [n_mem] ... and their file offsets
+    uint32_t n_mem;
+    int32_t  n_ref;
+};
+
+struct IndexWalk {
+    static constexpr uint32_t HEAD = 4;
+    static constexpr uint32_t HOLD = 4;
+    uint64_t ri = 0;
+
+    __device__ __forceinline__ void begin(const IdxWalkJob&, uint32_t) {}
+    // a record the range holds only in part ends the walk in front of it (end_off < seg_end tells the host).  In ANY segment:
+    // the guesses behind a cut record lie inside it, so the segment that meets it need not be the last
+    __device__ __forceinline__ uint32_t cut(const IdxWalkJob& j, uint32_t) const { return j.open_end ? 0u : (uint32_t)BW_CORRUPT; }
+    __device__ __forceinline__ BwStep step(const IdxWalkJob&, const uint8_t*, uint64_t, uint64_t, uint32_t&) { return BW_TAKE; }
+    __device__ __forceinline__ bool record(const IdxWalkJob& j, uint32_t s, uint32_t lane, uint64_t o, uint64_t, const uint8_t*)
+    {
+        const uint32_t block_size = ld32(j.data + o);
+        const uint8_t* const r = j.data + o + 4;
+        const uint32_t l_read_name = r[8];
+        const uint32_t n_cigar = (uint32_t)r[12] | ((uint32_t)r[13] << 8);
+        const uint32_t flag = (uint32_t)r[14] | ((uint32_t)r[15] << 8);
+        IdxRec c{(int32_t)ld32(r), (int32_t)ld32(r + 4), 0, 0u, 0ull};
+        const bool ok = 32ull + l_read_name + 4ull * n_cigar <= block_size && c.ref >= -1 && c.ref < j.n_ref;
+        if (ok) {
+            uint64_t rlen = 0;                               // the STORED CIGAR: M D N = X (a CG:B,I tag is not consulted)
+            const uint8_t* const cg = r + 32 + l_read_name;
+            for (uint32_t q = 0; q < n_cigar; ++q) {
+                const uint32_t op = ld32(cg + 4ull * q), t = op & 0xfu;
+                if (t == 0u || t == 2u || t == 3u || t == 7u || t == 8u) rlen += op >> 4;
+            }
+            if ((flag & 4u) || rlen == 0) rlen = 1;
+            const int64_t end = (int64_t)c.beg + (int64_t)rlen;
+            c.end = c.beg + 1;
+            if (flag & 4u) c.bin |= IX_UNMAPPED;
+            if (c.ref >= 0) {
+                if (c.beg < 0 || end > (1ll << 29)) c.bin |= IX_BADSPAN;
+                else { c.end = (int32_t)end; c.bin |= bai_reg2bin((uint32_t)c.beg, (uint32_t)end); }
+            }
+            // the member that holds byte o: the last one that begins at or before it (of several: the one with bytes)
+            uint32_t lo = 0, hi = j.n_mem;                   // m_out[lo] <= o < m_out[hi]
+            while (hi - lo > 1u) {
+                const uint32_t mid = lo + (hi - lo) / 2u;
+                if (j.m_out[mid] <= o) lo = mid; else hi = mid;
+            }
+            c.vbeg = (j.m_coff[lo] << 16) | (o - j.m_out[lo]);
+        }
+        const uint64_t at = j.slot_base[s] + ri + lane;
+        if (at < j.n_slots) j.slots[at] = c;
+        return ok && at < j.n_slots;
+    }
+    __device__ __forceinline__ void emit(const IdxWalkJob&, uint32_t, uint32_t, uint32_t n, const uint64_t*, bool) { ri += n; }
+    __device__ __forceinline__ void finish(const IdxWalkJob& j, uint32_t s, uint64_t off, uint32_t fl) const
+    {
+        j.n_rec[s] = (uint32_t)ri;
+        j.end_off[s] = off;
+        j.flags[s] = fl;
+    }
+};
+
+__global__ __launch_bounds__(64) void gd_idx_walk_kernel(IdxWalkJob j) { bam_walk(j, IndexWalk{}); }
 
 // A THREAD PER RECORD over the table the counting walk left: a workgroup per anchor segment (its record count, bases and
 // table entry come from the walk's tables), the fields and the CIGAR (the stored one or the CG tag's, found again) copied

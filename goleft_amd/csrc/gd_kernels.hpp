@@ -546,6 +546,8 @@ __global__ __launch_bounds__(256) void gd_regions_bounds_kernel(const RegionTab*
 #include "gd_inflate.hpp"
 #include "gd_bamdecode.hpp"
 #include "gd_covstats.hpp"
+#include "gd_bamguess.hpp"
+#include "gd_baiindex.hpp"
 #include "gd_indexcov.hpp"
 #include "gd_indexsplit.hpp"
 #include "gd_crai.hpp"

@@ -459,6 +459,14 @@ bool BamReader::linear_index(const std::string& bam_path, std::vector<std::vecto
 {
     std::vector<uint8_t> d;
     if (!load_bai(bam_path, &d)) return false;
+    return linear_index_bytes(d, per_ref, err, has_chunks, chunk_end, n_mapped, raw, n_unmapped);
+}
+
+bool BamReader::linear_index_bytes(const std::vector<uint8_t>& d, std::vector<std::vector<uint64_t>>* per_ref, std::string* err,
+                                   std::vector<char>* has_chunks, std::vector<uint64_t>* chunk_end, std::vector<int64_t>* n_mapped,
+                                   std::vector<std::vector<uint64_t>>* raw, std::vector<int64_t>* n_unmapped)
+{
+    if (d.size() < 8 || memcmp(d.data(), "BAI\1", 4) != 0) { if (err) *err = "not a BAI"; return false; }
     const int32_t n_ref = (int32_t)rd32(d.data() + 4);
     if (n_ref < 0 || (size_t)n_ref > (d.size() - 8) / 8) {     // every reference takes at least n_bin + n_intv
         if (err) *err = "corrupt BAI";

@@ -126,6 +126,11 @@ public:
                              std::string* err, std::vector<char>* has_chunks = nullptr,
                              std::vector<uint64_t>* chunk_end = nullptr, std::vector<int64_t>* n_mapped = nullptr,
                              std::vector<std::vector<uint64_t>>* raw = nullptr, std::vector<int64_t>* n_unmapped = nullptr);
+    // The same from the index's bytes (an index made in memory: host/index_host.cpp).
+    static bool linear_index_bytes(const std::vector<uint8_t>& bai, std::vector<std::vector<uint64_t>>* per_ref,
+                                   std::string* err, std::vector<char>* has_chunks = nullptr,
+                                   std::vector<uint64_t>* chunk_end = nullptr, std::vector<int64_t>* n_mapped = nullptr,
+                                   std::vector<std::vector<uint64_t>>* raw = nullptr, std::vector<int64_t>* n_unmapped = nullptr);
 
     // Fills `out` with up to max_reads records, all of one contig (a block ends
     // at a contig change).  Records with refID < 0 are skipped and counted.

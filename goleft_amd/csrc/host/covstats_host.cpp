@@ -23,6 +23,7 @@
 
 #include "../../../include/goleft_depth.h"
 #include "../../../include/goleft_depth_host.h"
+#include "bam_head.hpp"
 #include "bam_reader.hpp"
 #include "cli.hpp"
 #include "gpu_ingest.hpp"
@@ -87,44 +88,8 @@ bool ends_with(const std::string& s, const char* suf)
     return s.size() >= n && s.compare(s.size() - n, n, suf) == 0;
 }
 
-// ---- the BAM header: references, @RG SM names, and where the first record begins --------------------------------
-struct Header {
-    std::vector<std::string> names;
-    std::vector<int64_t> lengths;
-    std::string text;
-    uint64_t length = 0;        // bytes of the inflated stream in front of the first record
-};
-
-bool read_header(const std::string& path, Header* h, std::string* err)
-{
-    gzFile f = gzopen(path.c_str(), "rb");
-    if (!f) { *err = "cannot open " + path; return false; }
-    auto rd = [&](void* dst, size_t n) { return n == 0 || gzread(f, dst, (unsigned)n) == (int)n; };
-    uint8_t b4[4];
-    auto u32 = [&](uint32_t* v) { if (!rd(b4, 4)) return false; *v = (uint32_t)b4[0] | ((uint32_t)b4[1] << 8) | ((uint32_t)b4[2] << 16) | ((uint32_t)b4[3] << 24); return true; };
-    char magic[4];
-    uint32_t l_text = 0, n_ref = 0;
-    bool ok = rd(magic, 4) && memcmp(magic, "BAM\1", 4) == 0 && u32(&l_text);
-    if (ok) { h->text.resize(l_text); ok = rd(&h->text[0], l_text) && u32(&n_ref); }
-    h->length = 12ull + l_text;
-    for (uint32_t r = 0; ok && r < n_ref; ++r) {
-        uint32_t l_name = 0, l_ref = 0;
-        std::string name;
-        ok = u32(&l_name) && l_name > 0 && l_name < (1u << 20);
-        if (ok) { name.resize(l_name); ok = rd(&name[0], l_name) && u32(&l_ref); }
-        if (ok) {
-            name.resize(strnlen(name.c_str(), name.size()));
-            h->names.push_back(name);
-            h->lengths.push_back((int64_t)(int32_t)l_ref);
-            h->length += 8ull + l_name;
-        }
-    }
-    gzclose(f);
-    if (!ok) *err = path + ": not a BAM file or a truncated header";
-    const size_t nul = h->text.find('\0');
-    if (nul != std::string::npos) h->text.resize(nul);
-    return ok;
-}
+using Header = gdh::BamHead;
+using gdh::read_bam_head;
 
 // samplename.Names (sample_names.hpp), joined as covstats prints them
 std::string sample_names(const std::string& text)
@@ -345,7 +310,7 @@ int one_bam(gd_ctx* ctx, const CArgs& a, const std::string& bam, int64_t skip, u
     }
     Header h;
     std::string err;
-    if (!read_header(bam, &h, &err)) { fprintf(stderr, "covstats: %s\n", err.c_str()); return 1; }
+    if (!read_bam_head(bam, &h, &err)) { fprintf(stderr, "covstats: %s\n", err.c_str()); return 1; }
     const std::string names = sample_names(h.text);
     // the index: only for a path ending in .bam (x.bam.bai, else x.bai); a missing one is fatal
     std::vector<std::vector<uint64_t>> lin;
@@ -367,20 +332,7 @@ int one_bam(gd_ctx* ctx, const CArgs& a, const std::string& bam, int64_t skip, u
     double t0 = now_s();
     uint64_t first_voff = 0;
     bool have_first = false;
-    {
-        gdh::MemberTable mt;
-        uint64_t span = std::min<uint64_t>(fm.size, 1u << 20);
-        for (;;) {
-            if (!gdh::list_members_serial_fd(fm.fd, 0, (size_t)span, &mt)) { fprintf(stderr, "covstats: %s: not a BGZF file\n", bam.c_str()); return 1; }
-            uint64_t cum = 0;
-            for (size_t m = 0; m < mt.n && !have_first; ++m) {
-                if (h.length < cum + mt.isize[m]) { first_voff = (mt.off[m] << 16) | (h.length - cum); have_first = true; }
-                cum += mt.isize[m];
-            }
-            if (have_first || span >= fm.size) break;
-            span = std::min<uint64_t>(fm.size, span * 4);
-        }
-    }
+    if (!gdh::first_record_voffset(fm.fd, fm.size, h.length, &first_voff, &have_first)) { fprintf(stderr, "covstats: %s: not a BGZF file\n", bam.c_str()); return 1; }
     tm->list += now_s() - t0;
     CS_CHECK(gd_covstats_begin(ctx, a.n, skip));
     gd_covstats_counts cnt{};

@@ -28,6 +28,7 @@
 #include "cli.hpp"
 #include "fasta_stats.hpp"
 #include "gpu_ingest.hpp"
+#include "index_build.hpp"
 
 namespace {
 
@@ -457,6 +458,13 @@ static bool run_on_every_shard(Shards& S, const char* what, const std::function<
 
 struct ReadTimes { std::chrono::steady_clock::time_point indexed, mapped, read; };
 
+// Is there a file where the .bai of `bam` is looked for (x.bam.bai, x.bai)?
+static bool index_file_exists(const std::string& bam)
+{
+    if (access((bam + ".bai").c_str(), F_OK) == 0) return true;
+    return bam.size() > 4 && bam.compare(bam.size() - 4, 4, ".bam") == 0 && access((bam.substr(0, bam.size() - 4) + ".bai").c_str(), F_OK) == 0;
+}
+
 // ---- records into HBM (replaces the samtools children) ---------------------------
 // With a .bai next to the BAM (goleft depth needs one anyway: `samtools depth -r`), the whole
 // read happens on the device: the contig's byte range goes to gd_ingest_bgzf, which inflates
@@ -480,6 +488,19 @@ static int read_records(const DArgs& args, gdh::BamReader& bam, const std::vecto
         const char* gd_env = getenv("GOLEFT_GPU_DECODE");
         bool gpu_decode = !(gd_env && gd_env[0] == '0') && gdh::BamReader::linear_index(args.bam, &lin, &err, &has_chunks, &chunk_end) &&
                           lin.size() == contigs.size();
+        // GOLEFT_GPU_INDEX=1: a BAM whose index is NOT FOUND gets one made on the device, in memory (host/index_host.cpp; it is
+        // not written), and the read below takes the device path with it.  An index that is there but unusable stays what it was.
+        const char* gi_env = getenv("GOLEFT_GPU_INDEX");
+        if (!gpu_decode && gi_env && gi_env[0] == '1' && !(gd_env && gd_env[0] == '0') && !index_file_exists(args.bam)) {
+            std::vector<uint8_t> bai;
+            std::string ierr;
+            const int rc = gdh::build_bai(S.v[0].ctx, args.bam, &bai, &ierr);
+            if (rc != GD_OK) {
+                fprintf(stderr, "goleft depth: %s: cannot index on the device: %s\n", args.bam.c_str(), ierr.c_str());
+                return 1;
+            }
+            gpu_decode = gdh::BamReader::linear_index_bytes(bai, &lin, &err, &has_chunks, &chunk_end) && lin.size() == contigs.size();
+        }
         // a reference whose bins hold chunks but whose linear index is empty (a non-htslib indexer):
         // the anchors cannot be trusted to mean "no records" -> host decoder
         for (size_t r = 0; gpu_decode && r < lin.size(); ++r)

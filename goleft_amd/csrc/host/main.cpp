@@ -10,6 +10,7 @@
 //   goleft-depth scales [--level L] matrix.bed[.gz]                         (the factors emdepth --scales takes: dcnv's sample medians carried to one level)
 //   goleft-depth debias (--gc-values FILE | --fasta ref.fa) [--window W] matrix.bed[.gz]   (dcnv's ChunkDebiaser: the matrix freed of GC bias; emdepth takes the same as --gc-values | --gc-fasta, --gc-window)
 //   goleft-depth cnveval [-m MINOVERLAP] [-s] truth.bed[.gz] test.bed[.gz]   (the reference's cnveval command: precision and recall of a call set, per size class)
+//   goleft-depth index [-o OUT.bai] a.bam                                   (a .bai as htslib writes it, made on the device: no samtools needed)
 //   goleft-depth samplename [-e] a.bam                                     (goleft samplename: the @RG SM values)
 //   samtools depth -Q q -d D -r REGION in.bam                   (the same program installed under the NAME samtools,
 //                                                                goleft_amd/shim/samtools: an unmodified goleft finds it on PATH)
@@ -40,7 +41,8 @@ static const Entry kEntries[] = {
     {"covstats", "covstats", gdh_covstats_main},        {"indexcov", "indexcov", gdh_indexcov_main},
     {"indexsplit", "indexsplit", gdh_indexsplit_main},  {"emdepth", "emdepth", gdh_emdepth_main},
     {"scales", "scales", gdh_scales_main},              {"debias", "debias", gdh_debias_main},
-    {"samplename", "samplename", gdh_samplename_main},  {"cnveval", "cnveval", gdh_cnveval_main}};
+    {"samplename", "samplename", gdh_samplename_main},  {"cnveval", "cnveval", gdh_cnveval_main},
+    {"index", "index", gdh_index_main}};
 
 int main(int argc, char** argv)
 {

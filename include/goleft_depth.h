@@ -236,6 +236,12 @@ enum { GD_OPT_NT_STORES = 3,        /* 1 (default): non-temporal per-base stores
                                        and do not need the verdict block by block; gdh_produce_in_place runs this way */
        GD_OPT_MOVDEBIAS_SEGMENT = 26, /* gd_moving_debias*: sorted rows a workgroup owns: 0 (default) 256 for a window up to 63, 1024
                                        above; 1 .. 2^30.  A test knob: the results do not depend on it */
+       GD_OPT_INDEX_SLICE = 27,       /* gd_index_decode: bytes of the inflated stream per slice in which a record start is guessed:
+                                       65536 (default), 64 .. 2^30.  A test knob: the results do not depend on it */
+       GD_OPT_INDEX_GUESS_CHECKS = 28, /* ... and how many records the chain behind a candidate must stay a record: 3 (default),
+                                       0 .. 64.  With 0 nearly every guess is wrong; the results do not depend on it */
+       GD_OPT_INDEX_REPAIR_ROUNDS = 29, /* ... and after how many repair rounds whatever is still unconfirmed is walked as ONE segment behind
+                                       the confirmed ones: 4 (default), 0 (at once) .. 2^20 (in effect never).  A test knob as well */
 
        /* ---- RETIRED ----
         * Switches of link and occupancy experiments that were measured neutral or worse on an MI355X; their code is gone
@@ -585,6 +591,45 @@ int gd_covstats_decode(gd_ctx* ctx, uint64_t first_voffset, const uint64_t* anch
  * unordered (overflow: NULL or room for cap; *n_overflow: how many there are). */
 int gd_covstats_histogram(gd_ctx* ctx, int which, int64_t* lo, size_t* n_bins, uint64_t* bins, int64_t* overflow,
                           size_t cap, size_t* n_overflow);
+/* ---- a BAM's .bai (SAMv1 5.2) from the fed ranges of the device BAM read: no index needed, one is made ----
+ * gd_index_begin starts a run over ONE file: its references (n_ref lengths from the header), the virtual offset of its
+ * first record and its size.  Then, range after range in file order (gd_ingest_begin + gd_ingest_feed*; a range begins
+ * with the member that holds the previous call's `resume`), gd_index_decode walks every record of the oldest pending
+ * range and drops the range.  Record starts are GUESSED per slice of the inflated bytes (GD_OPT_INDEX_SLICE,
+ * GD_OPT_INDEX_GUESS_CHECKS) and CONFIRMED by the walk: a wrong guess costs a repair round, never the answer (`rounds`).
+ * last_range: the range ends the file (a record it holds only in part is an error); otherwise that record is where
+ * the next range resumes.  gd_index_result gives what a .bai is assembled from (gdh_bai_assemble of the host library):
+ * the runs -- maximal stretches of consecutive records of one (reference, bin), begin and end as virtual offsets, in file
+ * order, as if the file had been one range --, the linear index before its backward fill (entry lin_off[r] + w of
+ * reference r's 16 kb window w; all ones: no record touches the window; gd_index_windows gives lin_off[0 .. n_ref]: a
+ * reference has its length in windows and a few more, and the array grows when a read hangs further over the end than
+ * that, so ask after the last decode) and per reference the pseudo-bin's four words.  Every output may be NULL; a
+ * capacity below what is there is GD_E_CAPACITY with the counts set.
+ * Errors (gd_last_error names the record): GD_E_UNSORTED -- positions go backwards inside a reference, a reference
+ * resumes after another began, a placed record follows an unplaced one; GD_E_INVALID -- a damaged member or record, a
+ * placed record with a negative position or an end beyond 2^29.  gd_index_result before the file's last range has been
+ * decoded is GD_E_STATE. */
+typedef struct gd_index_counts {
+    int64_t records;          /* records walked since gd_index_begin */
+    int64_t range_records;    /* ... in the last range */
+    int64_t runs;             /* runs so far (the last one may still grow) */
+    int64_t n_no_coor;        /* records with refID < 0 so far */
+    uint64_t resume;          /* as gd_covstats_counts.resume */
+    int32_t slices;           /* of the last range: slices, */
+    int32_t guesses;          /* ... those with a guess, */
+    int32_t rounds;           /* ... and repair rounds: walks after the first (0: every guess was a record start) */
+    int32_t reserved;
+} gd_index_counts;
+typedef struct gd_index_run { int32_t ref; uint32_t bin; uint64_t beg, end; } gd_index_run;
+typedef struct gd_index_ref { uint64_t first_beg, last_end, n_mapped, n_unmapped; } gd_index_ref;   /* no records: all 0 */
+int gd_index_begin(gd_ctx* ctx, int32_t n_ref, const int64_t* ref_len, uint64_t first_voffset, uint64_t file_size);
+int gd_index_decode(gd_ctx* ctx, int last_range, gd_index_counts* out);
+int gd_index_windows(gd_ctx* ctx, uint64_t* lin_off, size_t cap);   /* cap >= n_ref + 1 */
+int gd_index_result(gd_ctx* ctx, gd_index_run* runs, size_t cap_runs, size_t* n_runs, uint64_t* linear, size_t cap_linear,
+                    size_t* n_linear, gd_index_ref* refs, uint64_t* n_no_coor);
+/* Seconds since gd_index_begin (measurement only): out[0] waiting for the inflate launches, [1] guessing, [2] the walks,
+ * all rounds, [3] compaction, runs and linear kernels, [4] read-back.  Fills min(n, 5) values. */
+int gd_index_timing(gd_ctx* ctx, double* out, size_t n);
 /* ---- `goleft indexcov` (indexcov/indexcov.go, types.go) on the tile sizes of a cohort of .bai linear indexes ----
  * gd_indexcov_upload takes, for n_samples samples, EVERY tile size of every reference of each index (sizes, the
  * samples one after the other: sample s owns [sample_off[s], sample_off[s + 1]), never empty, never negative) --

@@ -270,6 +270,28 @@ int gdh_cnveval_main(int argc, const char* const* argv);
 /* Same, writing to out_path (NULL = stdout). */
 int gdh_cnveval_run(int argc, const char* const* argv, const char* out_path);
 
+/* ---- `index`: a BAM's .bai (SAMv1 5.2) as htslib's indexer writes it, made on the device (gd_index_*; DESIGN.md section
+ * 3.19).  argv: [-o OUT.bai] in.bam; the index goes to in.bam.bai, or to -o, through a temporary file and a rename.
+ * GOLEFT_INDEX_TIMING=1 prints where the time went on stderr; GOLEFT_INDEX_RANGE_BYTES, GOLEFT_INDEX_SLICE and
+ * GOLEFT_INDEX_GUESS_CHECKS are test knobs: the bytes do not depend on them.  Returns the exit code: 0; 2 for a file that is
+ * not coordinate sorted, 1 for any other error -- each with a message that names the record, and nothing written; 255 on a
+ * usage error. ------------------------------------------------------------------------------------------------------- */
+int gdh_index_main(int argc, const char* const* argv);
+int gdh_index_run(int argc, const char* const* argv);
+/* The same index in memory: *out (gdh_index_free) and *n_out; stats (NULL, or room for three): records, repair rounds,
+ * ranges.  Returns a gd_* status, its message in errbuf. */
+int gdh_index_build(const char* bam, uint8_t** out, size_t* n_out, int64_t* stats, char* errbuf, size_t errcap);
+void gdh_index_free(uint8_t* p);
+/* The index arithmetic alone (no device): the runs of consecutive records of one (reference, bin) in file order -- grouped
+ * by ascending reference --, the linear index before its backward fill (reference r's windows at lin_off[r] ..
+ * lin_off[r + 1]; all ones: untouched) and the pseudo-bin's words per reference (no records: n_mapped + n_unmapped == 0)
+ * -> the .bai's bytes: htslib's bin compression (level 5 up to 1: a bin spanning fewer than 65536 compressed bytes joins
+ * its parent when that exists), chunks sorted and merged where they meet inside one BGZF member, bins ascending with the
+ * pseudo-bin 37450 last, n_intv = the last touched window + 1, n_no_coor at the end.  Returns the size of the index (written
+ * to out when cap holds it), -1 for arguments that are no such input. */
+int64_t gdh_bai_assemble(int32_t n_ref, const gd_index_run* runs, size_t n_runs, const uint64_t* lin_off, const uint64_t* linear,
+                         const gd_index_ref* refs, uint64_t n_no_coor, uint8_t* out, size_t cap);
+
 /* ---- BAM decode (replaces the read side of the samtools child) ---------- */
 /* How `goleft-depth` cuts a BAM into device passes (host/gpu_ingest.hpp; exported for tests):
  * start[r] / has[r] describe the n_refs references of the file (offset of the BGZF member of r's first
