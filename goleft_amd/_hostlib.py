@@ -43,8 +43,11 @@ SYMBOLS = {
     "gdh_index_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_index_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_index_build": (C.c_int, [C.c_char_p, C.POINTER(_P), C.POINTER(C.c_size_t), _P, C.c_char_p, C.c_size_t]),
+    "gdh_index_build_csi": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t), _P, C.c_char_p, C.c_size_t]),
     "gdh_index_free": (None, [_P]),
     "gdh_bai_assemble": (C.c_int64, [C.c_int32, _P, C.c_size_t, _P, _P, _P, C.c_uint64, _P, C.c_size_t]),
+    "gdh_csi_assemble": (C.c_int64, [C.c_int32, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.c_int32, C.c_int32, _P, C.c_size_t]),
+    "gdh_csi_read": (C.c_int, [_P, C.c_size_t, C.c_int32, _P, _P, C.c_size_t, _P, C.c_char_p, C.c_size_t]),
     "gdh_samplename_main":(C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_crai_read": (C.c_int, [C.c_char_p, C.c_size_t, C.c_size_t, _P, _P, _P, _P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                 C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]),

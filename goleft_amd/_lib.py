@@ -117,6 +117,7 @@ SYMBOLS = {
     "gd_covstats_decode": (C.c_int, [_P, C.c_uint64, _P, C.c_size_t, C.c_int, _P]),
     "gd_covstats_histogram": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
     "gd_index_begin": (C.c_int, [_P, C.c_int32, _P, C.c_uint64, C.c_uint64]),
+    "gd_index_begin_csi": (C.c_int, [_P, C.c_int32, _P, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32]),
     "gd_index_decode": (C.c_int, [_P, C.c_int, _P]),
     "gd_index_result": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P, C.c_size_t, C.POINTER(C.c_size_t), _P,
                                   C.POINTER(C.c_uint64)]),

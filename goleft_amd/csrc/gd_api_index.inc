@@ -1,4 +1,5 @@
-// gd_api_index.inc -- a BAM's .bai from the fed ranges of the device BAM read: begin (references, first record, file size)
+// gd_api_index.inc -- a BAM's .bai or .csi from the fed ranges of the device BAM read: begin (references, first record, file
+// size; gd_index_begin_csi: and the binning scheme)
 // / decode (guess, walk and confirm, runs, linear index of the oldest pending range) / result (part of gd_api.hip, inside
 // extern "C").  The guesses are gd_bamguess.hpp's, the walk gd_bamdecode.hpp's (IndexWalk), the other kernels
 // gd_baiindex.hpp's; what a decode begins with is gd_api_ingest.inc's, shared with the depth read and covstats.  The
@@ -13,6 +14,9 @@ struct IdxState {
     bool has_prev = false, finished = false;
     std::vector<int64_t> ref_len;              // as given
     uint64_t slack = 4;                        // windows every reference has beyond its length (grows when a read hangs further over)
+    uint32_t min_shift = 14, depth = 5;        // the binning scheme: a .bai's unless gd_index_begin_csi gave another
+    int64_t max_end = 1ll << 29;               // where a placed record may end at most
+    bool csi = false;
     gd::IdxRec prev{};                         // the last record of the range before
     std::vector<gd_index_run> runs;            // in file order, unplaced ones (ref -1) included: they end the run in front
     gd_index_counts tot{};
@@ -30,20 +34,26 @@ struct IdxSeg {
     bool ok = false, dirty = true;
 };
 
-// A reference's share of the linear array: its length in 16 kb windows and `slack` more (a read may hang over the end), at
-// most what a .bai can address.
+// The most windows a reference can have: what the geometry can address (32768 in a .bai).
+static uint64_t idx_max_windows(const IdxState& s) { return ((uint64_t)s.max_end + (1ull << s.min_shift) - 1) >> s.min_shift; }
+
+// A reference's share of the linear array: its length in windows of 2^min_shift positions (16 kb in a .bai) and `slack`
+// more (a read may hang over the end), at most what the geometry can address.
 static void idx_layout(IdxState& s)
 {
     s.lin_off.assign((size_t)s.n_ref + 1, 0);
+    const uint64_t win = 1ull << s.min_shift;
     for (int32_t r = 0; r < s.n_ref; ++r) {
-        const int64_t len = std::max<int64_t>(0, std::min<int64_t>(s.ref_len[(size_t)r], 1ll << 29));
-        s.lin_off[(size_t)r + 1] = s.lin_off[(size_t)r] + std::min<uint64_t>((uint64_t)((len + 16383) / 16384) + s.slack, 32768);
+        const uint64_t len = (uint64_t)std::max<int64_t>(0, std::min<int64_t>(s.ref_len[(size_t)r], s.max_end));
+        s.lin_off[(size_t)r + 1] = s.lin_off[(size_t)r] + std::min<uint64_t>((len + win - 1) / win + s.slack, idx_max_windows(s));
     }
 }
 
 }  // namespace
 
-int gd_index_begin(gd_ctx* c, int32_t n_ref, const int64_t* ref_len, uint64_t first_voffset, uint64_t file_size)
+// gd_index_begin and gd_index_begin_csi: the state, the window array, the counters
+static int idx_begin(gd_ctx* c, int32_t n_ref, const int64_t* ref_len, uint64_t first_voffset, uint64_t file_size, bool csi,
+                     int32_t min_shift, int32_t depth)
 {
     if (!c || n_ref < 0 || (n_ref && !ref_len)) return GD_E_INVALID;
     if (int r = set_device(c)) return r;
@@ -55,6 +65,10 @@ int gd_index_begin(gd_ctx* c, int32_t n_ref, const int64_t* ref_len, uint64_t fi
     s.next_voff = first_voffset;
     s.file_size = file_size;
     s.ref_len.assign(ref_len, ref_len + n_ref);
+    s.csi = csi;
+    s.min_shift = (uint32_t)min_shift;
+    s.depth = (uint32_t)depth;
+    s.max_end = std::min<int64_t>(1ll << (min_shift + 3 * depth), 0x7fffffffll);
     std::vector<int32_t> len32((size_t)n_ref);
     for (int32_t r = 0; r < n_ref; ++r) len32[(size_t)r] = (int32_t)std::min<int64_t>(ref_len[r] < 0 ? 0 : ref_len[r], 0x7fffffff);
     idx_layout(s);
@@ -72,6 +86,20 @@ int gd_index_begin(gd_ctx* c, int32_t n_ref, const int64_t* ref_len, uint64_t fi
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (double& t : c->idx_secs) t = 0;
     return GD_OK;
+}
+
+int gd_index_begin(gd_ctx* c, int32_t n_ref, const int64_t* ref_len, uint64_t first_voffset, uint64_t file_size)
+{
+    return idx_begin(c, n_ref, ref_len, first_voffset, file_size, false, 14, 5);
+}
+
+int gd_index_begin_csi(gd_ctx* c, int32_t n_ref, const int64_t* ref_len, uint64_t first_voffset, uint64_t file_size,
+                       int32_t min_shift, int32_t depth)
+{
+    if (!c) return GD_E_INVALID;
+    if (min_shift < 8 || min_shift > 24) return fail(c, GD_E_INVALID, "min_shift %d: a .csi is made with 8 to 24", min_shift);
+    if (depth < 0 || depth > 8) return fail(c, GD_E_INVALID, "depth %d: a .csi is made with 0 to 8 levels", depth);
+    return idx_begin(c, n_ref, ref_len, first_voffset, file_size, true, min_shift, depth);
 }
 
 int gd_index_decode(gd_ctx* c, int last_range, gd_index_counts* out)
@@ -145,6 +173,7 @@ int gd_index_decode(gd_ctx* c, int last_range, gd_index_counts* out)
         wj.open_end = last_range ? 0u : 1u; wj.slots = s.d_slots.as<gd::IdxRec>(); wj.n_slots = n_slots;
         wj.n_rec = t_nrec; wj.end_off = t_endoff; wj.flags = t_flags; wj.m_out = d_mout; wj.m_coff = d_mcoff;
         wj.n_mem = (uint32_t)g->nm; wj.n_ref = s.n_ref;
+        wj.min_shift = s.min_shift; wj.depth = s.depth; wj.max_end = s.max_end;
         std::vector<size_t> which;
         for (int walk = 0;; ++walk) {
             // ---- walk what has not been walked from its present start ----------------------------------------------
@@ -261,6 +290,7 @@ int gd_index_decode(gd_ctx* c, int last_range, gd_index_counts* out)
         ij.tile_base = s.d_tile.as<uint64_t>(); ij.tile_cnt = reinterpret_cast<uint32_t*>(ij.tile_base + n_tiles);
         ij.n_tiles = (uint32_t)n_tiles; ij.n_ref = s.n_ref; ij.runs = s.d_runs.as<gd::IdxRun>(); ij.runs_cap = N;
         ij.ref_cnt = s.d_ref_cnt; ij.acc = s.d_acc; ij.lin_off = s.d_lin_off; ij.lin = s.d_lin;
+        ij.min_shift = s.min_shift;
         hipLaunchKernelGGL(gd::gd_idx_tile_kernel, dim3((unsigned)n_tiles), dim3(256), 0, c->stream, ij);
         hipLaunchKernelGGL(gd::gd_idx_tscan_kernel, dim3(1), dim3(256), 0, c->stream, ij);
         hipLaunchKernelGGL(gd::gd_idx_runs_kernel, dim3((unsigned)n_tiles), dim3(256), 0, c->stream, ij);
@@ -273,7 +303,7 @@ int gd_index_decode(gd_ctx* c, int last_range, gd_index_counts* out)
             // (what was there is copied reference by reference; this happens once or twice a file, if ever), and the linear
             // kernel runs again over this range -- its minima are the same wherever they were taken before
             const std::vector<uint64_t> old_off = s.lin_off;
-            s.slack = std::min<uint64_t>(s.slack + acc[gd::IX_ACC_OVER], 32768);
+            s.slack = std::min<uint64_t>(s.slack + acc[gd::IX_ACC_OVER], idx_max_windows(s));
             idx_layout(s);
             DevArr<unsigned long long> grown;
             const size_t n_new = (size_t)s.lin_off[(size_t)s.n_ref];
@@ -299,8 +329,12 @@ int gd_index_decode(gd_ctx* c, int last_range, gd_index_counts* out)
         const double t4 = ing_now();
         c->idx_secs[3] += t4 - t3;
         // ---- refusals: the first offender of each kind, the earliest of them named -----------------------------------------
-        static const struct { uint32_t word; int code; const char* what; } kinds[] = {
-            {gd::IX_ERR_SPAN, GD_E_INVALID, "a placed record with a negative position or an end beyond 2^29: a .bai cannot hold it"},
+        char span_what[160] = "a placed record with a negative position or an end beyond 2^29: a .bai cannot hold it";
+        if (s.csi)
+            snprintf(span_what, sizeof span_what, "a placed record with a negative position or an end beyond %lld: an index with min_shift %u "
+                     "and depth %u cannot hold it", (long long)s.max_end, s.min_shift, s.depth);
+        const struct { uint32_t word; int code; const char* what; } kinds[] = {
+            {gd::IX_ERR_SPAN, GD_E_INVALID, span_what},
             {gd::IX_ERR_PLACED, GD_E_UNSORTED, "a placed record after an unplaced one"},
             {gd::IX_ERR_RESUME, GD_E_UNSORTED, "a reference resumes after another began"},
             {gd::IX_ERR_BACK, GD_E_UNSORTED, "positions go backwards inside a reference"}};

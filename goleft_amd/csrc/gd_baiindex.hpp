@@ -10,7 +10,7 @@
 //                          of a record is the begin of the one behind it); the last run's end is the host's (the range's
 //                          resume point, or the next range's first head).  Unplaced records form runs too (reference -1):
 //                          they end the run in front of them and are dropped by the host
-//   gd_idx_linear_kernel   the linear index: per (reference, 16 kb window) the smallest begin of a record that touches it,
+//   gd_idx_linear_kernel   the linear index: per (reference, window of 2^min_shift positions: 16 kb in a .bai) the smallest begin of a record that touches it,
 //                          one 64-bit atomic minimum per window and run of lanes (in file order the lowest lane of a wave
 //                          holds the smallest begin: a lane whose predecessor covers the window leaves it to that lane).
 //                          The array lives as long as the run: a window that continues across ranges comes out as one.
@@ -30,7 +30,7 @@ enum : uint32_t {
     IX_ERR_BACK,               // ... lies in front of its predecessor on the same reference
     IX_ERR_RESUME,             // ... belongs to a lower reference than its predecessor
     IX_ERR_PLACED,             // ... is placed and follows an unplaced one
-    IX_ERR_SPAN,               // ... has POS < 0 or an end beyond 2^29
+    IX_ERR_SPAN,               // ... has POS < 0 or an end beyond the geometry's limit (2^29 for a .bai)
     IX_ACC_WORDS
 };
 
@@ -51,6 +51,7 @@ struct IdxJob {
     unsigned long long* acc;       // [IX_ACC_WORDS]
     const uint64_t* lin_off;       // [n_ref + 1]
     unsigned long long* lin;       // [lin_off[n_ref]] all ones: unset
+    uint32_t min_shift = 14;       // a window of the linear array spans 2^min_shift positions (14: a .bai's 16 kb)
 };
 
 __global__ __launch_bounds__(256) void gd_idx_compact_kernel(const IdxRec* slots, const uint64_t* slot_base, const uint64_t* rec_base,
@@ -178,8 +179,8 @@ __global__ __launch_bounds__(256) void gd_idx_linear_kernel(IdxJob j)
             vbeg = c.vbeg;
             base = j.lin_off[ref];
             const uint64_t nwin = j.lin_off[ref + 1] - base;
-            w0 = (uint32_t)c.beg >> 14;
-            w1 = ((uint32_t)c.end - 1u) >> 14;
+            w0 = (uint32_t)c.beg >> j.min_shift;
+            w1 = ((uint32_t)c.end - 1u) >> j.min_shift;
             if (w1 >= nwin) {                              // the host grows the array and runs this kernel again
                 atomicMax(j.acc + IX_ACC_OVER, (unsigned long long)(w1 - nwin + 1u));
                 if (w0 >= nwin) { w0 = 1; w1 = 0; ref = -3; }

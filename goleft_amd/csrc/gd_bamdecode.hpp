@@ -396,19 +396,25 @@ struct IdxRec {
     uint64_t vbeg;                  // virtual offset of the record's first byte
 };
 constexpr uint32_t IX_UNMAPPED = 1u << 31;   // flag 0x4
-constexpr uint32_t IX_BADSPAN = 1u << 30;    // placed, and POS < 0 or end > 2^29: a .bai cannot hold it (end is POS + 1 then)
-constexpr uint32_t IX_BIN = 0xffffu;
+constexpr uint32_t IX_BADSPAN = 1u << 30;    // placed, and POS < 0 or end beyond the geometry's limit (2^29 for a .bai): end is POS + 1 then
+constexpr uint32_t IX_BIN = 0x3fffffffu;     // every bin of a geometry the API accepts (depth <= 8) lies below bit 30
 
-__device__ __forceinline__ uint32_t bai_reg2bin(uint32_t beg, uint32_t end)
+// The bin of [beg, end) in a binning scheme whose smallest bins span 2^min_shift positions, `depth` levels below bin 0
+// (a .bai: 14 and 5): from the deepest level up, the first level at which both ends share a bin.
+__device__ __forceinline__ uint32_t idx_reg2bin(uint32_t beg, uint32_t end, uint32_t min_shift, uint32_t depth)
 {
     --end;
-    if (beg >> 14 == end >> 14) return 4681u + (beg >> 14);
-    if (beg >> 17 == end >> 17) return 585u + (beg >> 17);
-    if (beg >> 20 == end >> 20) return 73u + (beg >> 20);
-    if (beg >> 23 == end >> 23) return 9u + (beg >> 23);
-    if (beg >> 26 == end >> 26) return 1u + (beg >> 26);
+    uint32_t s = min_shift;
+    uint32_t first = (uint32_t)(((1ull << (3u * depth)) - 1ull) / 7ull);     // the first bin of level `depth`
+    for (uint32_t l = depth; l > 0u; --l) {
+        if ((uint32_t)((uint64_t)beg >> s) == (uint32_t)((uint64_t)end >> s)) return first + (uint32_t)((uint64_t)beg >> s);
+        s += 3u;
+        first = (first - 1u) >> 3;
+    }
     return 0u;
 }
+
+__device__ __forceinline__ uint32_t bai_reg2bin(uint32_t beg, uint32_t end) { return idx_reg2bin(beg, end, 14u, 5u); }   // SAMv1 5.3
 
 struct IdxWalkJob {
     const uint8_t* data;            // inflated bytes of the range
@@ -427,6 +433,8 @@ struct IdxWalkJob {
     const uint64_t* m_coff;         // [n_mem] ... and their file offsets
     uint32_t n_mem;
     int32_t  n_ref;
+    uint32_t min_shift = 14, depth = 5;   // the binning scheme (as initialised: a .bai's)
+    int64_t  max_end = 1ll << 29;   // a placed record may end here and no further: min(2^(min_shift + 3 depth), 2^31 - 1)
 };
 
 struct IndexWalk {
@@ -460,8 +468,8 @@ struct IndexWalk {
             c.end = c.beg + 1;
             if (flag & 4u) c.bin |= IX_UNMAPPED;
             if (c.ref >= 0) {
-                if (c.beg < 0 || end > (1ll << 29)) c.bin |= IX_BADSPAN;
-                else { c.end = (int32_t)end; c.bin |= bai_reg2bin((uint32_t)c.beg, (uint32_t)end); }
+                if (c.beg < 0 || end > j.max_end) c.bin |= IX_BADSPAN;
+                else { c.end = (int32_t)end; c.bin |= idx_reg2bin((uint32_t)c.beg, (uint32_t)end, j.min_shift, j.depth); }
             }
             // the member that holds byte o: the last one that begins at or before it (of several: the one with bytes)
             uint32_t lo = 0, hi = j.n_mem;                   // m_out[lo] <= o < m_out[hi]

@@ -1,5 +1,6 @@
 // bam_reader.cpp -- see bam_reader.hpp.
 #include "bam_reader.hpp"
+#include "csi_reader.hpp"
 
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -453,19 +454,66 @@ bool load_bai(const std::string& bam_path, std::vector<uint8_t>* d)
 }
 }  // namespace
 
+namespace {
+bool has_suffix(const std::string& s, const char* suffix)
+{
+    const size_t n = strlen(suffix);
+    return s.size() > n && s.compare(s.size() - n, n, suffix) == 0;
+}
+
+// The .csi of `bam_path` (x.bam.csi, else x.csi; a path that ends in ".csi" is the index itself) -> its bytes as stored.
+bool load_csi(const std::string& bam_path, std::vector<uint8_t>* d)
+{
+    std::vector<std::string> names;
+    if (has_suffix(bam_path, ".csi")) names.push_back(bam_path);
+    else {
+        names.push_back(bam_path + ".csi");
+        if (has_suffix(bam_path, ".bam")) names.push_back(bam_path.substr(0, bam_path.size() - 4) + ".csi");
+    }
+    for (const std::string& name : names) {
+        FILE* fi = fopen(name.c_str(), "rb");
+        if (!fi) continue;
+        d->clear();
+        uint8_t tmp[65536];
+        size_t g;
+        while ((g = fread(tmp, 1, sizeof tmp, fi)) > 0) d->insert(d->end(), tmp, tmp + g);
+        fclose(fi);
+        return true;
+    }
+    return false;
+}
+}  // namespace
+
+// x.bam.bai, then x.bai, then x.bam.csi, then x.csi: a .bai that is found wins.  A caller that wants the interval arrays as
+// stored (raw) gets no .csi: it holds none.
 bool BamReader::linear_index(const std::string& bam_path, std::vector<std::vector<uint64_t>>* per_ref, std::string* err,
                              std::vector<char>* has_chunks, std::vector<uint64_t>* chunk_end, std::vector<int64_t>* n_mapped,
                              std::vector<std::vector<uint64_t>>* raw, std::vector<int64_t>* n_unmapped)
 {
     std::vector<uint8_t> d;
-    if (!load_bai(bam_path, &d)) return false;
-    return linear_index_bytes(d, per_ref, err, has_chunks, chunk_end, n_mapped, raw, n_unmapped);
+    if (!has_suffix(bam_path, ".csi") && load_bai(bam_path, &d)) return linear_index_bytes(d, per_ref, err, has_chunks, chunk_end, n_mapped, raw, n_unmapped);
+    d.clear();
+    if (!load_csi(bam_path, &d)) return false;
+    if (raw) { if (err) *err = kCsiHasNoTiles; return false; }
+    return linear_index_bytes(d, per_ref, err, has_chunks, chunk_end, n_mapped, nullptr, n_unmapped);
 }
 
 bool BamReader::linear_index_bytes(const std::vector<uint8_t>& d, std::vector<std::vector<uint64_t>>* per_ref, std::string* err,
                                    std::vector<char>* has_chunks, std::vector<uint64_t>* chunk_end, std::vector<int64_t>* n_mapped,
                                    std::vector<std::vector<uint64_t>>* raw, std::vector<int64_t>* n_unmapped)
 {
+    if (d.size() >= 4 && memcmp(d.data(), "BAI\1", 4) != 0 && (memcmp(d.data(), "CSI\1", 4) == 0 || (d[0] == 0x1f && d[1] == 0x8b))) {
+        // a .csi, as stored or its payload: the anchors stand where the linear index's entries do (csi_reader.hpp)
+        if (raw) { if (err) *err = kCsiHasNoTiles; return false; }
+        CsiIndex x;
+        if (!read_csi_bytes(d.data(), d.size(), &x, err)) return false;
+        *per_ref = std::move(x.anchors);
+        if (has_chunks) *has_chunks = std::move(x.has_chunks);
+        if (chunk_end) *chunk_end = std::move(x.chunk_end);
+        if (n_mapped) *n_mapped = std::move(x.n_mapped);
+        if (n_unmapped) *n_unmapped = std::move(x.n_unmapped);
+        return true;
+    }
     if (d.size() < 8 || memcmp(d.data(), "BAI\1", 4) != 0) { if (err) *err = "not a BAI"; return false; }
     const int32_t n_ref = (int32_t)rd32(d.data() + 4);
     if (n_ref < 0 || (size_t)n_ref > (d.size() - 8) / 8) {     // every reference takes at least n_bin + n_intv

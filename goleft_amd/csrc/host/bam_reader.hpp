@@ -95,6 +95,9 @@ struct RecordBlock {
     size_t size() const { return pos.size(); }
 };
 
+// What BamReader::linear_index says to a caller that wants a linear index's 16 kb tiles and finds a .csi.
+constexpr const char* kCsiHasNoTiles = "a .csi holds no 16 kb tiles (a .bai or a .crai is needed)";
+
 class BamReader {
 public:
     BamReader();
@@ -122,11 +125,15 @@ public:
     // (bin 37450, SAMv1 5.2), -1 when r has none; n_unmapped[r] = its unmapped-read count (0 when r has none).
     // raw[r] = the interval array AS STORED, zeros and repeats included (indexcov's tile sizes are the differences of
     // consecutive entries: a repeated offset is a tile without reads).  A bam_path that ends in ".bai" is the index itself.
+    // Without a .bai (x.bam.bai, else x.bai) a .csi serves (x.bam.csi, else x.csi; a bam_path that ends in ".csi" is the
+    // index itself): per_ref[r] are then its ANCHORS (csi_reader.hpp), record starts of r like a
+    // linear index's entries, and the other outputs are what its bins say.  It holds no interval arrays: a caller that
+    // asks for `raw` gets false and kCsiHasNoTiles in *err.
     static bool linear_index(const std::string& bam_path, std::vector<std::vector<uint64_t>>* per_ref,
                              std::string* err, std::vector<char>* has_chunks = nullptr,
                              std::vector<uint64_t>* chunk_end = nullptr, std::vector<int64_t>* n_mapped = nullptr,
                              std::vector<std::vector<uint64_t>>* raw = nullptr, std::vector<int64_t>* n_unmapped = nullptr);
-    // The same from the index's bytes (an index made in memory: host/index_host.cpp).
+    // The same from the index's bytes (an index made in memory: host/index_host.cpp), a .bai's or a .csi's.
     static bool linear_index_bytes(const std::vector<uint8_t>& bai, std::vector<std::vector<uint64_t>>* per_ref,
                                    std::string* err, std::vector<char>* has_chunks = nullptr,
                                    std::vector<uint64_t>* chunk_end = nullptr, std::vector<int64_t>* n_mapped = nullptr,

@@ -458,11 +458,15 @@ static bool run_on_every_shard(Shards& S, const char* what, const std::function<
 
 struct ReadTimes { std::chrono::steady_clock::time_point indexed, mapped, read; };
 
-// Is there a file where the .bai of `bam` is looked for (x.bam.bai, x.bai)?
+// Is there a file where the index of `bam` is looked for (x.bam.bai, x.bai, x.bam.csi, x.csi)?
 static bool index_file_exists(const std::string& bam)
 {
-    if (access((bam + ".bai").c_str(), F_OK) == 0) return true;
-    return bam.size() > 4 && bam.compare(bam.size() - 4, 4, ".bam") == 0 && access((bam.substr(0, bam.size() - 4) + ".bai").c_str(), F_OK) == 0;
+    const bool is_bam = bam.size() > 4 && bam.compare(bam.size() - 4, 4, ".bam") == 0;
+    for (const char* suffix : {".bai", ".csi"}) {
+        if (access((bam + suffix).c_str(), F_OK) == 0) return true;
+        if (is_bam && access((bam.substr(0, bam.size() - 4) + suffix).c_str(), F_OK) == 0) return true;
+    }
+    return false;
 }
 
 // ---- records into HBM (replaces the samtools children) ---------------------------
@@ -494,7 +498,11 @@ static int read_records(const DArgs& args, gdh::BamReader& bam, const std::vecto
         if (!gpu_decode && gi_env && gi_env[0] == '1' && !(gd_env && gd_env[0] == '0') && !index_file_exists(args.bam)) {
             std::vector<uint8_t> bai;
             std::string ierr;
-            const int rc = gdh::build_bai(S.v[0].ctx, args.bam, &bai, &ierr);
+            // (a reference no .bai can hold -- longer than 2^29 - 256 --: the same index as a .csi)
+            int64_t longest = 0;
+            for (const auto& ct : contigs) longest = std::max<int64_t>(longest, ct.length);
+            const int rc = gdh::build_index(S.v[0].ctx, args.bam, longest + 256 > (1ll << 29) ? gdh::IndexFormat::Csi : gdh::IndexFormat::Bai,
+                                            14, &bai, &ierr);
             if (rc != GD_OK) {
                 fprintf(stderr, "goleft depth: %s: cannot index on the device: %s\n", args.bam.c_str(), ierr.c_str());
                 return 1;

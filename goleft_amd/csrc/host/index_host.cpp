@@ -1,6 +1,6 @@
 // index_host.cpp -- `goleft-depth index`: a BAM's .bai made on the device.
 //
-//   goleft-depth index [-o OUT.bai] in.bam
+//   goleft-depth index [-c|--csi] [-m|--min-shift N] [-o OUT] in.bam
 //
 // The host reads the header (bam_head.hpp, shared with covstats), feeds the file range after range (gd_ingest_begin /
 // _feed_fd; ranges are cut at BGZF member boundaries, up to three are pending, and each begins with the last member of the
@@ -9,7 +9,8 @@
 // (gd_index_begin / _decode / _result).  What is left for the host is the index arithmetic on the runs -- far fewer than
 // records --: htslib's bin compression, the chunk merge, the backward fill and the file's layout (gdh_bai_assemble, plain
 // C++: a CPU test drives it without a device).  The same bytes serve `goleft depth` on a BAM without an index
-// (GOLEFT_GPU_INDEX=1: gdh::build_bai, nothing is written).
+// (GOLEFT_GPU_INDEX=1: gdh::build_index, nothing is written).  With -c the same runs, windows and counts become a .csi
+// (DESIGN.md section 3.20): the binning scheme is a parameter of the walk and of the assembler, a .bai's is (14, 5).
 #include <unistd.h>
 #include <zlib.h>
 
@@ -29,31 +30,39 @@
 #include "bam_head.hpp"
 #include "bam_reader.hpp"
 #include "cli.hpp"
+#include "csi_reader.hpp"
 #include "gpu_ingest.hpp"
 #include "index_build.hpp"
 
 namespace {
 
-constexpr uint32_t kPseudoBin = 37450;
 constexpr uint64_t kUnset = ~0ull;
 
 struct Chunk { uint64_t beg, end; };
 
-int bin_level(uint32_t b) { return b >= 4681 ? 5 : b >= 585 ? 4 : b >= 73 ? 3 : b >= 9 ? 2 : b >= 1 ? 1 : 0; }
+// The binning scheme: bins whose smallest span 2^min_shift positions, `depth` levels below bin 0 (a .bai: 14 and 5).
+uint32_t level_first(int level) { return (uint32_t)(((1ull << (3 * level)) - 1) / 7); }
+uint32_t pseudo_bin(int depth) { return level_first(depth + 1) + 1; }             // 37450 at depth 5
+int bin_level(uint32_t b, int depth)
+{
+    int level = depth;
+    while (level > 0 && b < level_first(level)) --level;
+    return level;
+}
 
 void put32(std::vector<uint8_t>* o, uint32_t v) { for (int k = 0; k < 4; ++k) o->push_back((uint8_t)(v >> (8 * k))); }
 void put64(std::vector<uint8_t>* o, uint64_t v) { for (int k = 0; k < 8; ++k) o->push_back((uint8_t)(v >> (8 * k))); }
 
 // One reference: its runs (file order) -> its bins after htslib's compression and chunk merge, ascending.
-std::map<uint32_t, std::vector<Chunk>> reference_bins(const gd_index_run* runs, size_t n)
+std::map<uint32_t, std::vector<Chunk>> reference_bins(const gd_index_run* runs, size_t n, int depth)
 {
     std::map<uint32_t, std::vector<Chunk>> bins;
     for (size_t k = 0; k < n; ++k) bins[runs[k].bin].push_back(Chunk{runs[k].beg, runs[k].end});
-    // level 5 up to level 1: a bin that spans fewer than 65536 compressed bytes moves into its parent -- if that exists
-    for (int level = 5; level >= 1; --level) {
+    // the deepest level up to level 1: a bin that spans fewer than 65536 compressed bytes moves into its parent -- if that exists
+    for (int level = depth; level >= 1; --level) {
         std::vector<uint32_t> at;
         for (const auto& b : bins)
-            if (bin_level(b.first) == level) at.push_back(b.first);
+            if (bin_level(b.first, depth) == level) at.push_back(b.first);
         for (uint32_t b : at) {
             std::vector<Chunk>& ch = bins[b];
             const uint32_t parent = (b - 1) >> 3;
@@ -77,51 +86,116 @@ std::map<uint32_t, std::vector<Chunk>> reference_bins(const gd_index_run* runs, 
     return bins;
 }
 
-}  // namespace
-
-extern "C" int64_t gdh_bai_assemble(int32_t n_ref, const gd_index_run* runs, size_t n_runs, const uint64_t* lin_off,
-                                    const uint64_t* linear, const gd_index_ref* refs, uint64_t n_no_coor, uint8_t* out, size_t cap)
+// Both layouts from one walk over the references: the bins (compressed and merged, ascending, the pseudo-bin last) and the
+// linear array as far as its last touched window, an untouched window taking the value of the one behind it.  A .bai
+// stores that array; a .csi stores, per real bin, the entry of the bin's first window (0 when that window lies behind the
+// last touched one; the pseudo-bin: 0) and no array.
+int64_t assemble(bool csi, int min_shift, int depth, int32_t n_ref, const gd_index_run* runs, size_t n_runs, const uint64_t* lin_off,
+                 const uint64_t* linear, const gd_index_ref* refs, uint64_t n_no_coor, uint8_t* out, size_t cap)
 {
     if (n_ref < 0 || (n_runs && !runs) || (n_ref && (!lin_off || !refs))) return -1;
+    const uint32_t pseudo = pseudo_bin(depth);
     for (size_t k = 0; k < n_runs; ++k)
-        if (runs[k].ref < 0 || runs[k].ref >= n_ref || runs[k].bin >= kPseudoBin || (k && runs[k].ref < runs[k - 1].ref)) return -1;
+        if (runs[k].ref < 0 || runs[k].ref >= n_ref || runs[k].bin >= pseudo || (k && runs[k].ref < runs[k - 1].ref)) return -1;
     std::vector<uint8_t> o;
-    o.insert(o.end(), {'B', 'A', 'I', 1});
+    if (csi) {
+        o.insert(o.end(), {'C', 'S', 'I', 1});
+        put32(&o, (uint32_t)min_shift);
+        put32(&o, (uint32_t)depth);
+        put32(&o, 0);                                                            // l_aux
+    } else o.insert(o.end(), {'B', 'A', 'I', 1});
     put32(&o, (uint32_t)n_ref);
+    std::vector<uint64_t> filled;
     size_t k = 0;
     for (int32_t r = 0; r < n_ref; ++r) {
         const size_t first = k;
         while (k < n_runs && runs[k].ref == r) ++k;
-        const std::map<uint32_t, std::vector<Chunk>> bins = k > first ? reference_bins(runs + first, k - first) : std::map<uint32_t, std::vector<Chunk>>();
-        const bool has = refs[r].n_mapped + refs[r].n_unmapped > 0;
-        put32(&o, (uint32_t)bins.size() + (has ? 1u : 0u));
-        for (const auto& b : bins) {
-            put32(&o, b.first);
-            put32(&o, (uint32_t)b.second.size());
-            for (const Chunk& c : b.second) { put64(&o, c.beg); put64(&o, c.end); }
-        }
-        if (has) {
-            put32(&o, kPseudoBin);
-            put32(&o, 2);
-            put64(&o, refs[r].first_beg); put64(&o, refs[r].last_end); put64(&o, refs[r].n_mapped); put64(&o, refs[r].n_unmapped);
-        }
-        // the linear index: as far as the last touched window; an untouched window takes the value of the one behind it
+        const std::map<uint32_t, std::vector<Chunk>> bins = k > first ? reference_bins(runs + first, k - first, depth) : std::map<uint32_t, std::vector<Chunk>>();
         if (lin_off[r + 1] < lin_off[r] || (lin_off[r + 1] > lin_off[r] && !linear)) return -1;
         const uint64_t* const lin = linear + lin_off[r];
         uint64_t n_intv = lin_off[r + 1] - lin_off[r];
         while (n_intv && lin[n_intv - 1] == kUnset) --n_intv;
-        put32(&o, (uint32_t)n_intv);
-        const size_t at = o.size();
-        o.resize(at + 8 * (size_t)n_intv);
+        filled.resize((size_t)n_intv);
         uint64_t behind = 0;
         for (uint64_t w = n_intv; w-- > 0;) {
             if (lin[w] != kUnset) behind = lin[w];
-            for (int b = 0; b < 8; ++b) o[at + 8 * (size_t)w + (size_t)b] = (uint8_t)(behind >> (8 * b));
+            filled[(size_t)w] = behind;
+        }
+        const bool has = refs[r].n_mapped + refs[r].n_unmapped > 0;
+        put32(&o, (uint32_t)bins.size() + (has ? 1u : 0u));
+        for (const auto& b : bins) {
+            put32(&o, b.first);
+            if (csi) {
+                const int level = bin_level(b.first, depth);
+                const uint64_t w = (uint64_t)(b.first - level_first(level)) << (3 * (depth - level));
+                put64(&o, w < n_intv ? filled[(size_t)w] : 0);
+            }
+            put32(&o, (uint32_t)b.second.size());
+            for (const Chunk& c : b.second) { put64(&o, c.beg); put64(&o, c.end); }
+        }
+        if (has) {
+            put32(&o, pseudo);
+            if (csi) put64(&o, 0);
+            put32(&o, 2);
+            put64(&o, refs[r].first_beg); put64(&o, refs[r].last_end); put64(&o, refs[r].n_mapped); put64(&o, refs[r].n_unmapped);
+        }
+        if (!csi) {
+            put32(&o, (uint32_t)n_intv);
+            for (uint64_t w = 0; w < n_intv; ++w) put64(&o, filled[(size_t)w]);
         }
     }
     put64(&o, n_no_coor);
     if (out && cap >= o.size()) memcpy(out, o.data(), o.size());
     return (int64_t)o.size();
+}
+
+// The payload as a BGZF file: members of at most 65280 payload bytes, then the empty member that ends such a file.
+bool bgzf_write(const std::vector<uint8_t>& payload, std::vector<uint8_t>* out)
+{
+    static const uint8_t eof_member[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    out->clear();
+    std::vector<uint8_t> buf(65536);
+    for (size_t at = 0; at < payload.size();) {
+        const size_t take = std::min<size_t>(payload.size() - at, 65280);
+        z_stream z;
+        memset(&z, 0, sizeof z);
+        if (deflateInit2(&z, 6, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+        z.next_in = const_cast<Bytef*>(payload.data() + at);
+        z.avail_in = (uInt)take;
+        z.next_out = buf.data();
+        z.avail_out = (uInt)buf.size() - 26;                                     // (what the header and the trailer take)
+        const int rc = deflate(&z, Z_FINISH);
+        const size_t clen = buf.size() - 26 - z.avail_out;
+        deflateEnd(&z);
+        if (rc != Z_STREAM_END) return false;                                    // (65280 bytes never deflate to more than 65510)
+        const uint8_t head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+        out->insert(out->end(), head, head + 16);
+        const size_t bsize = clen + 25;                                          // the member's size - 1
+        out->push_back((uint8_t)bsize);
+        out->push_back((uint8_t)(bsize >> 8));
+        out->insert(out->end(), buf.data(), buf.data() + clen);
+        put32(out, (uint32_t)crc32(crc32(0L, Z_NULL, 0), payload.data() + at, (uInt)take));
+        put32(out, (uint32_t)take);
+        at += take;
+    }
+    out->insert(out->end(), eof_member, eof_member + 28);
+    return true;
+}
+
+}  // namespace
+
+extern "C" int64_t gdh_bai_assemble(int32_t n_ref, const gd_index_run* runs, size_t n_runs, const uint64_t* lin_off,
+                                    const uint64_t* linear, const gd_index_ref* refs, uint64_t n_no_coor, uint8_t* out, size_t cap)
+{
+    return assemble(false, 14, 5, n_ref, runs, n_runs, lin_off, linear, refs, n_no_coor, out, cap);
+}
+
+extern "C" int64_t gdh_csi_assemble(int32_t n_ref, const gd_index_run* runs, size_t n_runs, const uint64_t* lin_off,
+                                    const uint64_t* linear, const gd_index_ref* refs, uint64_t n_no_coor, int32_t min_shift, int32_t depth,
+                                    uint8_t* out, size_t cap)
+{
+    if (min_shift < 8 || min_shift > 24 || depth < 0 || depth > 8) return -1;
+    return assemble(true, min_shift, depth, n_ref, runs, n_runs, lin_off, linear, refs, n_no_coor, out, cap);
 }
 
 namespace {
@@ -134,8 +208,25 @@ struct Timing { double list = 0, feed = 0, decode = 0, read_back = 0, assemble =
 
 namespace gdh {
 
+int csi_depth(const std::vector<int64_t>& lengths, int min_shift)
+{
+    int64_t longest = 0;
+    for (int64_t l : lengths) longest = std::max(longest, l);
+    int depth = 0;
+    while (longest + 256 > (1ll << (min_shift + 3 * depth))) ++depth;             // (htslib adds the 256)
+    return depth;
+}
+
 int build_bai(gd_ctx* ctx, const std::string& bam, std::vector<uint8_t>* out, std::string* err, IndexStats* stats)
 {
+    return build_index(ctx, bam, IndexFormat::Bai, 14, out, err, stats);
+}
+
+int build_index(gd_ctx* ctx, const std::string& bam, IndexFormat format, int min_shift, std::vector<uint8_t>* out, std::string* err,
+                IndexStats* stats)
+{
+    const bool csi = format == IndexFormat::Csi;
+    if (csi && (min_shift < 8 || min_shift > 24)) { *err = "min_shift " + std::to_string(min_shift) + ": a .csi is made with 8 to 24"; return GD_E_INVALID; }
     Timing tm;
     const double t_enter = now_s();
     BamHead head;
@@ -153,7 +244,9 @@ int build_bai(gd_ctx* ctx, const std::string& bam, std::vector<uint8_t>* out, st
     bool have_first = false;
     if (!first_record_voffset(fm.fd, fm.size, head.length, &first_voff, &have_first)) { *err = bam + ": not a BGZF file"; return GD_E_INVALID; }
     tm.list += now_s() - t0;
-    int rc = gd_index_begin(ctx, (int32_t)lengths.size(), lengths.data(), first_voff, fm.size);
+    const int depth = csi ? csi_depth(lengths, min_shift) : 5;
+    int rc = csi ? gd_index_begin_csi(ctx, (int32_t)lengths.size(), lengths.data(), first_voff, fm.size, min_shift, depth)
+                 : gd_index_begin(ctx, (int32_t)lengths.size(), lengths.data(), first_voff, fm.size);
     if (rc != GD_OK) return lib_fail(rc);
     gd_index_counts cnt{};
     if (have_first) {
@@ -231,10 +324,16 @@ int build_bai(gd_ctx* ctx, const std::string& bam, std::vector<uint8_t>* out, st
     rc = gd_index_windows(ctx, lin_off.data(), lin_off.size());
     if (rc != GD_OK) return lib_fail(rc);
     if (lin_off.back() != n_lin) { *err = "the device's linear index has another size than expected (internal error)"; return GD_E_INVALID; }
-    const int64_t need = gdh_bai_assemble((int32_t)lengths.size(), runs.data(), n_runs, lin_off.data(), linear.data(), refs.data(), n_no_coor, nullptr, 0);
+    const int64_t need = assemble(csi, min_shift, depth, (int32_t)lengths.size(), runs.data(), n_runs, lin_off.data(), linear.data(), refs.data(), n_no_coor, nullptr, 0);
     if (need < 0) { *err = "cannot assemble the index (internal error)"; return GD_E_INVALID; }
     out->resize((size_t)need);
-    (void)gdh_bai_assemble((int32_t)lengths.size(), runs.data(), n_runs, lin_off.data(), linear.data(), refs.data(), n_no_coor, out->data(), out->size());
+    (void)assemble(csi, min_shift, depth, (int32_t)lengths.size(), runs.data(), n_runs, lin_off.data(), linear.data(), refs.data(), n_no_coor, out->data(), out->size());
+    if (csi) {                                                                   // a .csi is BGZF; a .bai is stored as it is
+        std::vector<uint8_t> file;
+        if (!bgzf_write(*out, &file)) { *err = "cannot compress the index (internal error)"; return GD_E_INVALID; }
+        out->swap(file);
+    }
+    if (stats) { stats->min_shift = csi ? min_shift : 14; stats->depth = depth; }
     tm.assemble = now_s() - t0;
     if (stats) { stats->records = cnt.records; stats->rounds = tm.rounds; stats->ranges = tm.ranges; }
     if (getenv("GOLEFT_INDEX_TIMING")) {
@@ -254,7 +353,12 @@ int build_bai(gd_ctx* ctx, const std::string& bam, std::vector<uint8_t>* out, st
 
 namespace {
 
-void usage(FILE* f) { fputs("usage: index [-o OUT.bai] in.bam\n", f); }
+void usage(FILE* f)
+{
+    fputs("usage: index [-c|--csi] [-m|--min-shift N] [-o OUT] in.bam\n"
+          "  -c  write a .csi (in.bam.csi) instead of a .bai: for references longer than 2^29 - 256\n"
+          "  -m  the bits of the smallest bin's span, 8 to 24 (default 14); implies -c\n", f);
+}
 
 int env_int(const char* name, int dflt)
 {
@@ -265,6 +369,11 @@ int env_int(const char* name, int dflt)
 }  // namespace
 
 extern "C" int gdh_index_build(const char* bam, uint8_t** out, size_t* n_out, int64_t* stats, char* errbuf, size_t errcap)
+{
+    return gdh_index_build_csi(bam, 0, 14, out, n_out, stats, errbuf, errcap);
+}
+
+extern "C" int gdh_index_build_csi(const char* bam, int csi, int min_shift, uint8_t** out, size_t* n_out, int64_t* stats, char* errbuf, size_t errcap)
 {
     if (!bam || !out || !n_out) return GD_E_INVALID;
     *out = nullptr;
@@ -279,11 +388,12 @@ extern "C" int gdh_index_build(const char* bam, uint8_t** out, size_t* n_out, in
         if (getenv("GOLEFT_INDEX_SLICE")) (void)gd_set_option(ctx, GD_OPT_INDEX_SLICE, env_int("GOLEFT_INDEX_SLICE", 65536));
         if (getenv("GOLEFT_INDEX_GUESS_CHECKS")) (void)gd_set_option(ctx, GD_OPT_INDEX_GUESS_CHECKS, env_int("GOLEFT_INDEX_GUESS_CHECKS", 3));
         if (getenv("GOLEFT_INDEX_REPAIR_ROUNDS")) (void)gd_set_option(ctx, GD_OPT_INDEX_REPAIR_ROUNDS, env_int("GOLEFT_INDEX_REPAIR_ROUNDS", 4));
-        rc = gdh::build_bai(ctx, bam, &bytes, &err, &st);
+        rc = gdh::build_index(ctx, bam, csi ? gdh::IndexFormat::Csi : gdh::IndexFormat::Bai, min_shift, &bytes, &err, &st);
     }
     if (errbuf && errcap) snprintf(errbuf, errcap, "%s", err.c_str());
     if (rc != GD_OK) return rc;
     if (stats) { stats[0] = st.records; stats[1] = st.rounds; stats[2] = st.ranges; }
+    if (stats && csi) { stats[3] = st.min_shift; stats[4] = st.depth; }
     *out = static_cast<uint8_t*>(malloc(bytes.size() ? bytes.size() : 1));
     if (!*out) return GD_E_NOMEM;
     memcpy(*out, bytes.data(), bytes.size());
@@ -293,10 +403,33 @@ extern "C" int gdh_index_build(const char* bam, uint8_t** out, size_t* n_out, in
 
 extern "C" void gdh_index_free(uint8_t* p) { free(p); }
 
+extern "C" int gdh_csi_read(const uint8_t* bytes, size_t n, int32_t ref, int64_t* info, uint64_t* anchors, size_t cap, size_t* n_anchors,
+                            char* errbuf, size_t errcap)
+{
+    gdh::CsiIndex x;
+    std::string err;
+    if (!bytes || !info) err = "no input";
+    else if (gdh::read_csi_bytes(bytes, n, &x, &err) && ref >= (int32_t)x.anchors.size()) err = "no such reference";
+    if (errbuf && errcap) snprintf(errbuf, errcap, "%s", err.c_str());
+    if (!err.empty()) return GD_E_INVALID;
+    info[0] = x.min_shift; info[1] = x.depth; info[2] = (int64_t)x.anchors.size(); info[3] = x.has_no_coor ? 1 : 0; info[4] = (int64_t)x.n_no_coor;
+    if (n_anchors) *n_anchors = 0;
+    if (ref < 0) return GD_OK;
+    const std::vector<uint64_t>& v = x.anchors[(size_t)ref];
+    info[5] = x.has_chunks[(size_t)ref]; info[6] = (int64_t)x.chunk_end[(size_t)ref];
+    info[7] = x.n_mapped[(size_t)ref]; info[8] = x.n_unmapped[(size_t)ref];
+    if (n_anchors) *n_anchors = v.size();
+    if (anchors && cap < v.size()) return GD_E_CAPACITY;
+    if (anchors && !v.empty()) memcpy(anchors, v.data(), v.size() * sizeof(uint64_t));
+    return GD_OK;
+}
+
 extern "C" int gdh_index_run(int argc, const char* const* argv)
 {
     using gdh::cli::Args;
     std::string out_path, bam;
+    bool csi = false;
+    int min_shift = 14;
     Args c(argc, argv, usage);
     for (;;) {
         const Args::Kind kind = c.next();
@@ -307,17 +440,27 @@ extern "C" int gdh_index_run(int argc, const char* const* argv)
             bam = c.arg;
             continue;
         }
+        if (c.key == "-c" || c.key == "--csi") { csi = true; continue; }
+        if (c.key == "-m" || c.key == "--min-shift") {
+            if (!c.value()) return 255;
+            char* end = nullptr;
+            const long v = strtol(c.val.c_str(), &end, 10);
+            if (c.val.empty() || *end || v < 8 || v > 24) { (void)c.fail("-m %s: min_shift is 8 to 24", c.val.c_str()); return 255; }
+            min_shift = (int)v;
+            csi = true;
+            continue;
+        }
         if (c.key != "-o" && c.key != "--output") { (void)c.fail("unknown argument %s", c.arg.c_str()); return 255; }
         if (!c.value()) return 255;
         out_path = c.val;
     }
     if (bam.empty()) { (void)c.fail("a BAM is required"); return 255; }
-    if (out_path.empty()) out_path = bam + ".bai";
+    if (out_path.empty()) out_path = bam + (csi ? ".csi" : ".bai");
     uint8_t* bytes = nullptr;
     size_t n = 0;
-    int64_t stats[3] = {0, 0, 0};
+    int64_t stats[5] = {0, 0, 0, 0, 0};
     char err[1024] = "";
-    const int rc = gdh_index_build(bam.c_str(), &bytes, &n, stats, err, sizeof err);
+    const int rc = gdh_index_build_csi(bam.c_str(), csi ? 1 : 0, min_shift, &bytes, &n, stats, err, sizeof err);
     if (rc != GD_OK) {
         fprintf(stderr, "index: %s: %s\n", bam.c_str(), err[0] ? err : gd_strerror(rc));
         return rc == GD_E_UNSORTED ? 2 : 1;

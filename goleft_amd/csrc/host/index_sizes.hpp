@@ -85,7 +85,8 @@ inline bool read_index_sizes(const std::string& b, IndexSizes* s, std::string* w
     std::vector<int64_t> nm, nu;
     std::string err;
     if (!BamReader::linear_index(b, &lin, &err, nullptr, nullptr, &nm, &s->raw, &nu)) {
-        *why = "no usable index for " + b + (err.empty() ? "" : ": " + err);
+        if (err == kCsiHasNoTiles) *why = b + ": " + err;
+        else *why = "no usable index for " + b + (err.empty() ? "" : ": " + err);
         return false;
     }
     for (size_t r = 0; r < nm.size(); ++r)

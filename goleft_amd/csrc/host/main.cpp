@@ -10,7 +10,7 @@
 //   goleft-depth scales [--level L] matrix.bed[.gz]                         (the factors emdepth --scales takes: dcnv's sample medians carried to one level)
 //   goleft-depth debias (--gc-values FILE | --fasta ref.fa) [--window W] matrix.bed[.gz]   (dcnv's ChunkDebiaser: the matrix freed of GC bias; emdepth takes the same as --gc-values | --gc-fasta, --gc-window)
 //   goleft-depth cnveval [-m MINOVERLAP] [-s] truth.bed[.gz] test.bed[.gz]   (the reference's cnveval command: precision and recall of a call set, per size class)
-//   goleft-depth index [-o OUT.bai] a.bam                                   (a .bai as htslib writes it, made on the device: no samtools needed)
+//   goleft-depth index [-c] [-m N] [-o OUT] a.bam                            (a .bai as htslib writes it, or a .csi, made on the device: no samtools needed)
 //   goleft-depth samplename [-e] a.bam                                     (goleft samplename: the @RG SM values)
 //   samtools depth -Q q -d D -r REGION in.bam                   (the same program installed under the NAME samtools,
 //                                                                goleft_amd/shim/samtools: an unmodified goleft finds it on PATH)

@@ -1,4 +1,5 @@
-"""`goleft-depth index`: a BAM's .bai as htslib's indexer writes it, made on the device."""
+"""`goleft-depth index`: a BAM's .bai as htslib's indexer writes it, or its .csi (csi=True: for references beyond 2^29),
+made on the device (DESIGN.md sections 3.19 and 3.20)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -18,30 +19,38 @@ class Refused(Exception):
         self.status = status
 
 
-def build_stats(path: str):
-    """(the .bai's bytes, {"records", "rounds", "ranges"}) of the BAM at `path`; rounds: walks that repaired a wrong guess."""
+def build_stats(path: str, csi: bool = False, min_shift: int = 14):
+    """(the .bai's bytes, {"records", "rounds", "ranges"}) of the BAM at `path`; rounds: walks that repaired a wrong guess.
+    csi: the .csi's bytes (BGZF) with bins of 2^min_shift positions at the deepest level (8 to 24), and "min_shift" and
+    "depth" among the stats."""
     lib = _hostlib.load()
     out, n = C.c_void_p(), C.c_size_t()
-    stats = (C.c_int64 * 3)()
+    stats = (C.c_int64 * 5)()
     err = C.create_string_buffer(1024)
-    rc = lib.gdh_index_build(os.fsencode(path), C.byref(out), C.byref(n), stats, err, len(err))
+    if csi:
+        rc = lib.gdh_index_build_csi(os.fsencode(path), 1, min_shift, C.byref(out), C.byref(n), stats, err, len(err))
+    else:
+        rc = lib.gdh_index_build(os.fsencode(path), C.byref(out), C.byref(n), stats, err, len(err))
     if rc != 0:
         raise Refused(rc, err.value.decode("utf-8", "replace"))
     try:
-        return C.string_at(out, n.value), {"records": stats[0], "rounds": stats[1], "ranges": stats[2]}
+        st = {"records": stats[0], "rounds": stats[1], "ranges": stats[2]}
+        if csi:
+            st.update(min_shift=stats[3], depth=stats[4])
+        return C.string_at(out, n.value), st
     finally:
         lib.gdh_index_free(out)
 
 
-def build(path: str) -> bytes:
-    """The .bai of the BAM at `path`."""
-    return build_stats(path)[0]
+def build(path: str, csi: bool = False, min_shift: int = 14) -> bytes:
+    """The .bai of the BAM at `path`, or (csi) its .csi."""
+    return build_stats(path, csi, min_shift)[0]
 
 
-def write(path: str, out: str | None = None) -> str:
-    """Writes the index to `out` (default: path + ".bai") through a temporary file and a rename; returns where it is."""
-    out = out or path + ".bai"
-    data = build(path)
+def write(path: str, out: str | None = None, csi: bool = False, min_shift: int = 14) -> str:
+    """Writes the index to `out` (default: path + ".bai", or ".csi") through a temporary file and a rename; returns where it is."""
+    out = out or path + (".csi" if csi else ".bai")
+    data = build(path, csi, min_shift)
     tmp = "%s.tmp.%d" % (out, os.getpid())
     try:
         with open(tmp, "wb") as fh:

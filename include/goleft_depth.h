@@ -623,6 +623,13 @@ typedef struct gd_index_counts {
 typedef struct gd_index_run { int32_t ref; uint32_t bin; uint64_t beg, end; } gd_index_run;
 typedef struct gd_index_ref { uint64_t first_beg, last_end, n_mapped, n_unmapped; } gd_index_ref;   /* no records: all 0 */
 int gd_index_begin(gd_ctx* ctx, int32_t n_ref, const int64_t* ref_len, uint64_t first_voffset, uint64_t file_size);
+/* The same run for a .csi (CSI version 1): bins whose smallest span 2^min_shift positions (8 to
+ * 24), `depth` levels below bin 0 (0 to 8), so positions up to min(2^(min_shift + 3 depth), 2^31 - 1); the linear array has
+ * a window per 2^min_shift positions (gdh_csi_assemble takes the bins' loffset from it: a .csi stores no linear index).
+ * gd_index_begin is this with 14 and 5 -- a .bai's scheme -- and a .bai's wording when a record lies beyond 2^29.
+ * gd_index_decode, _result and _windows serve both.  GD_E_INVALID: min_shift or depth outside those ranges. */
+int gd_index_begin_csi(gd_ctx* ctx, int32_t n_ref, const int64_t* ref_len, uint64_t first_voffset, uint64_t file_size,
+                       int32_t min_shift, int32_t depth);
 int gd_index_decode(gd_ctx* ctx, int last_range, gd_index_counts* out);
 int gd_index_windows(gd_ctx* ctx, uint64_t* lin_off, size_t cap);   /* cap >= n_ref + 1 */
 int gd_index_result(gd_ctx* ctx, gd_index_run* runs, size_t cap_runs, size_t* n_runs, uint64_t* linear, size_t cap_linear,

@@ -281,6 +281,9 @@ int gdh_index_run(int argc, const char* const* argv);
 /* The same index in memory: *out (gdh_index_free) and *n_out; stats (NULL, or room for three): records, repair rounds,
  * ranges.  Returns a gd_* status, its message in errbuf. */
 int gdh_index_build(const char* bam, uint8_t** out, size_t* n_out, int64_t* stats, char* errbuf, size_t errcap);
+/* ... as a .csi when csi is not 0 (min_shift 8 to 24, else GD_E_INVALID; the depth follows from the longest reference):
+ * the file's bytes, BGZF, and stats has room for FIVE -- the three above, min_shift, depth.  csi 0 is gdh_index_build. */
+int gdh_index_build_csi(const char* bam, int csi, int min_shift, uint8_t** out, size_t* n_out, int64_t* stats, char* errbuf, size_t errcap);
 void gdh_index_free(uint8_t* p);
 /* The index arithmetic alone (no device): the runs of consecutive records of one (reference, bin) in file order -- grouped
  * by ascending reference --, the linear index before its backward fill (reference r's windows at lin_off[r] ..
@@ -291,6 +294,19 @@ void gdh_index_free(uint8_t* p);
  * to out when cap holds it), -1 for arguments that are no such input. */
 int64_t gdh_bai_assemble(int32_t n_ref, const gd_index_run* runs, size_t n_runs, const uint64_t* lin_off, const uint64_t* linear,
                          const gd_index_ref* refs, uint64_t n_no_coor, uint8_t* out, size_t cap);
+/* The same arithmetic for a .csi (CSI version 1) with bins whose smallest span 2^min_shift positions (8 to 24) and `depth`
+ * levels (0 to 8): the linear array has a window per 2^min_shift positions and is not stored -- every real bin carries the
+ * filled array's entry of its first window as loffset (0 when that window lies behind the last touched one), the pseudo-bin
+ * 0.  The compression runs from level `depth` up.  -> the UNCOMPRESSED payload; the file is that as BGZF. */
+int64_t gdh_csi_assemble(int32_t n_ref, const gd_index_run* runs, size_t n_runs, const uint64_t* lin_off, const uint64_t* linear,
+                         const gd_index_ref* refs, uint64_t n_no_coor, int32_t min_shift, int32_t depth, uint8_t* out, size_t cap);
+/* What the device BAM read takes from a .csi (host/csi_reader.hpp; exported for tests): bytes are the file's (BGZF) or its
+ * payload.  info[0 .. 4]: min_shift, depth, n_ref, whether n_no_coor is there, n_no_coor; with ref >= 0 also info[5 .. 8]:
+ * whether a real bin of the reference holds a chunk, its largest chunk end, the pseudo-bin's n_mapped (-1: none) and
+ * n_unmapped, and the reference's anchors (anchors: NULL or room for cap; *n_anchors: how many).  GD_E_INVALID with the
+ * reason in errbuf: not a .csi, or a count or offset its bytes do not hold. */
+int gdh_csi_read(const uint8_t* bytes, size_t n, int32_t ref, int64_t* info, uint64_t* anchors, size_t cap, size_t* n_anchors,
+                 char* errbuf, size_t errcap);
 
 /* ---- BAM decode (replaces the read side of the samtools child) ---------- */
 /* How `goleft-depth` cuts a BAM into device passes (host/gpu_ingest.hpp; exported for tests):
