@@ -171,6 +171,8 @@ SYMBOLS = {
     "gd_svd_debias_scaled_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_double, C.c_int, _P, _P, _P, _P]),
     "gd_cnveval": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, C.c_double, _P]),
     "gd_cnveval_timing": (C.c_int, [_P, _P, C.c_size_t]),
+    "gd_perbase_runs": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gd_perbase_runs_timing": (C.c_int, [_P, _P, C.c_size_t]),
     "gd_device_scale": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P]),
     "gd_sample_medians_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P]),
     "gd_emdepth_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P, _P, _P]),

@@ -269,6 +269,10 @@ struct gd_ctx {
     int64_t md_segment = 0;                                    // GD_OPT_MOVDEBIAS_SEGMENT: sorted rows a workgroup owns (0: by the window)
     double sv_secs[5] = {0, 0, 0, 0, 0};                       // gd_svd_debias*: upload, statistics + Gram, eigenpairs (host), projection, read-back of the last call (gd_api_svddebias.inc)
     double ce_secs[4] = {0, 0, 0, 0};                          // gd_cnveval: preparation + upload, kernels, read-back of the last call, and the first kernel's part of the second (gd_api_cnveval.inc)
+    DevArr<uint32_t> d_pb_cnt, d_pb_base;                      // gd_perbase_runs: run starts per chunk and their exclusive scan (grow-only; gd_api_perbase.inc)
+    DevArr<uint32_t> d_pb_start;                               // ... the runs of the last call: d_pb_start and d_pb_value grow together, d_pb_value last:
+    DevArr<int32_t> d_pb_value;                                // its capacity is PbJob::cap
+    double pb_secs[4] = {0, 0, 0, 0};                          // gd_perbase_runs: count, scan, emit, read-back of the last call
     double em_secs[3] = {0, 0, 0};                             // gd_emdepth*: upload, kernel, read-back of the last call (gd_api_emdepth.inc)
     PinArr<uint8_t> h_walk;                                    // gd_ingest_decode, gd_covstats_decode: per-segment tables of the record walk (page-locked host memory
                                                                // the walk kernels read and write over the link: no copy command)

@@ -226,6 +226,30 @@ class DepthEngine:
         """[n,3] int32 rows (start, end, class)."""
         return self._runs(self._lib.gd_callable, tid)
 
+    def perbase_runs(self, tid: int, start: int = 0, end: Optional[int] = None, cuts=None):
+        """gd_perbase_runs: the per-base vector of [start, end) as runs of equal depth -- with cuts, of equal depth bin
+        (the number of cuts <= the depth).  Returns (starts uint32, values int32); run k ends at starts[k + 1], the
+        last one at end.  The counting call, then the fetching call."""
+        if end is None:
+            end = self.contig_lengths[tid]
+        c = np.ascontiguousarray(cuts if cuts is not None else [], np.int32)
+        cp = c.ctypes.data if c.size else None
+        n = C.c_size_t()
+        rc = self._lib.gd_perbase_runs(self._ctx, tid, start, end, c.size, cp, None, None, 0, C.byref(n))
+        if rc not in (0, -8):
+            self._chk(rc)
+        starts, values = np.empty(n.value, np.uint32), np.empty(n.value, np.int32)
+        if n.value:
+            self._chk(self._lib.gd_perbase_runs(self._ctx, tid, start, end, c.size, cp, starts.ctypes.data, values.ctypes.data,
+                                                n.value, C.byref(n)))
+        return starts, values
+
+    def perbase_runs_timing(self):
+        """Seconds of the last perbase_runs call: dict(count_s, scan_s, emit_s, readback_s) (gd_perbase_runs_timing)."""
+        t = (C.c_double * 4)()
+        self._chk(self._lib.gd_perbase_runs_timing(self._ctx, t, 4))
+        return {"count_s": t[0], "scan_s": t[1], "emit_s": t[2], "readback_s": t[3]}
+
     def region_windows(self, tid: int, start: int, end: int):
         n = C.c_size_t()
         W = self.params.window_size

@@ -39,7 +39,7 @@ extern "C" {
 
 /* GD_ABI_VERSION changes when an existing entry point or structure changes; GD_ABI_REVISION counts the releases that only
  * ADDED entry points since then (revision 1: gd_indexcov_*; 2: gd_indexsplit_*; 3: gd_crai_sizes).  A caller built against (15, r) runs on any (15, r' >= r).
- * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, gd_sample_medians*, gd_chunk_debias*, gd_device_scale, the *_device entries, gd_moving_debias*, gd_svd_debias* and gd_svd_debias_scaled*, were added without a revision; look them up by symbol.  So were gd_cnveval and gd_cnveval_timing.
+ * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, gd_sample_medians*, gd_chunk_debias*, gd_device_scale, the *_device entries, gd_moving_debias*, gd_svd_debias* and gd_svd_debias_scaled*, were added without a revision; look them up by symbol.  So were gd_cnveval and gd_cnveval_timing.  So were gd_perbase_runs and gd_perbase_runs_timing.
  * Why indexcov did not become version 16: nothing that existed changed, so callers of ABI 15 need not be turned away, and
  * tests/test_host_cpu.py holds gd_abi_version() to 15 until something does change. */
 #define GD_ABI_VERSION 15
@@ -937,6 +937,30 @@ int gd_cnveval(gd_ctx* ctx, int32_t n_samples, const int64_t* cnv_off /* [n_samp
                const int64_t* t_off /* [n_truths + 1] */, const int32_t* t_samples, double min_overlap,
                int64_t* stats /* [n_samples][3][4] */);
 int gd_cnveval_timing(gd_ctx* ctx, double* out, size_t n);
+/* ---- the per-base vector of a region as runs of equal value: what bedGraph, mosdepth's
+ * per-base.bed and `bedtools genomecov -bga` hold, run-length encoded on the device so that only the runs cross the link.
+ * After a gd_compute with GD_OUT_PERBASE, for contig tid of length len, a region 0 <= start <= end <= len and the
+ * computed per-base vector d:
+ *   value     with n_cuts == 0, v(p) = d[p]; otherwise v(p) = the number of cuts <= d[p]: the index, 0 .. n_cuts, of the bin
+ *             [0, cuts[0]), [cuts[0], cuts[1]), ... [cuts[n_cuts - 1], inf) that holds the depth.  Cuts are strictly
+ *             increasing, each 1 .. 2^31 - 1, at most GD_PERBASE_MAX_CUTS of them.
+ *   run start position p starts a run iff p == start or v(p) != v(p - 1): the region's first position always does, even when
+ *             d[start] == d[start - 1]; a change of depth inside one bin starts none.
+ *   runs      run k is (run_start[k], run_value[k]), in ascending position; it ends at run_start[k + 1], the last one at
+ *             `end`.  Runs of depth 0 are runs like any other; a contig without records is one run of 0; start == end
+ *             gives no runs and GD_OK.
+ * The call pattern is gd_callable's: *n always receives the number of runs; GD_E_CAPACITY when cap is below it or an output
+ * is NULL (NULL and 0 is how a caller asks for the count), and the outputs are then untouched.  GD_E_RANGE: a region outside
+ * 0 <= start <= end <= len, a tid that is none or was not selected; GD_E_INVALID: cuts that do not increase, a cut below 1,
+ * more than GD_PERBASE_MAX_CUTS; GD_E_STATE: before a compute, while one is in flight, or when the context was computed
+ * without GD_OUT_PERBASE.  A refused call leaves the context as it was.  Two calls give the same bytes.
+ * gd_perbase_runs_timing: seconds of the last call (measurement only): the count kernel, the scan with the read of the
+ * count, the emit kernel, the read-back (the last two are 0 after a call that only counted).  Fills min(n, 4) values.
+ * Added without a revision, as the entry points before them: look them up by symbol. */
+#define GD_PERBASE_MAX_CUTS 32
+int gd_perbase_runs(gd_ctx* ctx, int32_t tid, int64_t start, int64_t end, int n_cuts, const int32_t* cuts /* [n_cuts] or NULL */,
+                    uint32_t* run_start, int32_t* run_value, size_t cap, size_t* n);
+int gd_perbase_runs_timing(gd_ctx* ctx, double* out, size_t n);
 int gd_ingest_abort(gd_ctx* ctx);
 /* Page-locked host memory for the byte range handed to gd_ingest_bgzf (read the file
  * straight into it: the H2D copy then runs at PCIe speed instead of through a bounce

@@ -270,6 +270,20 @@ int gdh_cnveval_main(int argc, const char* const* argv);
 /* Same, writing to out_path (NULL = stdout). */
 int gdh_cnveval_run(int argc, const char* const* argv, const char* out_path);
 
+/* ---- `perbase`: the per-base depth of a BAM as runs of equal depth, run-length encoded on the device (gd_perbase_runs;
+ * DESIGN.md section 3.21).  argv: [-Q Q] [-c CHROM] [-b regions.bed] [--quantize C1,C2,...] [-o OUT] in.bam.  The BAM is read
+ * exactly as `depth` reads it (device decode through .bai or .csi; GOLEFT_GPU_INDEX, GOLEFT_GPU_DECODE=0 and GOLEFT_DEVICE are
+ * honoured; flag mask 0x704, -Q default 1), on one device.  Lines `chrom \t start \t end \t value` for every wanted contig in
+ * header order, or with -b for every BED line in file order (parsed as depth parses a region, clipped to the contig, each on
+ * its own: overlapping lines repeat); value is the depth, or with --quantize the bin's label lo:hi (0:C1, C1:C2, ... Cn:inf;
+ * at most 32 cuts, increasing, from 1).  GOLEFT_PERBASE_SLICE: positions per device call (a test knob, default 2^25: the bytes
+ * do not depend on it); GOLEFT_PERBASE_TIMING=1: where the time went, on stderr.  Returns the exit code: 1, with the cause
+ * named and no device opened, for an unknown flag, a bad --quantize, a missing or .cram input, a chromosome or BED line that
+ * names a reference the header lacks, a BED line that holds no region (with its line number). ------------------------- */
+int gdh_perbase_main(int argc, const char* const* argv);
+/* Same, writing to out_path (NULL = stdout, or -o). */
+int gdh_perbase_run(int argc, const char* const* argv, const char* out_path);
+
 /* ---- `index`: a BAM's .bai (SAMv1 5.2) as htslib's indexer writes it, made on the device (gd_index_*; DESIGN.md section
  * 3.19).  argv: [-o OUT.bai] in.bam; the index goes to in.bam.bai, or to -o, through a temporary file and a rename.
  * GOLEFT_INDEX_TIMING=1 prints where the time went on stderr; GOLEFT_INDEX_RANGE_BYTES, GOLEFT_INDEX_SLICE and
