@@ -42,6 +42,8 @@ SYMBOLS = {
     "gdh_cnveval_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p]),
     "gdh_perbase_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_perbase_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p]),
+    "gdh_dist_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
+    "gdh_dist_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_index_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_index_run": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "gdh_index_build": (C.c_int, [C.c_char_p, C.POINTER(_P), C.POINTER(C.c_size_t), _P, C.c_char_p, C.c_size_t]),

@@ -173,6 +173,9 @@ SYMBOLS = {
     "gd_cnveval_timing": (C.c_int, [_P, _P, C.c_size_t]),
     "gd_perbase_runs": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "gd_perbase_runs_timing": (C.c_int, [_P, _P, C.c_size_t]),
+    "gd_depth_hist": (C.c_int, [_P, C.c_size_t, _P, _P, _P, C.c_int32, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gd_region_bins": (C.c_int, [_P, C.c_size_t, _P, _P, _P, C.c_int, _P, _P]),
+    "gd_dist_timing": (C.c_int, [_P, _P, C.c_size_t]),
     "gd_device_scale": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P]),
     "gd_sample_medians_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P]),
     "gd_emdepth_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P, _P, _P]),

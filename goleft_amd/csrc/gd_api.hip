@@ -5,7 +5,7 @@
 // the gd_api_*.inc files with the rest of the ABI, in this order: records (pinned staging ring + copy stream, records
 // host -> HBM, HBM-resident per-contig record streams), compute (route, launch sequencing, look-back), results
 // (read-back), aux, ingest, covstats, index, indexcov, indexsplit, crai, devmat, emdepth, emcnv, colselect, chunkdebias,
-// movdebias, svddebias, cnveval, perbase, comm; and behind them, where every kept state is a complete type, gd_destroy.  What the
+// movdebias, svddebias, cnveval, perbase, dist, comm; and behind them, where every kept state is a complete type, gd_destroy.  What the
 // context holds is owned by its members (gd_own.hpp, gd_api_state.hpp): gd_destroy is the order of the teardown, the
 // context's destructor the inventory.
 // Replaces gargs' process.Runner + the samtools child + the callback's parse loop of `goleft depth`
@@ -386,6 +386,7 @@ int gd_kernel_ms(gd_ctx* c, int id, float* ms)
 #include "gd_api_svddebias.inc"
 #include "gd_api_cnveval.inc"
 #include "gd_api_perbase.inc"
+#include "gd_api_dist.inc"
 #include "gd_api_comm.inc"
 
 void gd_destroy(gd_ctx* c)

@@ -273,6 +273,8 @@ struct gd_ctx {
     DevArr<uint32_t> d_pb_start;                               // ... the runs of the last call: d_pb_start and d_pb_value grow together, d_pb_value last:
     DevArr<int32_t> d_pb_value;                                // its capacity is PbJob::cap
     double pb_secs[4] = {0, 0, 0, 0};                          // gd_perbase_runs: count, scan, emit, read-back of the last call
+    DevArr<uint8_t> d_dist;                                    // gd_depth_hist, gd_region_bins: the region and chunk tables and the counts of the last call (grow-only; gd_api_dist.inc)
+    double dist_secs[3] = {0, 0, 0};                           // ... its upload, kernel and read-back
     double em_secs[3] = {0, 0, 0};                             // gd_emdepth*: upload, kernel, read-back of the last call (gd_api_emdepth.inc)
     PinArr<uint8_t> h_walk;                                    // gd_ingest_decode, gd_covstats_decode: per-segment tables of the record walk (page-locked host memory
                                                                // the walk kernels read and write over the link: no copy command)

@@ -560,6 +560,7 @@ __global__ __launch_bounds__(256) void gd_regions_bounds_kernel(const RegionTab*
 #include "gd_svdlog2.hpp"
 #include "gd_cnveval.hpp"
 #include "gd_perbase_runs.hpp"
+#include "gd_depth_hist.hpp"
 #include "gd_devmat.hpp"
 #include "gd_stage.hpp"
 

@@ -12,6 +12,7 @@
 //   goleft-depth cnveval [-m MINOVERLAP] [-s] truth.bed[.gz] test.bed[.gz]   (the reference's cnveval command: precision and recall of a call set, per size class)
 //   goleft-depth index [-c] [-m N] [-o OUT] a.bam                            (a .bai as htslib writes it, or a .csi, made on the device: no samtools needed)
 //   goleft-depth perbase [-Q Q] [-c CHROM] [-b BED] [--quantize C1,C2,...] [-o OUT] a.bam   (the per-base depth as a bedGraph: runs of equal depth, encoded on the device)
+//   goleft-depth dist [-Q Q] [-c CHROM] [-b BED] [--thresholds T1,T2,...] [--max-depth N] --prefix PREFIX a.bam   (the depth distribution, summary and threshold counts, counted on the device)
 //   goleft-depth samplename [-e] a.bam                                     (goleft samplename: the @RG SM values)
 //   samtools depth -Q q -d D -r REGION in.bam                   (the same program installed under the NAME samtools,
 //                                                                goleft_amd/shim/samtools: an unmodified goleft finds it on PATH)
@@ -43,7 +44,8 @@ static const Entry kEntries[] = {
     {"indexsplit", "indexsplit", gdh_indexsplit_main},  {"emdepth", "emdepth", gdh_emdepth_main},
     {"scales", "scales", gdh_scales_main},              {"debias", "debias", gdh_debias_main},
     {"samplename", "samplename", gdh_samplename_main},  {"cnveval", "cnveval", gdh_cnveval_main},
-    {"index", "index", gdh_index_main},                 {"perbase", "perbase", gdh_perbase_main}};
+    {"index", "index", gdh_index_main},                 {"perbase", "perbase", gdh_perbase_main},
+    {"dist", "dist", gdh_dist_main}};
 
 int main(int argc, char** argv)
 {

@@ -25,10 +25,14 @@
 #include "bam_reader.hpp"
 #include "bam_records.hpp"
 #include "cli.hpp"
+#include "regions.hpp"
 
 namespace {
 
 using gdh::cli::now_s;
+using gdh::regions::parse_cuts;
+using gdh::regions::parse_int;
+using gdh::regions::Region;
 
 struct PArgs {
     int q = 1;                          // -Q, as depth's
@@ -46,38 +50,6 @@ void usage(FILE* f)
           "  --quantize      cut points: runs of equal depth BIN, labelled lo:hi (0:C1, C1:C2, ... Cn:inf); at most 32, increasing, from 1\n"
           "  -o, --out       write here instead of stdout\n"
           "  BAM             coordinate sorted; its .bai or .csi is used when there is one\n", f);
-}
-
-bool parse_int(const std::string& s, int* out)
-{
-    char* end = nullptr;
-    errno = 0;
-    const long v = strtol(s.c_str(), &end, 10);
-    if (s.empty() || errno || *end || v < INT32_MIN || v > INT32_MAX) return false;
-    *out = (int)v;
-    return true;
-}
-
-// --quantize's list; the message names the cause
-bool parse_cuts(const std::string& s, std::vector<int32_t>* cuts, std::string* why)
-{
-    cuts->clear();
-    for (size_t b = 0;;) {
-        const size_t e = s.find(',', b);
-        const std::string tok = s.substr(b, e == std::string::npos ? e : e - b);
-        if (tok.empty()) { *why = "an empty field"; return false; }
-        int v = 0;
-        bool digits = true;
-        for (size_t i = tok[0] == '-' || tok[0] == '+' ? 1 : 0; i < tok.size(); ++i) digits = digits && tok[i] >= '0' && tok[i] <= '9';
-        if (!digits || !parse_int(tok, &v)) { *why = "'" + tok + "' is not an integer"; return false; }
-        if (v < 1) { *why = "cut " + tok + " is below 1"; return false; }
-        if (!cuts->empty() && v <= cuts->back()) { *why = "cut " + tok + " is not above the cut before it"; return false; }
-        cuts->push_back(v);
-        if (cuts->size() > (size_t)GD_PERBASE_MAX_CUTS) { *why = "more than " + std::to_string(GD_PERBASE_MAX_CUTS) + " cuts"; return false; }
-        if (e == std::string::npos) break;
-        b = e + 1;
-    }
-    return true;
 }
 
 // 0 ok, 1 help shown, -1 error (message printed)
@@ -109,38 +81,6 @@ int parse_args(int argc, const char* const* argv, PArgs* a)
     if (pos.empty()) return c.fail("bam is required");
     if (pos.size() > 1) return c.fail("too many positional arguments at '%s'", pos[1].c_str());
     a->bam = pos[0];
-    return 0;
-}
-
-struct Region { int32_t tid; int64_t start, end; };
-
-// -b: every line in file order, parsed as depth parses a region and clipped to its chromosome; blank lines and lines that
-// start with '#' are skipped
-int read_bed(const std::string& path, const std::map<std::string, int>& tid_of, const std::vector<int64_t>& lens, std::vector<Region>* out)
-{
-    gdh::cli::Lines in;
-    if (!in.open(path)) { fprintf(stderr, "perbase: cannot open %s\n", path.c_str()); return 1; }
-    std::string line;
-    std::vector<char> chrom(1 << 16);
-    while (in.next(&line)) {
-        if (line.empty() || line[0] == '#') continue;
-        const std::string nl = line + "\n";
-        int64_t s = 0, e = 0;
-        if (nl.size() >= chrom.size() || gdh_chrom_start_end(nl.c_str(), nl.size(), chrom.data(), chrom.size(), &s, &e) != 0) {
-            fprintf(stderr, "perbase: %s:%lld: cannot get a region from this line\n", path.c_str(), in.lineno);
-            return 1;
-        }
-        const auto it = tid_of.find(chrom.data());
-        if (it == tid_of.end()) {
-            fprintf(stderr, "perbase: %s:%lld: chromosome %s is not in the BAM header\n", path.c_str(), in.lineno, chrom.data());
-            return 1;
-        }
-        const int64_t len = lens[(size_t)it->second];
-        e = std::min(e, len);
-        s = std::min(s, e);
-        if (e < s) e = s;
-        out->push_back(Region{it->second, s, e});
-    }
     return 0;
 }
 
@@ -218,7 +158,7 @@ int run(const PArgs& a, FILE* out)
     std::vector<Region> regions;
     if (!a.chrom.empty() && !tid_of.count(a.chrom)) { fprintf(stderr, "perbase: chromosome %s is not in the BAM header\n", a.chrom.c_str()); return 1; }
     if (!a.bed.empty()) {
-        if (int rc = read_bed(a.bed, tid_of, lens, &regions)) return rc;
+        if (int rc = gdh::regions::read_bed("perbase", a.bed, tid_of, lens, &regions)) return rc;
         if (!a.chrom.empty()) {
             const int32_t only = tid_of[a.chrom];
             regions.erase(std::remove_if(regions.begin(), regions.end(), [&](const Region& r) { return r.tid != only; }), regions.end());

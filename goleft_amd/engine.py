@@ -250,6 +250,41 @@ class DepthEngine:
         self._chk(self._lib.gd_perbase_runs_timing(self._ctx, t, 4))
         return {"count_s": t[0], "scan_s": t[1], "emit_s": t[2], "readback_s": t[3]}
 
+    def _regions(self, tids, starts, ends):
+        """(tid int32, start int64, end int64) arrays of one length from scalars or sequences."""
+        t, s, e = (np.atleast_1d(np.asarray(x)) for x in (tids, starts, ends))
+        if not (t.ndim == s.ndim == e.ndim == 1 and t.shape == s.shape == e.shape):
+            raise ValueError("tids, starts and ends must be scalars or sequences of one length")
+        return np.ascontiguousarray(t, np.int32), np.ascontiguousarray(s, np.int64), np.ascontiguousarray(e, np.int64)
+
+    def depth_hist(self, tids, starts, ends, n_bins: int):
+        """gd_depth_hist: one histogram over all positions of the regions [starts[r], ends[r]) of contigs tids[r] (a
+        single region may be given as scalars): bins[k] counts the positions with min(depth, n_bins - 1) == k.
+        Returns (bins uint64 [n_bins], sum, min, max) -- the last three over the same positions, unclamped, 0 without
+        any."""
+        t, s, e = self._regions(tids, starts, ends)
+        bins = np.zeros(max(int(n_bins), 1), np.uint64)
+        tot, lo, hi = C.c_int64(), C.c_int32(), C.c_int32()
+        self._chk(self._lib.gd_depth_hist(self._ctx, t.size, t.ctypes.data, s.ctypes.data, e.ctypes.data, n_bins, bins.ctypes.data,
+                                          C.byref(tot), C.byref(lo), C.byref(hi)))
+        return bins, tot.value, lo.value, hi.value
+
+    def region_bins(self, tids, starts, ends, cuts=None) -> np.ndarray:
+        """gd_region_bins: uint64 [n_regions, n_cuts + 1]: per region, its positions in each depth bin (the number of
+        cuts <= the depth).  The positions at or above cut k are row[k + 1:].sum()."""
+        t, s, e = self._regions(tids, starts, ends)
+        c = np.ascontiguousarray(cuts if cuts is not None else [], np.int32)
+        out = np.zeros((t.size, c.size + 1), np.uint64)
+        self._chk(self._lib.gd_region_bins(self._ctx, t.size, t.ctypes.data, s.ctypes.data, e.ctypes.data, c.size,
+                                           c.ctypes.data if c.size else None, out.ctypes.data))
+        return out
+
+    def dist_timing(self):
+        """Seconds of the last depth_hist or region_bins call: dict(upload_s, kernel_s, readback_s) (gd_dist_timing)."""
+        t = (C.c_double * 3)()
+        self._chk(self._lib.gd_dist_timing(self._ctx, t, 3))
+        return {"upload_s": t[0], "kernel_s": t[1], "readback_s": t[2]}
+
     def region_windows(self, tid: int, start: int, end: int):
         n = C.c_size_t()
         W = self.params.window_size

@@ -39,7 +39,7 @@ extern "C" {
 
 /* GD_ABI_VERSION changes when an existing entry point or structure changes; GD_ABI_REVISION counts the releases that only
  * ADDED entry points since then (revision 1: gd_indexcov_*; 2: gd_indexsplit_*; 3: gd_crai_sizes).  A caller built against (15, r) runs on any (15, r' >= r).
- * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, gd_sample_medians*, gd_chunk_debias*, gd_device_scale, the *_device entries, gd_moving_debias*, gd_svd_debias* and gd_svd_debias_scaled*, were added without a revision; look them up by symbol.  So were gd_cnveval and gd_cnveval_timing.  So were gd_perbase_runs and gd_perbase_runs_timing.
+ * gd_emdepth, gd_emdepth_cells and gd_emdepth_timing, and after them gd_emcnv_*, gd_sample_medians*, gd_chunk_debias*, gd_device_scale, the *_device entries, gd_moving_debias*, gd_svd_debias* and gd_svd_debias_scaled*, were added without a revision; look them up by symbol.  So were gd_cnveval and gd_cnveval_timing.  So were gd_perbase_runs and gd_perbase_runs_timing.  So were gd_depth_hist, gd_region_bins and gd_dist_timing.
  * Why indexcov did not become version 16: nothing that existed changed, so callers of ABI 15 need not be turned away, and
  * tests/test_host_cpu.py holds gd_abi_version() to 15 until something does change. */
 #define GD_ABI_VERSION 15
@@ -961,6 +961,30 @@ int gd_cnveval_timing(gd_ctx* ctx, double* out, size_t n);
 int gd_perbase_runs(gd_ctx* ctx, int32_t tid, int64_t start, int64_t end, int n_cuts, const int32_t* cuts /* [n_cuts] or NULL */,
                     uint32_t* run_start, int32_t* run_value, size_t cap, size_t* n);
 int gd_perbase_runs_timing(gd_ctx* ctx, double* out, size_t n);
+/* ---- the per-base vector reduced along the depth axis: what mosdepth's *.dist.txt, *.summary.txt
+ * and *.thresholds.bed are made of, counted on the device so that a few kilobytes cross the link.  After a gd_compute with
+ * GD_OUT_PERBASE.  Region r is [start[r], end[r]) on contig tid[r], 0 <= start <= end <= that contig's length; regions may
+ * overlap, repeat, be empty and come in any order, and n_regions == 0 is GD_OK.
+ *   gd_depth_hist   one histogram over the multiset of all positions of all regions (a position that two regions hold counts
+ *                   twice): bins[k] = the number of positions p with min(d[p], n_bins - 1) == k, 1 <= n_bins <=
+ *                   GD_DEPTH_HIST_MAX_BINS; *sum = the sum of d[p], *min and *max over the same positions, not clamped.  Each
+ *                   of sum, min, max may be NULL.  Without a position every bin, *sum, *min and *max are 0.
+ *   gd_region_bins  for every region on its own: counts[r * (n_cuts + 1) + b] = the number of its positions whose number of
+ *                   cuts <= d[p] is b (gd_perbase_runs' value with cuts, and its rules for them).  n_cuts == 0: one column,
+ *                   the region's length.  The number of positions at or above cut k is the sum of columns k + 1 .. n_cuts.
+ * Both are exact integer counts: two calls give the same numbers.  The checks and their order are gd_perbase_runs':
+ * GD_E_RANGE: a region outside 0 <= start <= end <= len, a tid that is none or was not selected, more positions than one
+ * call takes (2^31 - 16 chunks of 4096 on each region's 16-byte grid); GD_E_INVALID: n_bins out of range, bad cuts, a NULL
+ * that is needed; GD_E_STATE: before a compute, while one is in flight, or computed without GD_OUT_PERBASE.  Everything is
+ * checked before anything is allocated or launched, and a refused call leaves the context and the outputs as they were.
+ * gd_dist_timing: seconds of the last call of either (measurement only): the tables' upload with the zeroing, the kernel,
+ * the read-back.  Fills min(n, 3) values.  Added without a revision, as the entry points before them. */
+#define GD_DEPTH_HIST_MAX_BINS 65536
+int gd_depth_hist(gd_ctx* ctx, size_t n_regions, const int32_t* tid, const int64_t* start, const int64_t* end,
+                  int32_t n_bins, uint64_t* bins /* [n_bins] */, int64_t* sum, int32_t* min, int32_t* max);
+int gd_region_bins(gd_ctx* ctx, size_t n_regions, const int32_t* tid, const int64_t* start, const int64_t* end,
+                   int n_cuts, const int32_t* cuts /* [n_cuts] or NULL */, uint64_t* counts /* [n_regions][n_cuts + 1] */);
+int gd_dist_timing(gd_ctx* ctx, double* out, size_t n);
 int gd_ingest_abort(gd_ctx* ctx);
 /* Page-locked host memory for the byte range handed to gd_ingest_bgzf (read the file
  * straight into it: the H2D copy then runs at PCIe speed instead of through a bounce

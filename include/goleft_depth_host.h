@@ -284,6 +284,29 @@ int gdh_perbase_main(int argc, const char* const* argv);
 /* Same, writing to out_path (NULL = stdout, or -o). */
 int gdh_perbase_run(int argc, const char* const* argv, const char* out_path);
 
+/* ---- `dist`: the depth distribution, the summary and the threshold counts of a BAM, counted on the device (gd_depth_hist,
+ * gd_region_bins).  argv: [-Q Q] [-c CHROM] [-b regions.bed] [--thresholds T1,T2,...] [--max-depth N]
+ * --prefix PREFIX in.bam.  The BAM is read exactly as `perbase` reads it, on one device.  Depths above N (1 .. 65535, the
+ * default) count as N.  Files, in mosdepth's layouts with this project's definitions:
+ *   PREFIX.dist.txt         `scope \t depth \t fraction`: per wanted contig of non-zero length in header order, then `total`,
+ *                           a line per depth from min(N, the scope's highest depth) down to 0; fraction = %.6f of (positions
+ *                           at that clamped depth or above) / (positions); a scope without positions has no lines
+ *   PREFIX.summary.txt      header `chrom length bases mean min max`, a row per wanted contig, then `total`: bases = the sum
+ *                           of the depths, mean = %.2f of bases / length (0.00 for length 0), min and max unclamped
+ *   PREFIX.region.dist.txt  with -b: the same over the BED's lines (parsed, clipped and refused as `perbase -b` does; every
+ *                           line on its own, so overlaps count repeatedly), per contig that has lines, then `total`; the
+ *                           summary gains a `<chrom>_region` row behind each such contig's and a last `total_region` row,
+ *                           length being the sum of the clipped line lengths
+ *   PREFIX.thresholds.bed   with --thresholds (at most 32, increasing, from 1; needs -b): header `#chrom start end region
+ *                           <T>X ...`, a row per BED line in file order with clipped coordinates, its fourth tab-separated
+ *                           field or `unknown`, and per threshold its positions at that depth or above
+ * GOLEFT_DIST_TIMING=1: where the time went, on stderr.  Returns the exit code: 1, with the cause named, nothing written and
+ * no device opened, for whatever `perbase` refuses and for a missing --prefix, a prefix whose directory cannot be written
+ * to, a bad --max-depth, a bad --thresholds list
+ * and --thresholds without -b. ------------------------------------------------------------------------------------------ */
+int gdh_dist_main(int argc, const char* const* argv);
+int gdh_dist_run(int argc, const char* const* argv);
+
 /* ---- `index`: a BAM's .bai (SAMv1 5.2) as htslib's indexer writes it, made on the device (gd_index_*; DESIGN.md section
  * 3.19).  argv: [-o OUT.bai] in.bam; the index goes to in.bam.bai, or to -o, through a temporary file and a rename.
  * GOLEFT_INDEX_TIMING=1 prints where the time went on stderr; GOLEFT_INDEX_RANGE_BYTES, GOLEFT_INDEX_SLICE and
